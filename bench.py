@@ -240,7 +240,15 @@ class Workload:
         # device-resident rollout: the step is enqueued on a torch stream and its outputs are consumed on that stream
         self.shard = TorchShard(self.venv, pipelined=pipelined)
         self.act_buf = torch.empty(n, self.act_dim, device=f"cuda:{local_rank}", dtype=torch.float32)
+        self.seed = 1 + rank * n
         self.draw = 0
+        self.last = None        # what the last step of the last timed window returned (obs, reward, done, info)
+
+    def rewind(self):
+        """The envs' RNG streams and the policy's draw counter back to where the constructor left them, so that a window opened by the
+        reset that follows sees the same inputs however many untimed steps (the time-bounded spin-up) ran before it."""
+        self.venv.seed(self.seed)
+        self.draw, self._fused_synced = 0, False
 
     def actions(self):
         """action_space.sample() for the whole batch: U[-0.25, 0.25), one device kernel on the env's stream (tg_sample_actions, counter
@@ -280,8 +288,10 @@ class Workload:
     def _timed(self, env, steps, barrier, flush=None):
         barrier()
         t0 = time.perf_counter()
+        out = None
         for _ in range(steps):
-            self.step(env)
+            out = self.step(env)
+        self.last = out
         self.flushed, self.error = None, None
         if flush is not None:
             try:
@@ -418,6 +428,33 @@ def read_traffic(env_id, n, image_size, key, ab):
     return None
 
 
+DUMP_MAX_ENVS = 256              # --dump-outputs: observations of at most this many envs (a fixed, seeded sample of the batch) ...
+DUMP_OBS_BYTES = 48 << 20       # ... and at most this many bytes of them (float32); rewards and dones of every env on top
+
+
+def dump_outputs(out_dir, obs, rew, done, sample_seed=0):
+    """Writes one step's outputs as `out_dir`/<name>.npy: `reward` and `done` of every env, each observation array of `obs` for a sample of
+    the envs drawn with numpy's default_rng(sample_seed) (their indices in `env_index`).  Every value is kept exactly: float32 and narrow
+    integers / booleans (uint8 images, done flags) as float32, everything else as float64.  Returns {name: bytes written}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = int(rew.shape[0])
+    per_env = sum(int(v[0].numel()) * max(v.element_size(), 4) for v in obs.values()) if n else 0
+    k = max(1, min(n, DUMP_MAX_ENVS, DUMP_OBS_BYTES // max(per_env, 1)))
+    idx = np.sort(np.random.default_rng(sample_seed).choice(n, size=k, replace=False))
+    arrays = {"env_index": idx, "reward": rew, "done": done}
+    for name, v in obs.items():
+        arrays[name] = v.index_select(0, torch.from_numpy(idx).to(v.device))
+    sizes = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        a = a.astype(np.float32 if a.dtype == np.float32 or (a.dtype.kind in "biu" and a.dtype.itemsize <= 2) else np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        sizes[name] = a.nbytes
+    return sizes
+
+
 def guard_report(w, env, steps, barrier):
     """The broadphase guard over `steps` further steps of the rollout with the check as a node of every step (tg_set_broadphase; survey row n2):
     how many env states were checked, how many unexpected pairs Bullet's broadphase would have handed to its narrowphase (world AABBs overlap) and
@@ -525,7 +562,12 @@ def main():
                     help="untimed device spin-up BEFORE the reset + W warm-up steps + K timed steps: the same rollout stepped for this many milliseconds, so "
                          "that a short window (the driver's W = 5, K = 20 is 1 ms of device time) does not sit on the clock ramp of a part that has just "
                          "been idle; reported as pre_warm_ms / pre_warm_steps; 0 switches it off")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what their last step returned (observations of a fixed sample of envs, every env's reward and "
+                         "done) as DIR/<name>.npy in float32 / float64; the same arguments give the same inputs, so two builds can be compared")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or os.environ.get("TG_BENCH_SPAWN") == "1"):   # TG_BENCH_SPAWN: the same path with one rank (1-GPU test)
@@ -606,6 +648,8 @@ def main():
                     k_pw += 50
                     torch.cuda.synchronize()
                 pre_warm["steps"], pre_warm["ms"] = k_pw, round(1e3 * (time.perf_counter() - t_pw), 1)
+            if steps is None:
+                w.rewind()                                 # the timed window's inputs do not depend on how long the spin-up ran
             e.reset()
             for _ in range(warmup):
                 w.step(e)
@@ -667,6 +711,10 @@ def main():
             except Exception:  # noqa: BLE001
                 pass
             env, dt, verified, why = measure("collective", "auto" if args.payload == "tiles" else args.payload, min(args.warmup, 10))
+    if args.dump_outputs and rank == 0:
+        # what the timed path handed its caller in its last step: rank 0's gathered batch, or the shard's own outputs
+        obs, rew, done = w.flushed[:3] if w.flushed is not None else w.last[:3]
+        dump_outputs(args.dump_outputs, obs, rew, done)
     with w.on_stream():
         no_gather = None
         if gathered and world > 1:               # the same K steps without the exchange: what per-rank learners would see

@@ -49,3 +49,28 @@ def test_algorithmic_bytes_follow_survey_8d():
     assert bench.algo_bytes("object_balance-v0", 256) == 256 * 256 + 300
     assert bench.algo_bytes("surface_follow-v0", 128) > 2 * 128 * 128
     assert bench.algo_bytes("object_push-v0", 128) == 128 * 128 + 400
+
+
+def test_dump_outputs_writes_float_arrays_of_a_fixed_sample_within_64_mb(tmp_path):
+    """--dump-outputs: every file is float32 / float64, the observation sample is the same on every call and the whole dump stays under
+    64 MB even for the largest images (object_balance at 256 x 256)."""
+    import numpy as np
+    import torch
+    n = 1024
+    g = torch.Generator().manual_seed(0)
+    obs = {"tactile": torch.randint(0, 256, (n, 256, 256, 1), dtype=torch.uint8, generator=g),
+           "extended_feature": torch.randn(n, 12, dtype=torch.float32, generator=g)}
+    rew = torch.randn(n, dtype=torch.float32, generator=g)
+    done = torch.randint(0, 2, (n,), dtype=torch.uint8, generator=g)
+    sizes = bench.dump_outputs(str(tmp_path / "a"), obs, rew, done)
+    bench.dump_outputs(str(tmp_path / "b"), obs, rew, done)
+    assert sum(sizes.values()) <= 64 << 20
+    assert set(sizes) == {"env_index", "reward", "done", "tactile", "extended_feature"}
+    for name in sizes:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    idx = np.load(tmp_path / "a" / "env_index.npy").astype(np.int64)
+    assert len(idx) > 0 and len(set(idx.tolist())) == len(idx) and idx.min() >= 0 and idx.max() < n
+    assert np.array_equal(np.load(tmp_path / "a" / "tactile.npy"), obs["tactile"].numpy()[idx].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "a" / "reward.npy"), rew.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "done.npy"), done.numpy().astype(np.float32))

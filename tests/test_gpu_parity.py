@@ -1361,6 +1361,32 @@ def test_bench_falls_back_to_the_rccl_gather_when_the_ipc_exchange_fails():
     assert d["value"] > 0 and d["rccl_ranks"] == 1
 
 
+def test_bench_dumps_the_same_outputs_whatever_the_spin_up(tmp_path):
+    """--dump-outputs: two runs with the same arguments but spin-ups of different lengths (so a different number of untimed steps before the
+    window) write the same last-step outputs, bit for bit; the window crosses an auto-reset (episodes of 200 steps), every file is float32 /
+    float64 and the dump stays under 64 MB."""
+    import json, os, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for tag, pre_warm in (("a", "400"), ("b", "50")):
+        d = tmp_path / tag
+        out = _run_bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "230", "--warmup", "5", "--num-envs", "256",
+                          "--no-cpu-baseline", "--no-literal", "--no-companions", "--pre-warm-ms", pre_warm, "--dump-outputs", str(d)], root, dict(os.environ), f"dump_{tag}")
+        assert out.returncode == 0, out.stderr[-12000:]
+        line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == 230 and line["ms_per_step"] > 0 and line["resets_in_timed_region"] is True
+        runs.append(d)
+    names = sorted(os.listdir(runs[0]))
+    assert names == sorted(os.listdir(runs[1])) and {"tactile.npy", "reward.npy", "done.npy", "env_index.npy"} <= set(names)
+    total = 0
+    for name in names:
+        a, b = np.load(runs[0] / name), np.load(runs[1] / name)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and np.array_equal(a, b), name
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(runs[0] / "reward.npy").shape == (256,) and np.load(runs[0] / "tactile.npy").std() > 0
+
+
 def test_sample_actions_is_a_counter_based_uniform_box_sample(edge_modes):
     """tg_sample_actions = action_space.sample() for the batch: float32 in [min_action, max_action), a function of (seed, counter,
     element) only, flat histogram."""
