@@ -10,6 +10,8 @@
 
 #include <stdint.h>
 
+#include "tactile_gym_hip.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -37,6 +39,37 @@ int tg_selftest_penetration_division(int64_t* mismatches);
  * called covered in which some pixel fails the pixel loops' coverage predicate (must be 0), out[4] = rectangles called covered, out[5] =
  * rectangles whose every pixel passes.  out: int64 [6]. */
 int tg_selftest_edge_exclusion(int64_t n, uint64_t seed, int64_t* out);
+
+/* The tactile render (tg_render_tactile / tg_render_tactile_heightfield) with a chosen raster kernel.  TG_RK_AUTO = the product's choice
+ * (csrc/tg_raster.hip: choose_render_kernel); any other id is launched if it can draw the input and refused (-1, nothing launched) if not:
+ * the block kernel above 32 triangles, 128-wide tiles on a 64-wide image, a heightfield kernel for a mesh, and so on. */
+enum {
+    TG_RK_AUTO = 0,
+    TG_RK_BLOCKS = 1,           /* k_render_blocks<16>: meshes of <= 32 triangles, 128-multiple images */
+    TG_RK_SMALL_QREJ = 2,       /* k_render_small<128,64,2,true>: meshes of <= 256 triangles, with the per-quad reject */
+    TG_RK_SMALL = 3,            /* k_render_small<128,64,2,false>: the same without it (every shared mesh of the product) */
+    TG_RK_HF_BANDS = 4,         /* k_render_tactile<128,64,true>: heightfields, bounding-box band masks */
+    TG_RK_HF_CELLS = 5,         /* k_render_tactile<128,64,true,true>: heightfields, edge-function cell masks */
+    TG_RK_TACTILE_128 = 6,      /* k_render_tactile<128,128,false>: 128-multiple images */
+    TG_RK_TACTILE_64 = 7,       /* k_render_tactile<64,64,false>: 64-multiple images */
+    TG_RK_SCATTER_128 = 8,      /* k_render_scatter<128,128>: meshes, 128-multiple images */
+    TG_RK_SCATTER_64 = 9        /* k_render_scatter<64,64>: meshes, 64-multiple images */
+};
+/* The kernel launch_render would launch (*chosen; -1: the forced one cannot draw the input) for a mesh, or (mesh NULL) a rows x cols
+ * heightfield of spacing grid_scale, with the stimulus flags skip_quad_reject / fills_view / backface_cull (Stimulus::closed_outward; -1 when
+ * asked for a mesh that is not closed and outward).  Host only: needs no device. */
+int tg_selftest_render_kernel(const tg_sensor* sensor, const tg_mesh* mesh, int32_t rows, int32_t cols, double grid_scale, int32_t kernel,
+                              int32_t skip_quad_reject, int32_t fills_view, int32_t backface_cull, int32_t* chosen);
+/* Draws n images (1..65535) as the above with kernel `kernel`; *launched = the kernel launched.  heights [n][rows*cols], zoff [n]: the
+ * heightfield when mesh is NULL.  out [n][H][W] is in / out: an env whose mask byte is 0 (mask NULL: all drawn) keeps what it held.
+ * term_xf [n][12], term_mask [n], term_out [n][H][W] (all or none): the fused auto-reset's terminal layer - envs flagged in term_mask (and
+ * in mask) also get the image of term_xf in term_out, the others keep what term_out held. */
+int tg_selftest_render(const tg_sensor* sensor, const tg_mesh* mesh, int32_t rows, int32_t cols, double grid_scale, const double* heights,
+                       const float* zoff, int32_t n, const float* xf, int32_t kernel, int32_t skip_quad_reject, int32_t fills_view,
+                       int32_t backface_cull, const uint8_t* mask, const float* term_xf, const uint8_t* term_mask, uint8_t* term_out,
+                       uint8_t* out, int32_t* launched);
+/* The message of the last failing call of this library on the calling thread. */
+const char* tg_selftest_last_error(void);
 
 #ifdef __cplusplus
 }

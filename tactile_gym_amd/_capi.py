@@ -265,7 +265,16 @@ TEST_SYMBOLS = {
     "tg_selftest_division": (C.c_int, [C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
     "tg_selftest_penetration_division": (C.c_int, [C.POINTER(C.c_int64)]),
     "tg_selftest_edge_exclusion": (C.c_int, [C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
+    "tg_selftest_render_kernel": (C.c_int, [C.POINTER(TgSensor), C.POINTER(TgMesh), C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "tg_selftest_render": (C.c_int, [C.POINTER(TgSensor), C.POINTER(TgMesh), C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                     C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "tg_selftest_last_error": (C.c_char_p, []),
 }
+# raster kernel ids of tg_selftest_render (TG_RK_*)
+RK_AUTO, RK_BLOCKS, RK_SMALL_QREJ, RK_SMALL, RK_HF_BANDS, RK_HF_CELLS, RK_TACTILE_128, RK_TACTILE_64, RK_SCATTER_128, RK_SCATTER_64 = range(10)
 _test_lib = None
 
 

@@ -99,6 +99,7 @@ int tg_inverse_kinematics(const tg_robot* robot, int32_t dtype, int32_t n, const
 
 int tg_render_tactile(const tg_sensor* sen, const tg_mesh* mesh, int32_t n, const float* xf, uint8_t* out) {
     if (!sen || !mesh || !xf || !out) return fail(-1, "NULL argument");
+    if (n < 0 || n > 65535) return fail(-1, "n must be in 0..65535 (the render launch carries the env index in grid.y)");
     if (int rc = need_device()) return rc;
     const int H = sen->image_h, W = sen->image_w;
     if (!((H % 128 == 0 && W % 128 == 0) || (H == 64 && W == 64))) return fail(-1, "image size must be 64x64 or a multiple of 128");
@@ -129,6 +130,7 @@ int tg_render_tactile(const tg_sensor* sen, const tg_mesh* mesh, int32_t n, cons
         TG_HIP(hipMemcpy(sp.p, soup.data(), soup.size() * 4, hipMemcpyHostToDevice));
     }
     S.kind = 0; S.verts = (const float*)vv.p; S.tris = (const int32_t*)tt.p; S.soup = (const float*)sp.p; S.n_tris = mesh->n_tris;
+    S.skip_quad_reject = 1;   // what tg_create sets for every shared mesh, so that this entry draws with the kernels the environments launch
     launch_render(P, S, (const float*)xx.p, 0, n, nullptr, (const float*)nd.p, (const uint8_t*)ng.p, (const uint8_t*)bm.p, (uint8_t*)oo.p, nullptr, nullptr, nullptr, nullptr, 0);
     TG_HIP(hipDeviceSynchronize());
     TG_HIP(hipMemcpy(out, oo.p, npix * n, hipMemcpyDeviceToHost));
@@ -138,6 +140,7 @@ int tg_render_tactile(const tg_sensor* sen, const tg_mesh* mesh, int32_t n, cons
 int tg_render_tactile_heightfield(const tg_sensor* sen, int32_t rows, int32_t cols, double grid_scale, int32_t n, const double* heights,
                                   const float* zoff, const float* xf, uint8_t* out) {
     if (!sen || !heights || !zoff || !xf || !out) return fail(-1, "NULL argument");
+    if (n < 0 || n > 65535) return fail(-1, "n must be in 0..65535 (the render launch carries the env index in grid.y)");
     if (int rc = need_device()) return rc;
     const int H = sen->image_h, W = sen->image_w;
     if (!((H % 128 == 0 && W % 128 == 0) || (H == 64 && W == 64))) return fail(-1, "image size must be 64x64 or a multiple of 128");

@@ -48,7 +48,29 @@ struct Stimulus {
                               // back faces are dropped at set-up for envs whose stimulus lies wholly beyond the near plane
     int fills_view;           // mesh: the stimulus covers the whole image in every frame (object_balance's plate on the sensor): launch_render keeps it off the block kernel
     int win_side;             // heightfield: largest side (in vertices) the frustum window can have (set by launch_render): sizes the LDS staging
+    int force_kernel;         // tests only (tg_selftest_render): a RenderKernel to launch instead of launch_render's choice; 0 (kRkAuto: the
+                              // product's value, what Stimulus{} holds) = the choice
 };
+
+// The raster kernels launch_render can launch (the ids are the test library's TG_RK_* values, include/tactile_gym_hip_test.h).
+enum RenderKernel : int {
+    kRkAuto = 0,
+    kRkBlocks = 1,          // k_render_blocks<16>
+    kRkSmallQrej = 2,       // k_render_small<128,64,2,true>
+    kRkSmall = 3,           // k_render_small<128,64,2,false>
+    kRkHfBands = 4,         // k_render_tactile<128,64,true>
+    kRkHfCells = 5,         // k_render_tactile<128,64,true,true>
+    kRkTactile128 = 6,      // k_render_tactile<128,128,false>
+    kRkTactile64 = 7,       // k_render_tactile<64,64,false>
+    kRkScatter128 = 8,      // k_render_scatter<128,128>
+    kRkScatter64 = 9,       // k_render_scatter<64,64>
+};
+
+// launch_render's choice for (P, S): S.force_kernel when it is set and can draw the input, -1 when it cannot (then launch_render launches
+// nothing).  Host only, no device access: P.blockmax / P.tmpl are only tested for null.  S.win_side is not read (heightfield_win_side).
+int choose_render_kernel(const RasterParams& P, const Stimulus& S);
+// Heightfield: the largest side (in vertices) the frustum window of k_render_tactile can have, for any camera orientation (Stimulus::win_side).
+int heightfield_win_side(const RasterParams& P, const Stimulus& S);
 
 RasterParams make_raster_params(int W, int H, double fov_deg, double near_, double far_, int turn_off_border, const float* nodef_dep_host);
 
@@ -61,7 +83,8 @@ void make_gray_u8(const float* nodef_gray_host, int npix, uint8_t* out_host);
 
 // term_xform / term_mask / term_out (all or none): for the envs whose term_mask byte is non-zero the kernel first draws the image of
 // term_xform (same SoA layout as xform) into term_out, then the regular one: the fused auto-reset of tg_step.
-void launch_render(const RasterParams& P, const Stimulus& stim, const float* xform, int xform_soa, int n_envs,
+// Returns the RenderKernel launched, -1 (nothing launched) when S.force_kernel cannot draw the input.
+int launch_render(const RasterParams& P, const Stimulus& stim, const float* xform, int xform_soa, int n_envs,
                    const uint8_t* mask, const float* nodef_dep, const uint8_t* gray_u8, const uint8_t* border, uint8_t* out,
                    uint8_t* save_prev, const float* term_xform, const uint8_t* term_mask, uint8_t* term_out, hipStream_t stream);
 

@@ -15,7 +15,7 @@
 //     records in LDS; the pixel phase then reads each record as an LDS broadcast;
 //   * each lane owns quads of 4 horizontally adjacent pixels whose depth values stay in VGPRs (the z-buffer): depth reduction is a
 //     register min, the reference images are read as 16-byte vectors and the uint8 image is written as 4-byte vectors;
-//   * four kernels, chosen per stimulus by launch_render:
+//   * four kernels (nine instantiations), chosen per stimulus by choose_render_kernel:
 //       k_render_blocks<16>        meshes of up to 32 triangles whose image is mostly the untouched sensor's (edge, cube): ONE workgroup per
 //                                  128 x 128 region, 16 x 16 pixel blocks, depth-plane block culls, only changed blocks written (see there);
 //       k_render_small<128,64,2>   the pole's plate (fills the view) and meshes of 33-256 triangles: 128 x 64 tiles, the pixel phase in two
@@ -1196,82 +1196,117 @@ void make_gray_u8(const float* nodef_gray_host, int npix, uint8_t* out_host) {
     for (int i = 0; i < npix; ++i) out_host[i] = (uint8_t)nodef_gray_host[i];   // the truncating cast of tactile_sensor.py:291-292
 }
 
-void launch_render(const RasterParams& P, const Stimulus& S_in, const float* xform, int xform_soa, int n_envs,
-                   const uint8_t* mask, const float* nodef_dep, const uint8_t* gray_u8, const uint8_t* border, uint8_t* out,
-                   uint8_t* save_prev, const float* term_xform, const uint8_t* term_mask, uint8_t* term_out, hipStream_t stream) {
-    Stimulus S = S_in;
-    S.win_side = 0;
-    if (S.kind == 1) {
-        // side of the frustum window (k_render_tactile) for any camera orientation: the truncated pyramid lies within the sphere of radius
-        // |apex - far corner| about the camera, so its xy box is at most 2 R wide; + 2 x 2 cells widening, + floor / ceil, + 1 (vertices)
-        const double w_cull = 1.01 * ((double)P.C1 / (((double)P.zcull + 2.0 * (double)kDepthSlack) - (double)P.C0));
-        const double ex = w_cull * ((double)P.hw / (double)P.kx), ey = w_cull * ((double)P.hh / (double)P.ky);
-        const double R = std::sqrt(ex * ex + ey * ey + w_cull * w_cull);
-        int side = (int)std::ceil(2.0 * R / (double)S.scale) + 8;
-        const int full = S.rows > S.cols ? S.rows : S.cols;
-        S.win_side = (side < full && side > 0) ? side : full;
+int heightfield_win_side(const RasterParams& P, const Stimulus& S) {
+    // side of the frustum window (k_render_tactile) for any camera orientation: the truncated pyramid lies within the sphere of radius
+    // |apex - far corner| about the camera, so its xy box is at most 2 R wide; + 2 x 2 cells widening, + floor / ceil, + 1 (vertices)
+    const double w_cull = 1.01 * ((double)P.C1 / (((double)P.zcull + 2.0 * (double)kDepthSlack) - (double)P.C0));
+    const double ex = w_cull * ((double)P.hw / (double)P.kx), ey = w_cull * ((double)P.hh / (double)P.ky);
+    const double R = std::sqrt(ex * ex + ey * ey + w_cull * w_cull);
+    int side = (int)std::ceil(2.0 * R / (double)S.scale) + 8;
+    const int full = S.rows > S.cols ? S.rows : S.cols;
+    return (side < full && side > 0) ? side : full;
+}
+
+// Can kernel k draw (P, S)?  Tile sizes divide the image; the block kernel needs its tables and holds <= 64 records (32 triangles) in one
+// round, k_render_small all of its records (rblocks[512]: <= 256 triangles); the banded kernels and the scatter kernel take one stimulus kind.
+static bool kernel_can_draw(int k, const RasterParams& P, const Stimulus& S) {
+    const bool r128 = P.W % 128 == 0 && P.H % 128 == 0, r64 = P.W % 64 == 0 && P.H % 64 == 0, mesh = S.kind == 0;
+    switch (k) {
+    case kRkBlocks: return r128 && mesh && S.n_tris <= 32 && P.blockmax != nullptr && P.tmpl != nullptr;
+    case kRkSmallQrej: case kRkSmall: return r128 && mesh && S.n_tris <= 256;
+    case kRkHfBands: case kRkHfCells: return r128 && !mesh;
+    case kRkTactile128: return r128;
+    case kRkTactile64: return r64;
+    case kRkScatter128: return r128 && mesh;
+    case kRkScatter64: return r64 && mesh;
+    default: return false;
     }
-    int rec_cap = 2 * S.n_tris;
-    static const bool scatter_off = getenv("TG_NO_SCATTER_RASTER") != nullptr;   // A/B switch for the parity test
-    rec_cap = rec_cap > kBatch ? kBatch : (rec_cap < 2 ? 2 : rec_cap);
-    if (S.kind == 1 && rec_cap > 256) rec_cap = 256;   // a dozen heightfield triangles survive the depth cull; more just take another round
-    const size_t wcap = S.kind == 1 ? (((size_t)S.win_side * S.win_side + 3) & ~(size_t)3) : 0;
-    const size_t lds = (size_t)rec_cap * sizeof(TriRec) + (S.kind == 1 ? wcap * (2 * sizeof(float) + 2 * sizeof(unsigned short) + 1) + (size_t)rec_cap * sizeof(unsigned) + 16 : 0);
+}
+
+int choose_render_kernel(const RasterParams& P, const Stimulus& S) {
+    if (S.force_kernel != kRkAuto) return kernel_can_draw(S.force_kernel, P, S) ? S.force_kernel : -1;
+    static const bool scatter_off = getenv("TG_NO_SCATTER_RASTER") != nullptr;   // A/B measurements: the marble on k_render_tactile
+    static const bool blocks_off = getenv("TG_NO_BLOCK_RASTER") != nullptr;      // A/B measurements: the edge / cube on k_render_small
     if (P.W % 128 == 0 && P.H % 128 == 0) {
-        if (S.kind == 0 && S.n_tris <= 256 && rec_cap >= 2 * S.n_tris) {
+        if (S.kind == 0 && S.n_tris <= 256) {
             // a small shared mesh (edge, cube, pole): every triangle fits the record buffer in one round -> the two-pass kernel with
             // 16 x 16 pass blocks on 128 x 64 tiles, whatever the launch size (16 384 envs: 0.75 -> 0.42 ms against 128 x 128 tiles)
             // up to 32 triangles whose image is mostly the untouched sensor's (edge, cube): the block kernel; a stimulus that fills the view
             // (the pole's plate: every block is drawn, nothing to skip) stays with the two-pass kernel below (256 x 256: 0.151 against 0.157 ms)
-            static const bool blocks_off = getenv("TG_NO_BLOCK_RASTER") != nullptr;   // A/B switch (parity test, measurements)
-            if (P.blockmax != nullptr && P.tmpl != nullptr && S.n_tris <= 32 && !S.fills_view && !blocks_off) {
-                dim3 gb((P.W / 128) * (P.H / 128), n_envs, term_xform ? 2 : 1);
-                hipLaunchKernelGGL((k_render_blocks<kBlockW>), gb, dim3(kThreads), lds, stream, P, S, xform, xform_soa, n_envs, mask,
-                                   nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
-                return;
-            }
-            // (the terminal image as a second pass of the env's own workgroups instead of a grid layer of its own - 8 192 workgroups per launch
-            //  that start, look and leave - was measured in round 5: the pass loop costs the kernel more registers than the layer costs time,
-            //  render 108 -> 125 us at 256 x 256; not kept)
-            dim3 grid((P.W / 128) * (P.H / 64), n_envs, term_xform ? 2 : 1);
-            if (S.skip_quad_reject)
-                hipLaunchKernelGGL((k_render_small<128, 64, 2, false>), grid, dim3(kThreads), lds, stream, P, S, xform, xform_soa, n_envs, mask,
-                                   nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
-            else
-                hipLaunchKernelGGL((k_render_small<128, 64, 2, true>), grid, dim3(kThreads), lds, stream, P, S, xform, xform_soa, n_envs, mask,
-                                   nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
-        } else {
-            dim3 grid((P.W / 128) * (P.H / 128), n_envs, term_xform ? 2 : 1);
-            if (S.kind == 1) {   // heightfield: 128 x 64 tiles (the per-workgroup staging is cheap since it is windowed: 0.108 -> 0.098 ms)
-                dim3 g2((P.W / 128) * (P.H / 64), n_envs, term_xform ? 2 : 1);
-                static const bool dbg_win = getenv("TG_DEBUG_WIN") != nullptr;
-                if (dbg_win) fprintf(stderr, "heightfield window side %d cells\n", S.win_side);
-                // a narrow view (DIGIT over the horizontal surface: a window of a few cells) leaves few records per tile: there the per-record
-                // cell masks pay (render 63 -> 57 us); a wide one (TacTip over the vertical surface) has hundreds of records and keeps the
-                // bounding-box bands - as its own instantiation, the cell code costs that kernel registers even when it is switched off
-                if (kEdgeReach && S.win_side <= kCellsWinSide)
-                    hipLaunchKernelGGL((k_render_tactile<128, 64, true, true>), g2, dim3(kThreads), lds, stream, P, S, xform, xform_soa, n_envs, mask,
-                                       nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
-                else
-                hipLaunchKernelGGL((k_render_tactile<128, 64, true>), g2, dim3(kThreads), lds, stream, P, S, xform, xform_soa, n_envs, mask,
-                                   nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
-            } else if (!scatter_off)   // a shared mesh of many small triangles (the marble): triangle-parallel, LDS z-buffer
-                hipLaunchKernelGGL((k_render_scatter<128, 128>), grid, dim3(kThreads), 0, stream, P, S, xform, xform_soa, n_envs, mask,
-                                   nodef_dep, gray_u8, border, out, save_prev, term_xform, term_mask, term_out);
-            else
-                hipLaunchKernelGGL((k_render_tactile<128, 128, false>), grid, dim3(kThreads), lds, stream, P, S, xform, xform_soa, n_envs, mask,
-                                   nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
+            if (P.blockmax != nullptr && P.tmpl != nullptr && S.n_tris <= 32 && !S.fills_view && !blocks_off) return kRkBlocks;
+            return S.skip_quad_reject ? kRkSmall : kRkSmallQrej;
         }
-    } else {  // 64x64 images
-        dim3 grid((P.W / 64) * (P.H / 64), n_envs, term_xform ? 2 : 1);
-        if (S.kind == 0 && S.n_tris > 256 && !scatter_off) {
-            hipLaunchKernelGGL((k_render_scatter<64, 64>), grid, dim3(kThreads), 0, stream, P, S, xform, xform_soa, n_envs, mask,
-                               nodef_dep, gray_u8, border, out, save_prev, term_xform, term_mask, term_out);
-            return;
-        }
-        hipLaunchKernelGGL((k_render_tactile<64, 64, false>), grid, dim3(kThreads), lds, stream, P, S, xform, xform_soa, n_envs, mask,
-                           nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
+        if (S.kind == 1)
+            // a narrow view (DIGIT over the horizontal surface: a window of a few cells) leaves few records per tile: there the per-record
+            // cell masks pay (render 63 -> 57 us); a wide one (TacTip over the vertical surface) has hundreds of records and keeps the
+            // bounding-box bands - as its own instantiation, the cell code costs that kernel registers even when it is switched off
+            return (kEdgeReach && heightfield_win_side(P, S) <= kCellsWinSide) ? kRkHfCells : kRkHfBands;
+        return scatter_off ? kRkTactile128 : kRkScatter128;   // a shared mesh of many small triangles (the marble): triangle-parallel, LDS z-buffer
     }
+    return (S.kind == 0 && S.n_tris > 256 && !scatter_off) ? kRkScatter64 : kRkTactile64;   // 64 x 64 images
+}
+
+int launch_render(const RasterParams& P, const Stimulus& S_in, const float* xform, int xform_soa, int n_envs,
+                  const uint8_t* mask, const float* nodef_dep, const uint8_t* gray_u8, const uint8_t* border, uint8_t* out,
+                  uint8_t* save_prev, const float* term_xform, const uint8_t* term_mask, uint8_t* term_out, hipStream_t stream) {
+    const int k = choose_render_kernel(P, S_in);
+    if (k < 0) return -1;
+    Stimulus S = S_in;
+    S.win_side = S.kind == 1 ? heightfield_win_side(P, S) : 0;
+    int rec_cap = 2 * S.n_tris;
+    rec_cap = rec_cap > kBatch ? kBatch : (rec_cap < 2 ? 2 : rec_cap);
+    if (S.kind == 1 && rec_cap > 256) rec_cap = 256;   // a dozen heightfield triangles survive the depth cull; more just take another round
+    const size_t wcap = S.kind == 1 ? (((size_t)S.win_side * S.win_side + 3) & ~(size_t)3) : 0;
+    const size_t lds = (size_t)rec_cap * sizeof(TriRec) + (S.kind == 1 ? wcap * (2 * sizeof(float) + 2 * sizeof(unsigned short) + 1) + (size_t)rec_cap * sizeof(unsigned) + 16 : 0);
+    const unsigned layers = term_xform ? 2 : 1;
+    const dim3 g128x128((P.W / 128) * (P.H / 128), n_envs, layers), g128x64((P.W / 128) * (P.H / 64), n_envs, layers),
+               g64x64((P.W / 64) * (P.H / 64), n_envs, layers), blk(kThreads);
+    switch (k) {
+    case kRkBlocks:     // ONE workgroup per 128 x 128 region
+        hipLaunchKernelGGL((k_render_blocks<kBlockW>), g128x128, blk, lds, stream, P, S, xform, xform_soa, n_envs, mask,
+                           nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
+        break;
+    // (the terminal image as a second pass of the env's own workgroups instead of a grid layer of its own - 8 192 workgroups per launch
+    //  that start, look and leave - was measured in round 5: the pass loop costs the kernel more registers than the layer costs time,
+    //  render 108 -> 125 us at 256 x 256; not kept)
+    case kRkSmall:
+        hipLaunchKernelGGL((k_render_small<128, 64, 2, false>), g128x64, blk, lds, stream, P, S, xform, xform_soa, n_envs, mask,
+                           nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
+        break;
+    case kRkSmallQrej:
+        hipLaunchKernelGGL((k_render_small<128, 64, 2, true>), g128x64, blk, lds, stream, P, S, xform, xform_soa, n_envs, mask,
+                           nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
+        break;
+    case kRkHfCells:    // heightfield: 128 x 64 tiles (the per-workgroup staging is cheap since it is windowed: 0.108 -> 0.098 ms)
+    case kRkHfBands: {
+        static const bool dbg_win = getenv("TG_DEBUG_WIN") != nullptr;
+        if (dbg_win) fprintf(stderr, "heightfield window side %d cells\n", S.win_side);
+        if (k == kRkHfCells)
+            hipLaunchKernelGGL((k_render_tactile<128, 64, true, true>), g128x64, blk, lds, stream, P, S, xform, xform_soa, n_envs, mask,
+                               nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
+        else
+            hipLaunchKernelGGL((k_render_tactile<128, 64, true>), g128x64, blk, lds, stream, P, S, xform, xform_soa, n_envs, mask,
+                               nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
+        break;
+    }
+    case kRkScatter128:
+        hipLaunchKernelGGL((k_render_scatter<128, 128>), g128x128, blk, 0, stream, P, S, xform, xform_soa, n_envs, mask,
+                           nodef_dep, gray_u8, border, out, save_prev, term_xform, term_mask, term_out);
+        break;
+    case kRkTactile128:
+        hipLaunchKernelGGL((k_render_tactile<128, 128, false>), g128x128, blk, lds, stream, P, S, xform, xform_soa, n_envs, mask,
+                           nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
+        break;
+    case kRkScatter64:
+        hipLaunchKernelGGL((k_render_scatter<64, 64>), g64x64, blk, 0, stream, P, S, xform, xform_soa, n_envs, mask,
+                           nodef_dep, gray_u8, border, out, save_prev, term_xform, term_mask, term_out);
+        break;
+    case kRkTactile64:
+        hipLaunchKernelGGL((k_render_tactile<64, 64, false>), g64x64, blk, lds, stream, P, S, xform, xform_soa, n_envs, mask,
+                           nodef_dep, gray_u8, border, out, save_prev, rec_cap, term_xform, term_mask, term_out);
+        break;
+    }
+    return k;
 }
 
 }  // namespace tg
