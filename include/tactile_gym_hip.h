@@ -303,7 +303,7 @@ int tg_get_bank_stats(tg_ctx* ctx, int64_t* swapped, int64_t* late, int32_t* mod
  * per env, sb3_helpers/rl_utils.py:17-30): tg_set_obs_targets names up to two caller-owned device buffers uint8 [num_envs][H][W] - rank 0's
  * blocks of its two alternating gathered batches - and tg_select_obs_target picks where the NEXT steps / resets draw the tactile observations:
  * 0 = the context's own buffer (tg_get_packed_outputs), 1 / 2 = the caller's.  Each target has its own changed-block record (the block raster
- * rewrites only what changes, so a buffer must see every launch that is meant for it... or none) and its own captured step graphs.  Reward /
+ * rewrites only what changes, so a buffer must see every launch that is meant for it... or none).  Reward /
  * done / feature stay in the context's packed block; tg_get_obs_tactile returns the selected target.  count = 0 forgets the targets. */
 int tg_set_obs_targets(tg_ctx* ctx, int32_t count, void* const* dev_ptrs);
 int tg_select_obs_target(tg_ctx* ctx, int32_t index);
@@ -447,10 +447,10 @@ int tg_get_state(tg_ctx* ctx, const tg_state_view* view);
 /* Overwrite joint state (tests): q, qd [num_envs][ndof]; re-evaluates the cached TCP pose. */
 int tg_set_joint_state(tg_ctx* ctx, const double* q, const double* qd);
 
-/* Per-kernel timing (bench.py's roofline leg).  enable = 1: HIP event pairs around every launch class on the launch stream, the step's launches
- * issued one by one (no graph); every figure carries what an EMPTY event pair measures (3 - 5 us).  enable = 2: only the kernels' own clock
- * (csrc/tg_kt.hpp: every wavefront stamps its start and end, wall_clock64; first start -> last end per class), the step's launches stay as the
- * rollout issues them (since round 6: on the stream; one replayed hipGraph with TG_STEP_GRAPH=1) - the figures of the rollout itself.  enable = 0: off.
+/* Per-kernel timing (bench.py's roofline leg).  enable = 1: HIP event pairs around every launch class on the launch stream, between the step's
+ * launches; every figure carries what an EMPTY event pair measures (3 - 5 us).  enable = 2: only the kernels' own clock
+ * (csrc/tg_kt.hpp: every wavefront stamps its start and end, wall_clock64; first start -> last end per class), no host call between the step's
+ * launches - the figures of the rollout itself.  enable = 0: off.
  * tg_profile_get which: 0 step kernel, 1 render of all envs (the one launch of a fused step), 2 reset sequence, 3 masked render (reset /
  * auto-reset envs only), 4 scene camera, 5 an empty event pair - by HIP events; 8 + k (k = 0 .. 3): class k by the kernels' own clock. */
 int tg_profile_enable(tg_ctx* ctx, int32_t enable);
@@ -559,8 +559,8 @@ int tg_sample_actions(tg_ctx* ctx, uint64_t seed, uint64_t counter, float* dev_a
 /* A random-action rollout step (the north_star's synthetic rollout: `env.step(env.action_space.sample())`, examples/demo_rl_env_base.py:34, for the
  * whole batch): tg_sample_actions' draw followed by tg_step on it as one sequence of launches - the draw is made by the step kernel itself where the
  * lane-mapped k_step / k_step_body_wave runs, by the sequence's first launch elsewhere; the draw counter lives in device memory and moves on by one
- * per call.  (Until round 6 the sequence was replayed as one captured hipGraph; TG_STEP_GRAPH=1 still does: a graph launch costs ~6.6 us before its
- * first kernel starts on this stack, a launch on the stream ~2 us.)  restart != 0 (or a new seed): the next step uses draw first_draw + 1.  The
+ * per call.  The launches go on the stream one by one (until round 6 the sequence was one captured graph, but a graph launch costs ~6.6 us before
+ * its first kernel starts on this stack, a launch on the stream ~2 us).  restart != 0 (or a new seed): the next step uses draw first_draw + 1.  The
  * actions are the context's own buffer (tg_get_actions: device float32 [num_envs][act_dim]); draw k equals tg_sample_actions(seed, k). */
 int tg_step_random(tg_ctx* ctx, uint64_t seed, uint64_t first_draw, int32_t restart);
 int tg_get_actions(tg_ctx* ctx, void** dev_actions);

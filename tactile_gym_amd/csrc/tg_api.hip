@@ -443,8 +443,9 @@ __global__ void k_sample_actions(int total, uint64_t seed, uint64_t counter, flo
     out[i] = lo + (hi - lo) * u;
 }
 
-// tg_step_random's sampler: the draw counter and the seed live in device memory (a captured graph has no per-launch arguments); every thread
-// reads the counter, the workgroup that finishes last moves it on - nobody can still be reading it then.  Draw k is tg_sample_actions' draw k.
+// tg_step_random's sampler: the draw counter and the seed live in device memory (a caller may capture the step into a graph of its own, and a
+// graph has no per-launch arguments); every thread reads the counter, the workgroup that finishes last moves it on - nobody can still be
+// reading it then.  Draw k is tg_sample_actions' draw k.
 __global__ void k_sample_actions_ctr(int total, unsigned long long* __restrict__ ctr, float lo, float hi, float* __restrict__ out, unsigned long long* tl) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     TG_TL(tl, 0);
@@ -605,7 +606,7 @@ static void reset_sequence(tg_ctx* c, const uint8_t* d_mask, bool bank = false, 
     }
 }
 
-// The refill of the reset bank: outside the step graph, on the bank's low-priority stream, paced by a marker on the step stream (so the host
+// The refill of the reset bank: after the step's launches, on the bank's low-priority stream, paced by a marker on the step stream (so the host
 // running ahead of the device cannot spend all its refills before the episodes they are for have ended).  It never blocks the stream the
 // steps run on; the only data-path ordering between the two streams is the tag / RNG acquire-release pair (tg_kernels.hpp).
 static void bank_refill(tg_ctx* c) {
@@ -620,12 +621,11 @@ static void bank_refill(tg_ctx* c) {
         // host, i.e. the refills stay spread over the rollout however fast the host enqueues, and the host is never further ahead than that.
         // (Until round 5 the refill waited for its marker on the bank stream.  A host that runs ahead - any rollout that does not read a result
         // every step - then keeps a blocked barrier packet in a second hardware queue all the time, and every dispatch of the step stream was
-        // ~1 us slower for it: 45.9 instead of 42.1 us per step on the headline, whatever `bank_every` and whatever the queue's priority.
-        // TG_BANK_PACE=0 is that scheme.)
-        static const bool by_barrier = getenv("TG_BANK_PACE") != nullptr && atoi(getenv("TG_BANK_PACE")) == 0;
+        // ~1 us slower for it: 45.9 instead of 42.1 us per step on the headline, whatever `bank_every` and whatever the queue's priority.)
+        // A caller capturing the step into a graph of its own (torch.cuda.graph) cannot synchronise an event: the cross-stream wait then.
         hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(c->stream, &cap);
-        if (by_barrier || cap != hipStreamCaptureStatusNone) {
+        if (cap != hipStreamCaptureStatusNone) {
             (void)hipEventRecord(c->ev_bank, c->stream);
             (void)hipStreamWaitEvent(c->bank_stream, c->ev_bank, 0);
         } else {
@@ -729,7 +729,6 @@ static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sen
     *out = c;                            // owned by tg_create's guard from here on
     c->cfg = *cfg; c->robot = *robot; c->H = H; c->W = W;
     TG_HIP(hipStreamCreate(&c->own_stream));
-    TG_HIP(hipStreamCreateWithFlags(&c->capture_stream, hipStreamNonBlocking));   // non-blocking: a capture must not drag the legacy default stream (torch's) into its rules
     if (cfg->env_kind == TG_ENV_OBJECT_BALANCE) {
         TG_HIP(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
         TG_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)); TG_HIP(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
@@ -982,6 +981,7 @@ static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sen
     if (make_block_tables(c->rp, sensor->nodef_dep, sensor->nodef_gray, sensor->border_mask, n, &c->d_block_tables)) return fail(-2, "hipMalloc failed (raster block tables)");
     c->fused_pref = cfg->fused_step == TG_FUSED_OFF ? -1 : cfg->fused_step == TG_FUSED_ON ? 1 : 0;
     if (const char* e = getenv("TG_FUSED_STEP")) c->fused_pref = e[0] == '0' ? -1 : 1;   // A/B switch (tests, measurements)
+    c->no_inline_reset = getenv("TG_NO_INLINE_RESET") != nullptr;
 #ifdef TG_TL_STAMPS
     c->rp.tl = s.tl;
 #endif
@@ -1025,7 +1025,6 @@ static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sen
             if (bad) return fail(-2, "hipMalloc failed (reset bank)");
             int lo = 0, hi = 0;
             (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // lo = the least priority
-            if (getenv("TG_BANK_PRIO0")) lo = 0;
             TG_HIP(hipStreamCreateWithPriority(&c->bank_stream, hipStreamNonBlocking, lo));
             TG_HIP(hipEventCreateWithFlags(&c->ev_bank, hipEventDisableTiming)); TG_HIP(hipEventCreateWithFlags(&c->ev_bank_done, hipEventDisableTiming));
             for (int k = 0; k < tg_ctx::kBankRing; ++k) TG_HIP(hipEventCreateWithFlags(&c->ev_bank_ring[k], hipEventDisableTiming));   // the refill's pacing markers (bank_refill)
@@ -1040,15 +1039,6 @@ static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sen
     return 0;
 }
 
-
-}  // extern "C"
-void drop_step_graphs(tg_ctx* c) {   // every captured step graph of every render target (they are captured again on the next step)
-    for (int t = 0; t < 3; ++t) {
-        for (int k = 0; k < 2; ++k) if (c->step_graph_t[t][k]) { (void)hipGraphExecDestroy(c->step_graph_t[t][k]); c->step_graph_t[t][k] = nullptr; }
-        if (c->random_graph_t[t]) { (void)hipGraphExecDestroy(c->random_graph_t[t]); c->random_graph_t[t] = nullptr; }
-    }
-}
-extern "C" {
 int tg_destroy(tg_ctx* c) {
     if (!c) return 0;
     (void)hipSetDevice(c->cfg.device);
@@ -1084,7 +1074,6 @@ int tg_destroy(tg_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
     if (c->bank_stream) (void)hipStreamSynchronize(c->bank_stream);
-    drop_step_graphs(c);
     for (int k = 0; k < 2; ++k) if (c->drawn_ext[k]) (void)hipFree(c->drawn_ext[k]);
     if (c->d_draw) (void)hipFree(c->d_draw);
     if (c->d_bp) (void)hipFree(c->d_bp);
@@ -1107,7 +1096,6 @@ int tg_destroy(tg_ctx* c) {
     for (void* p_ : c->bank_allocs) (void)hipFree(p_);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->capture_stream) (void)hipStreamDestroy(c->capture_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
     delete c;
     return 0;
@@ -1150,20 +1138,12 @@ int tg_reset(tg_ctx* c, const uint8_t* host_mask) {
     return 0;
 }
 
-// Whether a step is replayed as a captured graph or enqueued launch by launch.  Until round 6 every step was ONE graph launch; measured on an
+// Every step is enqueued launch by launch on the bound stream.  Until round 6 every step was ONE captured-graph launch; measured on an
 // MI355X with ROCm 7.2 (tools/dev/graph_floor.hip: 15-us kernels back to back, the device never idle) a graph launch costs ~6.6 us before its
 // first kernel starts and ~1.7 us per further dependent node, launches on the stream ~2.0 us each - and on the host a graph launch is ~9 us
 // against ~2.8 us per kernel launch.  The steps here are 2 - 4 launches (the policy draw and the auto-reset live inside k_step), so the stream
 // wins up to ~16 launches per step: headline 42.2 -> 37.2 us per step (24.3 -> 27.5 M env-steps/s), episodes out of phase 47.8 -> 42.8 us,
-// surface_follow-v0 100.4 -> 95.8 us, object_balance 117 -> 112.5 us (tools/desync_rate.py, same box, alternating).  Default: the stream.
-// TG_STEP_GRAPH=1 keeps the graphs (A/B measurements; a host that cannot keep two launches per step ahead of the device).
-static bool step_as_graph(const tg_ctx* c) {
-    static const int forced = getenv("TG_STEP_GRAPH") != nullptr ? atoi(getenv("TG_STEP_GRAPH")) : -1;
-    if (forced >= 0) return forced != 0;
-    (void)c;
-    return false;
-}
-
+// surface_follow-v0 100.4 -> 95.8 us, object_balance 117 -> 112.5 us (tools/desync_rate.py, same box, alternating).
 static void enqueue_step(tg_ctx* c, const float* d_act) {
     if (c->profile) { Timer t(c, 5); }   // an empty event pair: what every per-kernel figure of this mode carries on top of its kernel
     bool reset_inlined = false;          // object_balance: k_step_body_wave has reset its finished envs itself
@@ -1180,7 +1160,7 @@ static void enqueue_step(tg_ctx* c, const float* d_act) {
             // the reset of finished envs inside the step's launch: auto-reset with a valid template, the pole, no scene / oracle draw between
             // the step and the reset (they show the pre-reset state)
             const int inline_reset = (c->cfg.auto_reset && c->st.reset_tmpl != nullptr && c->tmpl_ready && c->cfg.balance_object == TG_BALANCE_POLE &&
-                                      !c->scene_every_step && !c->oracle_every_step && getenv("TG_NO_INLINE_RESET") == nullptr) ? 1 : 0;
+                                      !c->scene_every_step && !c->oracle_every_step && !c->no_inline_reset) ? 1 : 0;
             if (c->cfg.balance_object == TG_BALANCE_SPINNING_PLATE) {
                 (void)launch_step_spin(c->cfg.physics_dtype, c->robot.topology, c->cfg.control_mode, c->cfg.num_envs, c->cfg.spin_n_dish, c->stream, c->d_robot,
                                        c->d_const, c->st, d_act);   // one wavefront per env (tg_spin.hip); tg_create has checked the combination
@@ -1207,14 +1187,13 @@ static void enqueue_step(tg_ctx* c, const float* d_act) {
         } else {
             // edge_follow / surface_follow: the auto-reset's first launch (edge_follow: its only one) inside the step kernel, unless something
             // is drawn or checked between the step and the reset (scene / oracle observations, the broadphase guard: the pre-reset state)
-            static const bool no_inline = getenv("TG_NO_INLINE_RESET") != nullptr;
             const bool fused_render_path = c->cfg.env_kind == TG_ENV_EDGE_FOLLOW || c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO;
             // Only with the reset bank on: the swap-in is a copy, identical wherever it runs; a reset computed on the spot (IK, blocking move) inside
             // k_step<.., true> is another instantiation of reset_env than k_reset's, and the compiler contracts each one's f64 expressions into FMAs
             // on its own - measured: one build in which a bank-off rollout differed from the k_reset launch's in the last bits of q (12 grey levels
             // of one image sum).  With the bank off the reset is 90 us on the spot anyway, and it stays the k_reset launch.  (With the bank on, an env
             // that finds no entry - none in any measured rollout - is reset on the spot in here, as k_step_render does.)
-            const int reset_phase = (c->cfg.auto_reset && fused_render_path && c->bank_mode != 0 && !no_inline && !c->scene_every_step && !c->oracle_every_step && !(c->d_bp && c->bp_every_step))
+            const int reset_phase = (c->cfg.auto_reset && fused_render_path && c->bank_mode != 0 && !c->no_inline_reset && !c->scene_every_step && !c->oracle_every_step && !(c->d_bp && c->bp_every_step))
                                         ? (c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO ? 1 : 0) : -1;
 #define CALL(T, TOPO) reset_inlined = launch_step_t<T, TOPO>(c, d_act, reset_phase)
             TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
@@ -1237,7 +1216,7 @@ static void enqueue_step(tg_ctx* c, const float* d_act) {
         // object_balance: a pole falls somewhere in the batch on nearly every step, and its reset (rest pose, blocking move, settling: a
         // serial chain of 0.14 ms on a few wavefronts) depends on k_step only.  Fork: it runs on the second stream while this one draws the
         // step's observations from term_xform (k_step's second copy of the transforms, which the reset does not touch); join; then the
-        // masked launch saves the terminal observations and draws the post-reset ones.  Inside the captured graph this is a fork/join.
+        // masked launch saves the terminal observations and draws the post-reset ones.
         (void)hipEventRecord(c->ev_fork, c->stream);
         (void)hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0);
         {
@@ -1268,59 +1247,10 @@ static void enqueue_step(tg_ctx* c, const float* d_act) {
 int tg_step(tg_ctx* c, const float* actions, int32_t on_device) {
     if (!c || !actions) return fail(-1, "tg_step: NULL argument");
     TG_ENTER(c);
-    const float* d_act = actions;
+    const float* d_act = actions;        // device actions are read in place
     if (!on_device) {
         TG_HIP(hipMemcpyAsync(c->d_actions, actions, (size_t)c->cfg.num_envs * c->act_dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
         d_act = c->d_actions;
-    }
-    // The launch sequence of a step is the same every step (all arguments are device pointers owned by the context, the action
-    // buffer aside), so it is captured once and replayed as one graph launch.  Two graphs, neither ever re-captured:
-    //   slot 0  reads the context's own action buffer: host actions are uploaded into it, and so are device actions that arrive in a
-    //           buffer other than the pinned one below - a policy that hands over a fresh tensor every step costs one 8 KB device
-    //           copy per step, not a graph instantiation;
-    //   slot 1  reads the FIRST caller-owned device buffer seen, in place (a rollout that reuses one action tensor, e.g. bench.py).
-    // Not while profiling (the per-kernel events are host calls between the launches) and not for the lane-per-env push kernels
-    // (hipFuncSetAttribute on first launch).
-    const bool want_graph = !c->profile && !c->graph_broken && c->cfg.env_kind != TG_ENV_OBJECT_PUSH && c->cfg.env_kind != TG_ENV_OBJECT_ROLL && step_as_graph(c);
-    if (want_graph) {
-        int slot = 0;
-        if (on_device) {
-            if (c->step_graph_actions[1] == nullptr && c->step_graph[1] == nullptr) c->step_graph_actions[1] = d_act;   // pin the first one
-            if (c->step_graph_actions[1] == d_act) slot = 1;
-            else {
-                TG_HIP(hipMemcpyAsync(c->d_actions, actions, (size_t)c->cfg.num_envs * c->act_dim * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-                d_act = c->d_actions;
-            }
-        }
-        if (!c->step_graph[slot]) {
-            // Captured on a stream of its own, never on the stream the work runs on: while a stream is capturing, hipEventQuery on an event
-            // that was recorded on it BEFORE the capture began fails with hipErrorCapturedEvent, and other threads do query such events - the
-            // watchdog thread of torch's RCCL process group polls the end events of collectives that ran on the caller's stream, and a poll
-            // that fell into the few hundred microseconds of a capture aborted the process (seen in 2 of ~100 one-rank bench runs).  A graph
-            // is not tied to the stream it was captured on, so tg_set_stream needs no re-capture either.
-            hipGraph_t g = nullptr;
-            const hipStream_t run_stream = c->stream;
-            c->stream = c->capture_stream;
-            if (hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                enqueue_step(c, d_act);
-                const hipError_t e1 = hipStreamEndCapture(c->capture_stream, &g);
-                if (e1 == hipSuccess && g && hipGraphInstantiate(&c->step_graph[slot], g, nullptr, nullptr, 0) == hipSuccess) {
-                    c->step_graph_stream[slot] = run_stream;
-                } else {
-                    c->step_graph[slot] = nullptr; c->graph_broken = true;
-                }
-                if (g) (void)hipGraphDestroy(g);
-            } else {
-                c->graph_broken = true;
-            }
-            c->stream = run_stream;
-            (void)hipGetLastError();
-        }
-        if (c->step_graph[slot]) {
-            TG_HIP(hipGraphLaunch(c->step_graph[slot], c->stream));
-            bank_refill(c);
-            return 0;
-        }
     }
     enqueue_step(c, d_act);
     bank_refill(c);
@@ -1349,38 +1279,18 @@ int tg_step_random(tg_ctx* c, uint64_t seed, uint64_t first_draw, int32_t restar
 #endif
                            );
     };
-    const bool want_graph = !c->profile && !c->graph_broken && c->cfg.env_kind != TG_ENV_OBJECT_PUSH && c->cfg.env_kind != TG_ENV_OBJECT_ROLL && step_as_graph(c);
-    // the lane-mapped k_step (edge_follow / surface_follow, TCP_velocity_control) draws its own actions: no sampler node at all - a dependent
-    // kernel in this graph costs its ~6 us dispatch floor whatever it computes (profiles/r4_exp_reset_launch.txt)
+    // the lane-mapped k_step (edge_follow / surface_follow, TCP_velocity_control) draws its own actions: no sampler launch at all - a dependent
+    // kernel costs its dispatch floor whatever it computes (profiles/r4_exp_reset_launch.txt)
     // (round 5: so does object_balance's k_step_body_wave - the conditions of launch_step_body_wave)
     const bool in_kernel = ((c->cfg.env_kind == TG_ENV_EDGE_FOLLOW || c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) &&
                             c->cfg.control_mode == TG_CONTROL_TCP_VELOCITY && !use_arm_wave(c)) ||
                            (c->cfg.env_kind == TG_ENV_OBJECT_BALANCE && use_contact_wave(c) && c->cfg.physics_dtype == TG_PHYSICS_F64 &&
                             c->robot.topology == 0 && c->cfg.control_mode == TG_CONTROL_TCP_VELOCITY && !use_fused_step(c));
-    struct DrawScope {                   // c->st carries the counter only while this call enqueues / captures
+    struct DrawScope {                   // c->st carries the counter only while this call enqueues
         tg_ctx* c; bool on;
         DrawScope(tg_ctx* c_, bool on_) : c(c_), on(on_) { if (on) { c->st.draw = c->d_draw; c->st.act_out = c->d_actions; } }
         ~DrawScope() { if (on) { c->st.draw = nullptr; c->st.act_out = nullptr; } }
     } scope(c, in_kernel);
-    if (want_graph && !c->random_graph_t[c->obs_sel]) {
-        hipGraph_t g = nullptr;
-        const hipStream_t run_stream = c->stream;
-        c->stream = c->capture_stream;
-        if (hipStreamBeginCapture(c->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            if (!in_kernel) sample();
-            enqueue_step(c, c->d_actions);
-            const hipError_t e1 = hipStreamEndCapture(c->capture_stream, &g);
-            if (!(e1 == hipSuccess && g && hipGraphInstantiate(&c->random_graph_t[c->obs_sel], g, nullptr, nullptr, 0) == hipSuccess)) { c->random_graph_t[c->obs_sel] = nullptr; c->graph_broken = true; }
-            if (g) (void)hipGraphDestroy(g);
-        } else c->graph_broken = true;
-        c->stream = run_stream;
-        (void)hipGetLastError();
-    }
-    if (want_graph && c->random_graph_t[c->obs_sel]) {
-        TG_HIP(hipGraphLaunch(c->random_graph_t[c->obs_sel], c->stream));
-        bank_refill(c);
-        return 0;
-    }
     if (!in_kernel) sample();
     enqueue_step(c, c->d_actions);
     bank_refill(c);
@@ -1393,11 +1303,7 @@ int tg_set_obs_targets(tg_ctx* c, int32_t count, void* const* dev_ptrs) {
     for (int k = 0; k < count; ++k) if (!dev_ptrs[k]) return fail(-1, "tg_set_obs_targets: NULL target");   // (every argument is checked before anything is changed)
     TG_ENTER(c);
     TG_HIP(hipStreamSynchronize(c->stream));
-    for (int t = 1; t < 3; ++t) {        // the old targets' graphs name their buffers: gone with them
-        for (int k = 0; k < 2; ++k) if (c->step_graph_t[t][k]) { (void)hipGraphExecDestroy(c->step_graph_t[t][k]); c->step_graph_t[t][k] = nullptr; }
-        if (c->random_graph_t[t]) { (void)hipGraphExecDestroy(c->random_graph_t[t]); c->random_graph_t[t] = nullptr; }
-    }
-    c->obs_sel = 0; c->step_graph = c->step_graph_t[0];
+    c->obs_sel = 0;
     const size_t regions = (c->rp.W % 128 == 0 && c->rp.H % 128 == 0) ? (size_t)(c->rp.W / 128) * (c->rp.H / 128) : 0;
     for (int k = 0; k < 2; ++k) {
         c->obs_ext[k] = k < count ? (uint8_t*)dev_ptrs[k] : nullptr;
@@ -1412,7 +1318,6 @@ int tg_set_obs_targets(tg_ctx* c, int32_t count, void* const* dev_ptrs) {
 int tg_select_obs_target(tg_ctx* c, int32_t index) {
     if (!c || index < 0 || index > 2 || (index > 0 && c->obs_ext[index - 1] == nullptr)) return fail(-1, "tg_select_obs_target: no such target");
     c->obs_sel = index;
-    c->step_graph = c->step_graph_t[index];
     return 0;
 }
 
@@ -1445,7 +1350,6 @@ int tg_unpack_interior(tg_ctx* c, const void* src_dev, int32_t n_images, void* d
 int tg_enable_oracle_obs(tg_ctx* c) {
     if (!c) return fail(-1, "NULL ctx");
     TG_ENTER(c);
-    if (c->step_graph[0] || c->step_graph[1]) return fail(-1, "tg_enable_oracle_obs: call before the first tg_step");
     if (!c->d_oracle) TG_HIP(hipMalloc(&c->d_oracle, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
     if (!c->d_oracle_term) TG_HIP(hipMalloc(&c->d_oracle_term, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
     TG_HIP(hipMemset(c->d_oracle, 0, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
@@ -1495,7 +1399,6 @@ static int set_scene_impl(tg_ctx* c, const tg_scene* sc) {
     if (!c || !sc) return fail(-1, "tg_set_scene: NULL argument");
     TG_ENTER(c);
     if (c->scene_on) return fail(-1, "tg_set_scene: the scene is already set");
-    if (sc->every_step && (c->step_graph[0] || c->step_graph[1])) return fail(-1, "tg_set_scene: every_step needs the call before the first tg_step");
     if (!sc->verts || !sc->tris || !sc->tri_frame || !sc->tri_rgb || sc->n_tris <= 0 || sc->n_verts <= 0) return fail(-1, "tg_set_scene: empty scene");
     const int W = sc->image_w, H = sc->image_h;
     if (W <= 0 || H <= 0 || (W > 128 && W % 128) || (H > 128 && H % 128)) return fail(-1, "tg_set_scene: image sides must be <= 128 or multiples of 128");

@@ -77,7 +77,6 @@ int tg_set_broadphase(tg_ctx* c, const tg_broadphase* g) {
     if (!c) return fail(-1, "NULL argument");
     TG_ENTER(c);
     TG_HIP(hipStreamSynchronize(c->stream));
-    drop_step_graphs(c);                         // the guard is (or stops being) a node of the step graphs
     if (c->d_bp) { (void)hipFree(c->d_bp); c->d_bp = nullptr; }
     if (c->d_bp_hull) { (void)hipFree(c->d_bp_hull); c->d_bp_hull = nullptr; }
     c->bp_every_step = false;
@@ -305,11 +304,7 @@ int tg_profile_enable(tg_ctx* c, int32_t enable) {
     (void)hipStreamSynchronize(c->stream);
     drain_events(c);
     c->profile = enable == 1;
-    if (c->profile_clock != (enable == 2)) {
-        // the step graphs carry the slot pointer (or its absence) in their kernel arguments: captured again on the next step
-        drop_step_graphs(c);
-        c->profile_clock = enable == 2;
-    }
+    c->profile_clock = enable == 2;
     for (int k = 0; k < 6; ++k) { c->prof_ms[k] = 0; c->prof_n[k] = 0; }
     if (enable && !c->d_kt) {
         // slots for the largest launch of this context: a render of every env's image in 64-row tiles, two passes, four wavefronts each

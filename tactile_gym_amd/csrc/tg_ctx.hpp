@@ -1,6 +1,6 @@
 // tg_ctx.hpp - what the translation units of the C ABI share: the context behind a tg_ctx*, error reporting, the device-selection / dispatch macros,
-// the host -> device translation of a robot description.  tg_api.hip (configuration, creation, the step / reset launch sequences and their graphs,
-// the reset bank), tg_api_state.hip (state read-back, inspection, profiling, the broadphase guard's entry points) and tg_api_ops.hip (the
+// the host -> device translation of a robot description.  tg_api.hip (configuration, creation, the step / reset launch sequences, the reset
+// bank), tg_api_state.hip (state read-back, inspection, profiling, the broadphase guard's entry points) and tg_api_ops.hip (the
 // context-free function-level entry points) include it; round 6 split them out of one 2 400-line file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -193,7 +193,6 @@ struct tg_ctx {
     int H, W, act_dim;
     hipStream_t own_stream = nullptr, stream = nullptr;
     bool tmpl_ready = false;               // object_balance: State.reset_tmpl has been (or will have been, in stream order) filled by a full reset
-    hipStream_t capture_stream = nullptr;   // the step graph is captured here, never on the stream work runs on (see tg_step)
     void *d_robot = nullptr, *d_const = nullptr;   // DevRobot<T>, EnvConst<T>
     // broadphase guard (tg_set_broadphase; tg_broadphase.hip): device scene + hull vertices, per-env results [3][n], totals {env-checks, pairs, hits}
     tg::BpScene* d_bp = nullptr;
@@ -229,24 +228,16 @@ struct tg_ctx {
     float* d_oracle_term = nullptr;   // tg_enable_oracle_obs: the step's own vectors (before any reset): rows of finished envs = terminal observation
     bool oracle_every_step = false;
     bool cfg_turn_off_border = false;
-    // hipGraph of one tg_step launch sequence, keyed by the device action pointer it was captured with (launch-bound inner loop:
-    // 3-4 kernels per step, one graph launch instead)
     hipStream_t aux_stream = nullptr;                // object_balance: the reset of finished envs runs here, beside the render
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // Render targets (tg_set_obs_targets, round 5): the tactile images of a step land in the context's own buffer (target 0) or in one of up to two
     // caller-owned buffers (targets 1, 2: rank 0's blocks of the two alternating gathered batches, parallel.py) - each with its own changed-block
-    // record and its own captured graphs, since the destination is a kernel argument.
+    // record.
     uint8_t* obs_ext[2] = {nullptr, nullptr};
     unsigned long long* drawn_ext[2] = {nullptr, nullptr};
     int obs_sel = 0;                                             // 0 own buffer, 1 / 2 = obs_ext[0 / 1]
-    hipGraphExec_t step_graph_t[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};   // [target][0 reads d_actions, 1 the pinned caller-owned device buffer]
-    hipGraphExec_t* step_graph = step_graph_t[0];                // the selected target's pair
-    const float* step_graph_actions[2] = {nullptr, nullptr};
-    hipStream_t step_graph_stream[2] = {nullptr, nullptr};
-    bool graph_broken = false;
-    // tg_step_random: the policy of a random-action rollout (action_space.sample() for the whole batch) inside the step's graph
+    // tg_step_random: the policy of a random-action rollout (action_space.sample() for the whole batch) on the device
     unsigned long long* d_draw = nullptr;      // [0] draw counter, [1] seed, [2] ticket of the sampler's last-block election
-    hipGraphExec_t random_graph_t[3] = {nullptr, nullptr, nullptr};
     uint64_t random_seed = 0;
     // reset bank (edge_follow / surface_follow, auto_reset; tg_kernels.hpp: BankAux)
     tg::State bk{};                    // the bank view: st's layout, the reset-written arrays in allocations of the bank's own
@@ -264,14 +255,15 @@ struct tg_ctx {
     std::vector<void*> bank_allocs;
     void* d_bank = nullptr;            // BankDev {bk, aux} in device memory (k_reset's argument)
     // profiling
-    bool profile = false;          // tg_profile_enable(1): HIP event pairs around every launch class, no graph
-    bool profile_clock = false;    // tg_profile_enable(2): the kernels' own clock only (tg_kt.hpp): the step stays ONE graph, reduce nodes behind its scopes
+    bool profile = false;          // tg_profile_enable(1): HIP event pairs around every launch class
+    bool profile_clock = false;    // tg_profile_enable(2): the kernels' own clock only (tg_kt.hpp): no host call between the launches, a reduce launch behind each timed scope
     struct Ev { hipEvent_t a, b; int which; };
     std::vector<Ev> events;
     double prof_ms[6] = {0, 0, 0, 0, 0, 0};      // HIP events: step, render (k_step_render when fused), reset sequence, masked render, scene camera, an EMPTY
     int64_t prof_n[6] = {0, 0, 0, 0, 0, 0};      // event pair (what every figure before it carries on top of its kernels)
     // one launch per step (tg_fused.hip): -1 = TG_FUSED_STEP=0, 1 = TG_FUSED_STEP=1, 0 = where it measures faster (use_fused_step)
     int fused_pref = 0;
+    bool no_inline_reset = false;  // TG_NO_INLINE_RESET (tests, measurements): finished envs are reset by the k_reset launch, never inside the step's launch
     // profiling by the kernels' own clock (tg_kt.hpp): per-wavefront {start, end} slots, reduced after every timed scope into {ticks, scopes}
     unsigned long long* d_kt = nullptr;          // [kt_slots][2]
     unsigned long long* d_kt_acc = nullptr;      // [8][2]
@@ -344,8 +336,6 @@ static int need_device() {
 }
 bool use_fused_step(const tg_ctx* c);                        // tg_api.hip
 }  // namespace tg
-
-void drop_step_graphs(tg_ctx* c);                            // tg_api.hip: every captured step graph of every render target (captured again on the next step)
 
 // Every entry point that touches the device first makes the context's device current: the caller may have switched devices
 // (torch.cuda.set_device, another thread) since tg_create.

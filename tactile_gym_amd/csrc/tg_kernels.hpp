@@ -1205,7 +1205,7 @@ __global__ __launch_bounds__(64) void k_reset(const DevRobot<T>* __restrict__ mp
     reset_or_swap<T, TOPO>(mp, cp, st, env, mask != nullptr, phase, bd);
 }
 
-// The refill (second stream, outside the step graph): for every env whose bank entry does not belong to its current RNG state, the same
+// The refill (second stream, after the step's launches): for every env whose bank entry does not belong to its current RNG state, the same
 // reset_env on the bank view, started from the main RNG state.  Phases as k_reset's: 0 all in one (edge_follow); 1 the task draws, then
 // k_gen_surface on the bank's heights with mask = need, then 2 the robot half (surface_follow).  The last phase publishes the tag.
 template <typename T, int TOPO>

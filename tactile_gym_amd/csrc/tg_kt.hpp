@@ -11,7 +11,7 @@
 // all: workgroups are dispatched in index order, so the first start is among the first kEdge of them and the last end (but for a straggler that
 // outlives 8192 later wavefronts) among the last kEdge of a z-layer (see ~KtScope).  A scope of several instrumented launches moves the base
 // on between them (reset_sequence), so that a later launch does not overwrite the first one's start stamps.  base == nullptr (every launch outside
-// profiling mode, every graph): one uniform branch.
+// profiling mode): one uniform branch.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -262,7 +262,6 @@ class ShardedVecEnv:
         self._last_counts = None
         self._prev_ids = [None, None]
         self._root_cache, self._out_cache, self._tac_view = [None, None], [None, None], [None, None]
-        self._captured = set()                       # step kinds whose graph capture has been made safe (_quiesce_before_capture)
 
     def env_slice(self):
         return slice(self.rank * self.n_local, (self.rank + 1) * self.n_local)
@@ -383,7 +382,7 @@ class ShardedVecEnv:
         if self.transport == "ipc" and self.rank != self.root:
             self._scratch = torch.zeros(max(rest_bytes, 16), dtype=torch.uint8, device=dev) if packed is None else None
         # Rank 0 draws its own shard STRAIGHT into its block of the gathered batch (round 5): the two alternating batches are the env library's
-        # render targets 1 and 2 (tg_set_obs_targets: each with its own changed-block record and step graphs), selected before every step by
+        # render targets 1 and 2 (tg_set_obs_targets: each with its own changed-block record), selected before every step by
         # the slot its message will use.  Until round 4 the shard was drawn into the library's buffer and copied over (16.8 MB per step at
         # 1024 envs: the one-rank ipc + tiles step 57.5 us against 43 without an exchange).
         self._direct = False
@@ -393,11 +392,6 @@ class ShardedVecEnv:
             venv.sync()
             venv.set_obs_targets([self._batch_buffer(s)[self.root * n:(self.root + 1) * n].data_ptr() for s in (0, 1)])
             self._direct = True
-            # these two targets' step graphs can only be captured now that the batches exist, i.e. under the process group: the first steps
-            # on them go through the quiesce below even on a primed shard (once, in reset(), outside any timed region; no collective runs
-            # between the steps of the ipc transport, so the watchdog has nothing to poll while the two captures happen)
-            self._captured.clear()
-            self._quiesce_always = True
 
     # ------------------------------------------------------------------ sender side
     def _rest_tensor(self, obs, rew, done):
@@ -640,9 +634,7 @@ class ShardedVecEnv:
         if self._lay is None:
             self._setup(obs)
         if self.transport != "ipc":
-            out = {k: self._gather("obs_" + k, v) for k, v in obs.items()}
-            self._quiesce_before_capture("step", "random")   # here rather than in the first step: outside any timed region
-            return out
+            return {k: self._gather("obs_" + k, v) for k, v in obs.items()}
         # ipc: the reset observations travel like a step's message (zero reward / done), synchronously
         n = self._lay["n"]
         zr = self.torch.zeros(n, dtype=self.torch.float32, device=self._lay["dev"])
@@ -650,36 +642,12 @@ class ShardedVecEnv:
         self._drain()
         self._tick += 1
         self._send(self._tick, obs, zr, zd, False)
-        out = self._receive(self._tick)[0] if self.rank == self.root else obs
-        self._quiesce_before_capture("step", "random")
-        return out
+        return self._receive(self._tick)[0] if self.rank == self.root else obs
 
     def _drain(self):
         for k in (0, 1):
             self._wait(self._pending[k])
             self._pending[k] = None
-
-    def _quiesce_before_capture(self, *kinds):
-        """The first step of each kind makes the library capture its step graph (tg_step / tg_step_random).  While a HIP stream is capturing,
-        hipEventQuery from ANOTHER thread can fail with hipErrorCapturedEvent, and torch's RCCL process group has such a thread: its watchdog
-        polls the end events of the collectives still in its list every 100 ms, and a poll that fell into the few hundred microseconds of a
-        capture aborted the process (2 of ~100 one-rank bench runs, all ranks would go down with it).  The ordering that cannot race is
-        TorchShard.prime() before the process group is created (bench.py does that): then this is a no-op.  The fallback for a shard that was
-        not primed: finish all device work, then give the watchdog three periods to retire the completed collectives - it polls nothing while
-        its list is empty.  reset() does it for both kinds (outside any timed region); a step without a reset before it for its own kind."""
-        todo = [k for k in kinds if k not in self._captured]
-        if not todo or self._solo:
-            return
-        self._captured.update(todo)
-        if not capi.step_graphs_enabled():
-            return                                   # round 6: steps are enqueued launch by launch - the library captures nothing, there is nothing to race with
-        if getattr(self.local, "primed", False) and not getattr(self, "_quiesce_always", False):
-            return                                   # TorchShard.prime(): the graphs were captured before the process group existed - nothing to wait for
-        if not (getattr(self.local, "raw", False) and self.torch.cuda.is_available()):
-            return                                   # a host-side shard (the gloo tests): nothing is captured
-        import time
-        self.torch.cuda.synchronize()
-        time.sleep(0.3)
 
     def _aim(self):
         """Rank 0, direct mode: the next message is t = tick + 1 and lands in slot t & 1 - the library draws this step's images there."""
@@ -687,14 +655,12 @@ class ShardedVecEnv:
             self.local.venv.select_obs_target(1 + ((self._tick + 1) & 1))
 
     def step_random(self, seed, first_draw=0, restart=False):
-        """step(action_space.sample()) on every rank's shard (TorchShard.step_random: the draw inside the step's graph), then the exchange of step().
+        """step(action_space.sample()) on every rank's shard (TorchShard.step_random: the draw on the device), then the exchange of step().
         Every rank passes its own seed."""
-        self._quiesce_before_capture("random")
         self._aim()
         return self._exchange(*self.local.step_random(seed, first_draw, restart))
 
     def step(self, local_actions):
-        self._quiesce_before_capture("step")
         self._aim()
         return self._exchange(*self.local.step(local_actions))
 
@@ -895,12 +861,8 @@ class TorchShard:
         return self._obs()
 
     def prime(self, device_actions=None):
-        """Make the library capture its step graphs NOW (tg_step's two slots - host actions / the caller's device tensor - and tg_step_random's),
-        by one reset and one step of each kind.  Meant to be called BEFORE the process group exists: a capture that happens while torch's RCCL
-        watchdog thread may poll an event is what aborted one-rank runs in rounds 3-4 (ShardedVecEnv._quiesce_before_capture waited three
-        watchdog periods instead: a timing workaround).  With the graphs captured up front no step of the rollout captures anything, whatever the
-        watchdog does - an ordering, not a delay.  `device_actions`: the float32 [n, act_dim] CUDA tensor the rollout will pass to step()
-        (tg_step pins the first device pointer it sees to its in-place graph)."""
+        """Warm-up: one reset and one step of each kind the rollout will run (host actions, the caller's device tensor, tg_step_random),
+        before the timed region.  `device_actions`: the float32 [n, act_dim] CUDA tensor the rollout will pass to step() (zeroed here)."""
         import contextlib
         import numpy as np
         import torch
@@ -908,13 +870,12 @@ class TorchShard:
         ctx = torch.cuda.stream(self.stream) if self.pipelined else contextlib.nullcontext()
         with ctx:
             self.reset()
-            self.step(np.zeros((v.num_envs, v.act_dim), dtype=np.float32))          # slot 0: the context's own action buffer
+            self.step(np.zeros((v.num_envs, v.act_dim), dtype=np.float32))          # host actions: the context's own action buffer
             if device_actions is not None:
                 device_actions.zero_()
-                self.step(device_actions)                                            # slot 1: this tensor, in place
-            self.step_random(0, 0, restart=True)                                    # the random-action graph
+                self.step(device_actions)                                            # this tensor, in place
+            self.step_random(0, 0, restart=True)                                    # the random-action step
         v.sync()
-        self.primed = True
         return self
 
     def step(self, actions):
@@ -925,7 +886,7 @@ class TorchShard:
         return self._obs(), rew, done, {}
 
     def step_random(self, seed, first_draw=0, restart=False):
-        """step(action_space.sample()) with the draw inside the step's graph (TactileVecEnv.step_random_async)."""
+        """step(action_space.sample()) with the draw on the device (TactileVecEnv.step_random_async)."""
         self.venv.step_random_async(seed, first_draw, restart)
         if not self.pipelined:
             self.venv.sync()

@@ -183,9 +183,9 @@ class TactileVecEnv(_VecEnvBase):
 
     def _bind_torch_stream(self):
         """obs_mode="torch": the zero-copy observation / reward / done tensors and CUDA action tensors are produced and consumed on
-        torch's CURRENT stream, so the library is put on that stream before work is enqueued (tg_set_stream is a pointer swap; with
-        TG_STEP_GRAPH=1 the step graph is captured on a stream of the library's own and replays on whichever stream is bound).  Ordering between the policy's kernels and the env's is then the
-        stream's own: no event, no host wait, and correct under non-default or per-thread torch streams as well."""
+        torch's CURRENT stream, so the library is put on that stream before work is enqueued (tg_set_stream is a pointer swap: every
+        step's launches go on whichever stream is bound).  Ordering between the policy's kernels and the env's is then the stream's own: no event,
+        no host wait, and correct under non-default or per-thread torch streams as well."""
         if self.obs_mode != "torch" or self._pinned_stream:
             return
         import torch
@@ -658,7 +658,7 @@ class TactileVecEnv(_VecEnvBase):
     def set_broadphase_guard(self, every_step=False):
         """(Re)install the broadphase guard: the check that no pair of collision objects other than the ones the solver has rows for can touch
         (what PyBullet's broadphase would find, robots/arms/robot.py:141; include/tactile_gym_hip.h: tg_set_broadphase).  every_step: the check is a
-        node of every step's graph; otherwise check_broadphase() runs it on demand.  Results: get_state()["broadphase_pairs" / "_hits" / "_mask"]."""
+        launch of every step; otherwise check_broadphase() runs it on demand.  Results: get_state()["broadphase_pairs" / "_hits" / "_mask"]."""
         from .broadphase import Guard
         sp = self._guard_spec
         if sp is None:
@@ -723,8 +723,8 @@ class TactileVecEnv(_VecEnvBase):
         capi.check(self._L.tg_set_joint_state(self._ctx, q.ctypes.data_as(dp), qd.ctypes.data_as(dp)))
 
     def profile(self, enable=True):
-        """True / 1: HIP events around every launch class (no graph) + the kernels' own clock; 2 / "clock": the own clock only, the step's launches stay
-        as the rollout itself runs them; False: off."""
+        """True / 1: HIP events around every launch class + the kernels' own clock; 2 / "clock": the own clock only, no host call between the
+        step's launches; False: off."""
         capi.check(self._L.tg_profile_enable(self._ctx, 2 if enable == "clock" else int(enable)))
 
     def profile_get(self):

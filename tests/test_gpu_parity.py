@@ -395,7 +395,7 @@ def test_object_balance_env_matches_oracle(size, mapping):
 
 def test_object_balance_autoreset_forked_reset_matches_oracle():
     """object_balance with auto_reset: the reset of the finished envs runs on a second stream beside the render of the step's
-    observations (fork/join inside the step graph).  Two auto-resets in a row: terminal observations, post-reset
+    observations (a fork/join across the two streams).  Two auto-resets in a row: terminal observations, post-reset
     observations and states against oracle envs that are stepped and reset by hand."""
     import tactile_gym_amd as tg
     from oracle.ref_env import OracleObjectBalanceEnv
@@ -1281,7 +1281,7 @@ def test_raster_edge_exclusion_never_hides_a_coverable_pixel():
 def _run_bench(cmd, root, env, tag):
     """One bench.py child; on failure its whole stderr is kept under gpurun_out/ (a gpurun call brings it back).  That is how the cause of
     a rare SIGABRT of one-rank RCCL runs was found: the process group's watchdog thread polled an event of the caller's stream while
-    tg_step was capturing its step graph on that stream (hipErrorCapturedEvent); the graph is now captured on a stream of its own."""
+    tg_step was capturing its step graph on that stream (hipErrorCapturedEvent); tg_step now captures nothing."""
     import os, subprocess
     out = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     os.makedirs(os.path.join(root, "gpurun_out"), exist_ok=True)
@@ -1473,7 +1473,7 @@ def test_edge_follow_oracle_observation_vector(edge_modes, arm):
 @pytest.mark.gpu
 def test_fresh_action_tensor_every_step_and_non_default_stream(edge_modes):
     """The documented device-resident usage env.step(policy(obs)) hands over a NEW action tensor on most steps, possibly on a
-    non-default torch stream: results must equal the host-action path step for step (the step graph is not re-captured per pointer,
+    non-default torch stream: results must equal the host-action path step for step (each step reads the tensor it is given,
     the env runs on torch's current stream so reads / writes are ordered with the policy's kernels)."""
     import torch
     import tactile_gym_amd as tg

@@ -1,8 +1,8 @@
 """The per-kernel durations bench.py quotes (tg_profile_enable(2): the kernels' own clock, csrc/tg_kt.hpp) against the step they are part of.
 
 VERDICT r4 found bench lines whose HIP-event kernel durations added up to MORE than the step (47.0 > 44.1 us): an event pair carries 3 - 5 us of
-its own.  The own-clock figures - every wavefront of the first / last 2048 workgroups stamps wall_clock64 at its start / end, the step stays
-one hipGraph - must fit: their sum per step below the measured step time, each class positive, and the event figures above them by roughly
+its own.  The own-clock figures - every wavefront of the first / last 2048 workgroups stamps wall_clock64 at its start / end, no host call between
+the step's launches - must fit: their sum per step below the measured step time, each class positive, and the event figures above them by roughly
 what an empty event pair measures."""
 import time
 
@@ -29,7 +29,7 @@ def test_kernel_clock_durations_fit_inside_the_step():
         v.step_random_async(9, 20 + k)
     v.sync()
     step_ms = 1e3 * (time.perf_counter() - t0) / steps
-    v.profile("clock")                                   # re-captures the graph with the stamp slots in its kernels' arguments
+    v.profile("clock")                                   # the stamp slots go into the kernels' arguments
     for k in range(steps):
         v.step_random_async(9, 20 + steps + k, restart=(k == 0))
     v.sync()
@@ -41,7 +41,7 @@ def test_kernel_clock_durations_fit_inside_the_step():
     v.sync()
     ev = v.profile_get()
     v.profile(False)
-    v.step_random_async(9, 1000, restart=True)           # the plain graph is captured again and runs
+    v.step_random_async(9, 1000, restart=True)           # the plain step runs again
     v.sync()
     # (round 6: edge_follow's auto-reset runs inside k_step's launch - no reset class unless TG_NO_INLINE_RESET is set)
     per = {k: clk[k + "_clock"][0] / max(clk[k + "_clock"][1], 1) for k in ("step", "render", "reset") if clk[k + "_clock"][1] > 0}
