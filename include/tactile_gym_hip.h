@@ -308,7 +308,8 @@ int tg_get_bank_stats(tg_ctx* ctx, int64_t* swapped, int64_t* late, int32_t* mod
 int tg_set_obs_targets(tg_ctx* ctx, int32_t count, void* const* dev_ptrs);
 int tg_select_obs_target(tg_ctx* ctx, int32_t index);
 /* How tg_step runs on this context: *mode = 1 one launch per step (tg_config.fused_step; csrc/tg_fused.hip), 0 separate step / reset / render
- * launches; *envs_per_wavefront = envs one wavefront steps and draws in the one-launch form (0 otherwise). */
+ * launches; *envs_per_wavefront = envs one wavefront steps and draws in the one-launch form; in the separate form, envs one wavefront of the
+ * last arm step launch stepped (16: k_step_quad, a quad of lanes per env; 64: a lane per env), 0 before the first such launch. */
 int tg_get_step_mode(tg_ctx* ctx, int32_t* mode, int32_t* envs_per_wavefront);
 int tg_pack_interior(tg_ctx* ctx, void* dst_dev);
 int tg_unpack_interior(tg_ctx* ctx, const void* src_dev, int32_t n_images, void* dst_dev);

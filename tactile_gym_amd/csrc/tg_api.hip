@@ -294,12 +294,24 @@ struct Timer {
 // the UR5 only - on the MG400 a step is 0.7 ms of full ticks and the launch it would save is noise); returns whether it did
 template <typename T, int TOPO> static bool launch_step_t(tg_ctx* c, const float* d_actions, int reset_phase = -1) {
     const int n = c->cfg.num_envs;
+    c->step_envs_per_wave = 64;
     if (c->cfg.control_mode == TG_CONTROL_TCP_POSITION) {
         hipLaunchKernelGGL((k_step_pos<T, TOPO>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
                            (const EnvConst<T>*)c->d_const, c->st, d_actions);
         return false;
     }
     if constexpr (TOPO == 0 && std::is_same<T, double>::value) {   // (f64 physics: the configuration every BASELINE config runs)
+        if (c->kstep_quad) {   // a quad of lanes per env (k_step_quad): 4 n threads
+            const dim3 grid((unsigned)((4 * (size_t)n + 63) / 64));
+            c->step_envs_per_wave = 16;
+            if (reset_phase >= 0)
+                hipLaunchKernelGGL((k_step_quad<T, true>), grid, dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot, (const EnvConst<T>*)c->d_const,
+                                   c->st, d_actions, reset_phase, c->bank_mode != 0 ? (const BankDev*)c->d_bank : (const BankDev*)nullptr);
+            else
+                hipLaunchKernelGGL((k_step_quad<T, false>), grid, dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot, (const EnvConst<T>*)c->d_const,
+                                   c->st, d_actions, -1, (const BankDev*)nullptr);
+            return reset_phase >= 0;
+        }
         if (reset_phase >= 0) {
             hipLaunchKernelGGL((k_step<T, TOPO, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
                                (const EnvConst<T>*)c->d_const, c->st, d_actions, reset_phase, c->bank_mode != 0 ? (const BankDev*)c->d_bank : (const BankDev*)nullptr);
@@ -982,6 +994,7 @@ static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sen
     c->fused_pref = cfg->fused_step == TG_FUSED_OFF ? -1 : cfg->fused_step == TG_FUSED_ON ? 1 : 0;
     if (const char* e = getenv("TG_FUSED_STEP")) c->fused_pref = e[0] == '0' ? -1 : 1;   // A/B switch (tests, measurements)
     c->no_inline_reset = getenv("TG_NO_INLINE_RESET") != nullptr;
+    { const char* e = getenv("TG_KSTEP_QUAD"); c->kstep_quad = !(e != nullptr && e[0] == '0'); }
 #ifdef TG_TL_STAMPS
     c->rp.tl = s.tl;
 #endif

@@ -135,7 +135,7 @@ int tg_get_broadphase_totals(tg_ctx* c, int64_t* checks, int64_t* pairs, int64_t
 int tg_get_step_mode(tg_ctx* c, int32_t* mode, int32_t* envs_per_wavefront) {
     if (!c || !mode) return fail(-1, "NULL argument");
     *mode = use_fused_step(c) ? 1 : 0;
-    if (envs_per_wavefront) *envs_per_wavefront = *mode ? fused_envs_per_wave(c->cfg.num_envs) : 0;
+    if (envs_per_wavefront) *envs_per_wavefront = *mode ? fused_envs_per_wave(c->cfg.num_envs) : c->step_envs_per_wave;
     return 0;
 }
 

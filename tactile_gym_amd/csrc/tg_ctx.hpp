@@ -264,6 +264,8 @@ struct tg_ctx {
     // one launch per step (tg_fused.hip): -1 = TG_FUSED_STEP=0, 1 = TG_FUSED_STEP=1, 0 = where it measures faster (use_fused_step)
     int fused_pref = 0;
     bool no_inline_reset = false;  // TG_NO_INLINE_RESET (tests, measurements): finished envs are reset by the k_reset launch, never inside the step's launch
+    int step_envs_per_wave = 0;    // envs per wavefront of the last arm step launch: 16 k_step_quad, 64 k_step / k_step_pos (tg_get_step_mode)
+    bool kstep_quad = true;        // TG_KSTEP_QUAD=0 (tests, measurements): the UR5's f64 step runs k_step (a lane per env) instead of k_step_quad (a quad per env)
     // profiling by the kernels' own clock (tg_kt.hpp): per-wavefront {start, end} slots, reduced after every timed scope into {ticks, scopes}
     unsigned long long* d_kt = nullptr;          // [kt_slots][2]
     unsigned long long* d_kt_acc = nullptr;      // [8][2]

@@ -205,32 +205,54 @@ __device__ unsigned long long g_kstep_stamps[16];
 // Episode statistics (the Monitor wrapper the reference's callers always apply: sb3_helpers/rl_utils.py:17-30, 59): the return is the sum, in
 // double, of the float32 rewards as handed out - what a Monitor around this env would add up.  done: the finished episode's figures are
 // kept for info["episode"] and the running sum starts again.
-__device__ __forceinline__ void episode_step(const State& st, int env, float reward, bool done, int step_count) {
-    const double acc = st.ep_return[env] + (double)reward;
+__device__ __forceinline__ void episode_step(const State& st, int env, float reward, bool done, int step_count,
+                                             const double* prev = nullptr /* st.ep_return[env], loaded by the caller earlier */) {
+    const double acc = (prev != nullptr ? *prev : st.ep_return[env]) + (double)reward;
     if (done) { st.ep_final_return[env] = (float)acc; st.ep_final_len[env] = step_count; }
     st.ep_return[env] = done ? 0.0 : acc;
 }
 
+template <typename T, typename TcpRot, typename CamFrame>
+__device__ __forceinline__ bool finish_env_from(const EnvConst<T>& c, const State& st, int env, V3<T> ptcp, TcpRot rot, CamFrame cam, T edge_ang,
+                                                int step_count, bool write_reward_done, bool lazy_rpy, const T* pre_sc = nullptr,
+                                                const double* pre_ep = nullptr);
 template <typename T, int TOPO>
 __device__ __forceinline__ bool finish_env(const DevRobot<T>& m, const EnvConst<T>& c, const State& st, int env, const T (&q)[Topo<TOPO>::N],
                                            T edge_ang, int step_count, bool write_reward_done, const JointTrig<T, Topo<TOPO>::N>* trig = nullptr,
                                            bool lazy_rpy = false /* k_step: tcp_rpy is a read-back only, tg_get_state recomputes it (k_refresh_rpy) */) {
-    const int n = c.num_envs;
-    bool done_flag = false;   // what went into st.done[env], for a caller that resets the env in the same launch (k_step<.., true>)
     Kin<T, TOPO> k;
     if (trig != nullptr) forward_kinematics<T, TOPO, true>(m, q, k, trig);
     else forward_kinematics<T, TOPO>(m, q, k);
     V3<T> ptcp; M3<T> Rtcp;
     link_frame<T, TOPO>(k, m.tcp_link, m.tcp_pos, m.tcp_rot, ptcp, Rtcp);
+    return finish_env_from<T>(c, st, env, ptcp, [&]() { return Rtcp; },
+                              [&](V3<T>& pc, V3<T>& f, V3<T>& up) {   // camera frame = sensor-body frame o cam offset
+                                  V3<T> pb; M3<T> Rb;
+                                  link_frame<T, TOPO>(k, m.sensor_link, m.sensor_pos, m.sensor_rot, pb, Rb);
+                                  pc = pb + mul(Rb, load_v3(c.cam_pos));
+                                  const M3<T> Rc = mul(Rb, c.cam_rot);
+                                  f = mk(Rc.m[0], Rc.m[3], Rc.m[6]); up = mk(Rc.m[2], Rc.m[5], Rc.m[8]);
+                              },
+                              edge_ang, step_count, write_reward_done, lazy_rpy);
+}
+// finish_env from the TCP frame on.  rot(): the TCP rotation; cam(pc, f, up): the camera's position, forward axis R[:,0] and up axis
+// R[:,2] - each asked for where it is needed, so that k_step_quad gathers them from the quad's lanes only there.  pre_sc / pre_ep: the
+// env's edge_sc pair and ep_return, loaded by the caller at the start of its step (k_step_quad), else read here.
+template <typename T, typename TcpRot, typename CamFrame>
+__device__ __forceinline__ bool finish_env_from(const EnvConst<T>& c, const State& st, int env, V3<T> ptcp, TcpRot rot, CamFrame cam, T edge_ang,
+                                                int step_count, bool write_reward_done, bool lazy_rpy, const T* pre_sc, const double* pre_ep) {
+    const int n = c.num_envs;
+    bool done_flag = false;   // what went into st.done[env], for a caller that resets the env in the same launch (k_step<.., true>)
     st.tcp_pos[0 * n + env] = (double)ptcp.x; st.tcp_pos[1 * n + env] = (double)ptcp.y; st.tcp_pos[2 * n + env] = (double)ptcp.z;
     if (!lazy_rpy) {
         T rpy[3];
-        { Q4<T> qq = quat_from_mat(Rtcp); euler_from_quat(qq, rpy[0], rpy[1], rpy[2]); }
+        { Q4<T> qq = quat_from_mat(rot()); euler_from_quat(qq, rpy[0], rpy[1], rpy[2]); }
         st.tcp_rpy[0 * n + env] = (double)rpy[0]; st.tcp_rpy[1 * n + env] = (double)rpy[1]; st.tcp_rpy[2 * n + env] = (double)rpy[2];
     }
     T se = T(0), ce = T(1);   // stimulus yaw: edge angle for edge_follow (sin / cos cached by the reset), none for the surface
     if (c.env_kind == TG_ENV_EDGE_FOLLOW) {
-        if (lazy_rpy) { se = (T)st.edge_sc[0 * n + env]; ce = (T)st.edge_sc[1 * n + env]; }
+        if (lazy_rpy && pre_sc != nullptr) { se = pre_sc[0]; ce = pre_sc[1]; }
+        else if (lazy_rpy) { se = (T)st.edge_sc[0 * n + env]; ce = (T)st.edge_sc[1 * n + env]; }
         else { tsincos(edge_ang, &se, &ce); st.edge_sc[0 * n + env] = (double)se; st.edge_sc[1 * n + env] = (double)ce; }
     }
     if (write_reward_done && c.env_kind == TG_ENV_EDGE_FOLLOW) {
@@ -248,7 +270,7 @@ __device__ __forceinline__ bool finish_env(const DevRobot<T>& m, const EnvConst<
         st.reward[env] = (float)reward;
         st.done[env] = done ? 1 : 0;
         done_flag = done;
-        episode_step(st, env, (float)reward, done, step_count);
+        episode_step(st, env, (float)reward, done, step_count, pre_ep);
     }
     TG_KSTAMP(5)
     if ((write_reward_done || c.reward_mode == TG_REWARD_SPARSE) && c.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) {
@@ -265,6 +287,7 @@ __device__ __forceinline__ bool finish_env(const DevRobot<T>& m, const EnvConst<
         V3<T> nrm{-gx_, -gy_, T(1)};
         nrm = (T(1) / norm(nrm)) * nrm;
         const T gdx = ptcp.x - (T)st.goal[0 * n + env], gdy = ptcp.y - (T)st.goal[1 * n + env], gdz = ptcp.z - (T)st.goal[2 * n + env];
+        const M3<T> Rtcp = rot();
         T reward;
         if (c.surf_vertical) {   // the `vertical_simplex` branches (:703-758) on the flipped surface_array / normals (:486-516); vert_env :66-81
             nrm = mul(c.stim_R, nrm);
@@ -294,7 +317,7 @@ __device__ __forceinline__ bool finish_env(const DevRobot<T>& m, const EnvConst<
             st.reward[env] = (float)out;
             st.done[env] = (at_goal || step_count >= c.max_steps) ? 1 : 0;
             done_flag = at_goal || step_count >= c.max_steps;
-            episode_step(st, env, (float)out, at_goal || step_count >= c.max_steps, step_count);
+            episode_step(st, env, (float)out, at_goal || step_count >= c.max_steps, step_count, pre_ep);
         }
     }
     if (c.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO && st.feature != nullptr) {
@@ -310,12 +333,9 @@ __device__ __forceinline__ bool finish_env(const DevRobot<T>& m, const EnvConst<
         }
     }
     TG_KSTAMP(6)
-    // camera frame = sensor-body frame o cam offset; eye axes (right, up, -forward) with forward = R[:,0], up = R[:,2]
-    V3<T> pb; M3<T> Rb;
-    link_frame<T, TOPO>(k, m.sensor_link, m.sensor_pos, m.sensor_rot, pb, Rb);
-    const V3<T> pc = pb + mul(Rb, load_v3(c.cam_pos));
-    const M3<T> Rc = mul(Rb, c.cam_rot);
-    V3<T> f{Rc.m[0], Rc.m[3], Rc.m[6]}, up{Rc.m[2], Rc.m[5], Rc.m[8]};
+    // eye axes (right, up, -forward) with forward = R[:,0], up = R[:,2] of the camera frame
+    V3<T> pc, f, up;
+    cam(pc, f, up);
     f = (T(1) / norm(f)) * f;
     V3<T> s = cross(f, up);
     s = (T(1) / norm(s)) * s;
@@ -541,24 +561,34 @@ template <typename T> __device__ __forceinline__ void scale_actions(const EnvCon
     }
 }
 
+template <typename T, int TOPO, typename TcpRot>
+__device__ __forceinline__ void tcp_velocity_solve(const DevRobot<T>& m, const EnvConst<T>& c, const Kin<T, TOPO>& k, V3<T> ptcp, TcpRot rot,
+                                                   T (&vels)[6], T (&qd_des)[Topo<TOPO>::N], T work_dz);
 // BaseRobotArm.tcp_velocity_control (base_robot_arm.py:281-332): TCP limit check, work -> world twist, Jacobian inverse.
 template <typename T, int TOPO>
 __device__ __forceinline__ void tcp_velocity_control(const DevRobot<T>& m, const EnvConst<T>& c, const T (&q)[Topo<TOPO>::N], T (&vels)[6],
                                                      T (&qd_des)[Topo<TOPO>::N], const JointTrig<T, Topo<TOPO>::N>* trig = nullptr,
                                                      T work_dz = T(0) /* per-env z offset of the work-frame origin (object_roll) */) {
-    constexpr int N = Topo<TOPO>::N;
     Kin<T, TOPO> k;
     if (trig != nullptr) forward_kinematics<T, TOPO, true>(m, q, k, trig);
     else forward_kinematics<T, TOPO>(m, q, k);
     V3<T> ptcp; M3<T> Rtcp;
     link_frame<T, TOPO>(k, m.tcp_link, m.tcp_pos, m.tcp_rot, ptcp, Rtcp);
     TG_KSTAMP(10)
+    tcp_velocity_solve<T, TOPO>(m, c, k, ptcp, [&]() { return Rtcp; }, vels, qd_des, work_dz);
+}
+// The controller from the TCP frame on.  k: only the joint origins and axes are read; rot(): the TCP rotation, asked for only where a
+// wavefront needs the work-frame orientation (k_step_quad gathers it from the quad's lanes there).
+template <typename T, int TOPO, typename TcpRot>
+__device__ __forceinline__ void tcp_velocity_solve(const DevRobot<T>& m, const EnvConst<T>& c, const Kin<T, TOPO>& k, V3<T> ptcp, TcpRot rot,
+                                                   T (&vels)[6], T (&qd_des)[Topo<TOPO>::N], T work_dz) {
+    constexpr int N = Topo<TOPO>::N;
     V3<T> wpos; T wrpy[3] = {T(0), T(0), T(0)}, rpyw[3];
     // The work-frame orientation of the TCP (matrix -> quaternion -> euler -> quaternion -> multiply -> euler: nine f64 transcendentals)
     // only enters the limit check of the rotational components; a movement mode without rotational velocity (a zero stays a zero in that
     // check) needs the position alone.  Wave-uniform.
     if (__any(vels[3] != T(0) || vels[4] != T(0) || vels[5] != T(0)))
-        world_to_work<T, false>(c, mk(ptcp.x, ptcp.y, ptcp.z - work_dz), Rtcp, wpos, wrpy, rpyw);
+        world_to_work<T, false>(c, mk(ptcp.x, ptcp.y, ptcp.z - work_dz), rot(), wpos, wrpy, rpyw);
     else
         wpos = load_v3(c.work_inv_pos) + mul(c.work_Rinv, mk(ptcp.x, ptcp.y, ptcp.z - work_dz));
     const T cur[6] = {wpos.x, wpos.y, wpos.z, wrpy[0], wrpy[1], wrpy[2]};
@@ -589,15 +619,55 @@ __device__ __forceinline__ void tcp_velocity_control(const DevRobot<T>& m, const
     }
 }
 
+// tcp_velocity_control and finish_env on a quad of lanes (k_step_quad): the kinematics by rows (tg_physics.hpp: KinRow), then what the
+// rest reads - the TCP position, the joint origins and axes of the Jacobian, the camera frame's position and axes - gathered to every
+// lane of the quad, which all carry on with the same code as one lane does.
+template <typename T, int TOPO>
+__device__ __forceinline__ void tcp_velocity_control_quad(const DevRobot<T>& m, const EnvConst<T>& c, T (&vels)[6], T (&qd_des)[Topo<TOPO>::N],
+                                                          const JointTrig<T, Topo<TOPO>::N>& trig) {
+    constexpr int N = Topo<TOPO>::N;
+    KinRow<T, TOPO> kr;
+    forward_kinematics_quad<T, TOPO>(m, kr, trig);
+    T pr; V3<T> Rr;
+    link_frame_quad<T, TOPO>(kr, m.tcp_link, m.tcp_pos, m.tcp_rot, pr, Rr);
+    const V3<T> ptcp = quad_gather(pr);
+    Kin<T, TOPO> k;   // origins and axes only: tcp_jacobian reads nothing else
+#pragma unroll
+    for (int i = 0; i < N; ++i) { k.o[i] = quad_gather(kr.o[i]); k.a[i] = quad_gather(kr.a[i]); }
+    TG_KSTAMP(10)
+    tcp_velocity_solve<T, TOPO>(m, c, k, ptcp, [&]() { return quad_gather(Rr); }, vels, qd_des, T(0));
+}
+template <typename T, int TOPO>
+__device__ __forceinline__ bool finish_env_quad(const DevRobot<T>& m, const EnvConst<T>& c, const State& st, int env, T edge_ang, int step_count,
+                                                const JointTrig<T, Topo<TOPO>::N>& trig, const T (&pre_sc)[2], const double& pre_ep) {
+    KinRow<T, TOPO> kr;
+    forward_kinematics_quad<T, TOPO>(m, kr, trig);
+    T pr; V3<T> Rr;
+    link_frame_quad<T, TOPO>(kr, m.tcp_link, m.tcp_pos, m.tcp_rot, pr, Rr);
+    return finish_env_from<T>(c, st, env, quad_gather(pr), [&]() { return quad_gather(Rr); },
+                              [&](V3<T>& pc, V3<T>& f, V3<T>& up) {
+                                  T pbr; V3<T> Rbr;
+                                  link_frame_quad<T, TOPO>(kr, m.sensor_link, m.sensor_pos, m.sensor_rot, pbr, Rbr);
+                                  const T pcr = pbr + row_dot(Rbr, load_v3(c.cam_pos));
+                                  const V3<T> Rcr = row_mul(Rbr, c.cam_rot);
+                                  pc = quad_gather(pcr); f = quad_gather(Rcr.x); up = quad_gather(Rcr.z);
+                              },
+                              edge_ang, step_count, true, true, pre_sc, &pre_ep);
+}
+
 // encode_actions of the arm-only tasks: the policy's dimensions scattered into the 6-vector the controller takes.
 template <typename T>
 __device__ __forceinline__ void encode_arm_actions(const EnvConst<T>& c, const State& st, int env, const float* __restrict__ a, T (&enc)[6]) {
     const int n = c.num_envs;
     if (c.env_kind == TG_ENV_EDGE_FOLLOW) {               // encode_actions (edge_follow_env.py:345-369)
         enc[0] = (T)a[0]; enc[1] = (T)a[1];
-        if (c.movement_mode == TG_MOVE_XYZ) enc[2] = (T)a[2];
-        else if (c.movement_mode == TG_MOVE_XYRZ) enc[5] = (T)a[2];
-        else if (c.movement_mode == TG_MOVE_XYZRZ) { enc[2] = (T)a[2]; enc[5] = (T)a[3]; }
+        // (each element by its own select: an assignment to enc[2] or enc[5] chosen by the mode became one store at a computed index,
+        //  which put enc in scratch memory)
+        const int mm = c.movement_mode;
+        const T a2 = (mm == TG_MOVE_XYZ || mm == TG_MOVE_XYRZ || mm == TG_MOVE_XYZRZ) ? (T)a[2] : T(0);
+        const T a3 = (mm == TG_MOVE_XYZRZ) ? (T)a[3] : T(0);
+        enc[2] = (mm == TG_MOVE_XYZ || mm == TG_MOVE_XYZRZ) ? a2 : enc[2];
+        enc[5] = mm == TG_MOVE_XYRZ ? a2 : (mm == TG_MOVE_XYZRZ ? a3 : enc[5]);
     } else if (c.surf_goal) {                             // surface_follow_goal_env.py:27-52: every dimension from the agent
         if (c.movement_mode == TG_SMOVE_YZ) { enc[1] = (T)a[0]; enc[2] = (T)a[1]; }
         else if (c.movement_mode == TG_SMOVE_YZRX) { enc[1] = (T)a[0]; enc[2] = (T)a[1]; enc[3] = (T)a[2]; }
@@ -620,9 +690,10 @@ __device__ __forceinline__ void encode_arm_actions(const EnvConst<T>& c, const S
 // ------------------------------------------------------------------------------------------------ step kernel
 // BaseTactileEnv.step (base_tactile_env.py:166-185): encode + scale the action, tcp_velocity_control
 // (base_robot_arm.py:281-332), action_repeat sim ticks (robot.py:182-183), reward / done, render transform.
-// One env's step, one lane (k_step: 64 consecutive envs per wavefront; k_step_render in tg_fused.hip: the envs of one render wavefront).
+// One env's step, one lane (k_step: 64 consecutive envs per wavefront; k_step_render in tg_fused.hip: the envs of one render wavefront), or
+// QUAD: one quad of lanes (k_step_quad: 16 envs per wavefront), whose four lanes run this code alike except for the kinematics.
 // Returns whether this step ran a full solve (development stamps only).
-template <typename T, int TOPO>
+template <typename T, int TOPO, bool QUAD = false>
 __device__ __forceinline__ bool step_env(const DevRobot<T>& m, const EnvConst<T>& c, const State& st, int env, const float* __restrict__ actions,
                                          bool* done_out = nullptr /* what the step wrote to st.done[env] */) {
     constexpr int N = Topo<TOPO>::N;
@@ -631,6 +702,18 @@ __device__ __forceinline__ bool step_env(const DevRobot<T>& m, const EnvConst<T>
     T q[N], qd[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) { q[i] = (T)st.q[i * n + env]; qd[i] = (T)st.qd[i * n + env]; }
+    // QUAD: every load of the env's state this step makes, issued here in one batch ahead of its first store.  (The vector memory counter
+    // counts stores too, so a load issued behind a store is waited for together with the store; and the State pointers may alias, so the
+    // compiler does not move the later loads up by itself.)  Nothing this step stores before their old place is among them.
+    int pre_lic = 0, pre_count = 0;
+    T pre_ts[N], pre_tc[N], pre_sc[2] = {T(0), T(1)};
+    double pre_ep = 0.0;
+    if constexpr (QUAD) {
+        pre_lic = st.licence[env]; pre_count = st.step_count[env]; pre_ep = st.ep_return[env];
+#pragma unroll
+        for (int i = 0; i < N; ++i) { pre_ts[i] = (T)st.trig_sc[i * n + env]; pre_tc[i] = (T)st.trig_sc[(8 + i) * n + env]; }
+        if (c.env_kind == TG_ENV_EDGE_FOLLOW) { pre_sc[0] = (T)st.edge_sc[0 * n + env]; pre_sc[1] = (T)st.edge_sc[1 * n + env]; }
+    }
     T enc[6] = {T(0), T(0), T(0), T(0), T(0), T(0)};
     if (st.draw != nullptr) {
         // tg_step_random: action_space.sample() for this env inside the step (element i = env * act_dim + j of draw `counter`, the arithmetic of
@@ -654,19 +737,23 @@ __device__ __forceinline__ bool step_env(const DevRobot<T>& m, const EnvConst<T>
     }
     T vels[6];
     scale_actions<T>(c, enc, vels);
-    const int step_count = st.step_count[env] + 1;
+    const int step_count = (QUAD ? pre_count : st.step_count[env]) + 1;
     st.step_count[env] = step_count;
-    JointTrig<T, N> trig;             // sin/cos of the joint angles, advanced by angle addition through the ticks.  While the licence
-    const int lic = st.licence[env];  // below holds they are carried over from the last step (q has not changed in between: a reset or
-    if (__all(lic > 0)) {             // tg_set_joint_state drops the licence), i.e. they are evaluated exactly once per 8 steps
-#pragma unroll
-        for (int i = 0; i < N; ++i) { trig.s[i] = (T)st.trig_sc[i * n + env]; trig.c[i] = (T)st.trig_sc[(8 + i) * n + env]; }
+    JointTrig<T, N> trig;                              // sin/cos of the joint angles, advanced by angle addition through the ticks.  While the
+    const int lic = QUAD ? pre_lic : st.licence[env];  // licence below holds they are carried over from the last step (q has not changed in
+    if (__all(lic > 0)) {                              // between: a reset or tg_set_joint_state drops the licence), i.e. they are evaluated
+#pragma unroll                                         // exactly once per 8 steps
+        for (int i = 0; i < N; ++i) {
+            if constexpr (QUAD) { trig.s[i] = pre_ts[i]; trig.c[i] = pre_tc[i]; }
+            else { trig.s[i] = (T)st.trig_sc[i * n + env]; trig.c[i] = (T)st.trig_sc[(8 + i) * n + env]; }
+        }
     } else {
         trig_init<T, N>(q, trig);
     }
     T qd_des[N];
     TG_KSTAMP(1)
-    tcp_velocity_control<T, TOPO>(m, c, q, vels, qd_des, &trig);
+    if constexpr (QUAD) tcp_velocity_control_quad<T, TOPO>(m, c, vels, qd_des, trig);
+    else tcp_velocity_control<T, TOPO>(m, c, q, vels, qd_des, &trig);
     TG_KSTAMP(2)
 #pragma unroll
     for (int i = 0; i < N; ++i) st.qd_target[i * n + env] = (double)qd_des[i];
@@ -724,7 +811,9 @@ __device__ __forceinline__ bool step_env(const DevRobot<T>& m, const EnvConst<T>
 #pragma unroll
     for (int i = 0; i < N; ++i) { st.trig_sc[i * n + env] = (double)trig.s[i]; st.trig_sc[(8 + i) * n + env] = (double)trig.c[i]; }
     TG_KSTAMP(4)
-    const bool done = finish_env<T, TOPO>(m, c, st, env, q, (T)st.edge_ang[env], step_count, true, &trig, true);
+    bool done;
+    if constexpr (QUAD) done = finish_env_quad<T, TOPO>(m, c, st, env, T(0) /* unread: the edge angle's sin / cos are in pre_sc */, step_count, trig, pre_sc, pre_ep);
+    else done = finish_env<T, TOPO>(m, c, st, env, q, (T)st.edge_ang[env], step_count, true, &trig, true);
     if (done_out != nullptr) *done_out = done;
     return ran_full;
 }
@@ -791,6 +880,31 @@ __global__ __launch_bounds__(64) void k_step(const DevRobot<T>* __restrict__ mp,
     const bool ran_full = step_env<T, TOPO>(*mp, *cp, st, env, actions, &done);
     if (RESET) {   // (the flag from a register: reading st.done[env] back is a memory round trip at the end of the step's chain, +1 us)
         if (done) reset_or_swap<T, TOPO>(mp, cp, st, env, true, reset_phase, bd);   // (out of line - a noinline wrapper - was measured: k_step 21.7 us, the call changes the whole kernel's register allocation)
+    }
+    draw_counter_advance(st);
+    TG_KSTAMP(9)
+#ifdef TG_KSTEP_STAMPS
+    if (blockIdx.x == 0 && threadIdx.x == 0) g_kstep_stamps[15] = ran_full ? 1 : 0;
+#else
+    (void)ran_full;
+#endif
+}
+
+// k_step for the UR5 on a quad of lanes per env (lanes 4e .. 4e + 3 of the grid): 16 envs per wavefront, 4x the wavefronts of k_step.  The
+// kinematics of the step's two poses run by rows (step_env<.., true>); everything else runs alike on the four lanes, which therefore store
+// the same value to the same address.  The licence and fast-forward votes cover the wavefront's 16 envs.  The in-step reset and every
+// atomic run on the quad's first lane only.  TG_KSTEP_QUAD=0 selects k_step instead.
+template <typename T, bool RESET = false>
+__global__ __launch_bounds__(64) void k_step_quad(const DevRobot<T>* __restrict__ mp, const EnvConst<T>* __restrict__ cp, State st,
+                                                  const float* __restrict__ actions, int reset_phase, const BankDev* __restrict__ bd) {
+    KtScope kt_scope_(st.kt);
+    const int env = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 2);
+    TG_TL(st.tl, 1);
+    if (env >= cp->num_envs) return;   // (a whole quad: its lanes share the env)
+    bool done = false;
+    const bool ran_full = step_env<T, 0, true>(*mp, *cp, st, env, actions, &done);
+    if (RESET) {
+        if (done && (threadIdx.x & 3) == 0) reset_or_swap<T, 0>(mp, cp, st, env, true, reset_phase, bd);
     }
     draw_counter_advance(st);
     TG_KSTAMP(9)

@@ -258,6 +258,75 @@ template <typename T, int TOPO> __device__ __forceinline__ void link_frame(const
     }
 }
 
+// ------------------------------------------------------------------------------------------------ kinematics on a quad of lanes
+// One env per quad of lanes (k_step_quad): lane r < 3 of the quad carries row r of every link rotation and component r of the link
+// origins and axes; lane 3 repeats row 2.  Every element is the expression of mul() / forward_kinematics() above, in the same order, so
+// the rows hold the bits the one-lane evaluation holds.  Values cross lanes only by 32-bit DPP quad_perm moves (exact copies).
+template <typename T, int TOPO> struct KinRow {
+    static constexpr int N = Topo<TOPO>::N;
+    V3<T> R[N];    // row r of R[i]
+    T o[N], a[N];  // component r of o[i], a[i]
+};
+__device__ __forceinline__ int quad_row() { const int r = (int)(threadIdx.x & 3); return r == 3 ? 2 : r; }
+template <typename T> __device__ __forceinline__ T pick3(int r, T x, T y, T z) { return r == 0 ? x : (r == 1 ? y : z); }
+// row r of A times B (row r of mul(A, B)), and row r of A dotted with v (component r of mul(A, v))
+template <typename T> __device__ __forceinline__ V3<T> row_mul(V3<T> a, const M3<T>& B) {
+    return {a.x * B.m[0] + a.y * B.m[3] + a.z * B.m[6], a.x * B.m[1] + a.y * B.m[4] + a.z * B.m[7], a.x * B.m[2] + a.y * B.m[5] + a.z * B.m[8]};
+}
+template <typename T> __device__ __forceinline__ T row_dot(V3<T> a, V3<T> v) { return a.x * v.x + a.y * v.y + a.z * v.z; }
+// lane K of the quad, to every lane of the quad
+template <int K> __device__ __forceinline__ double quad_bcast(double x) {
+    const long long b = __double_as_longlong(x);
+    const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), K * 0x55, 0xF, 0xF, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), K * 0x55, 0xF, 0xF, false);
+    return __longlong_as_double(((long long)hi << 32) | (long long)(unsigned)lo);
+}
+template <int K> __device__ __forceinline__ float quad_bcast(float x) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), K * 0x55, 0xF, 0xF, false));
+}
+// the vector whose component r lane r holds
+template <typename T> __device__ __forceinline__ V3<T> quad_gather(T x) { return {quad_bcast<0>(x), quad_bcast<1>(x), quad_bcast<2>(x)}; }
+template <typename T> __device__ __forceinline__ M3<T> quad_gather(V3<T> row) {
+    const V3<T> c0 = quad_gather(row.x), c1 = quad_gather(row.y), c2 = quad_gather(row.z);
+    return M3<T>{{c0.x, c1.x, c2.x, c0.y, c1.y, c2.y, c0.z, c1.z, c2.z}};
+}
+
+// forward_kinematics<T, TOPO, true> by rows: each lane still forms the whole link rotation Rl (it needs all of it), the products only by its row
+template <typename T, int TOPO>
+__device__ __forceinline__ void forward_kinematics_quad(const DevRobot<T>& m, KinRow<T, TOPO>& k, const JointTrig<T, Topo<TOPO>::N>& trig) {
+    constexpr int N = Topo<TOPO>::N;
+    const int r = quad_row();
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int p = Topo<TOPO>::parent(i);
+        const V3<T> ax = load_v3(m.jaxis[i]);
+        const T sq = trig.s[i], cq = trig.c[i];
+        M3<T> Rl;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Rl.m[e] = m.fkA[i][e] + cq * m.fkB[i][e] + sq * m.fkC[i][e];
+        if (p < 0) {
+            k.R[i] = mk(pick3(r, Rl.m[0], Rl.m[3], Rl.m[6]), pick3(r, Rl.m[1], Rl.m[4], Rl.m[7]), pick3(r, Rl.m[2], Rl.m[5], Rl.m[8]));
+            k.o[i] = pick3(r, m.jpos[i][0], m.jpos[i][1], m.jpos[i][2]);
+        } else {
+            k.R[i] = row_mul(k.R[p], Rl);
+            k.o[i] = k.o[p] + row_dot(k.R[p], load_v3(m.jpos[i]));
+        }
+        k.a[i] = row_dot(k.R[i], ax);
+    }
+}
+// link_frame by rows: component r of the frame's origin, row r of its rotation
+template <typename T, int TOPO> __device__ __forceinline__ void link_frame_quad(const KinRow<T, TOPO>& k, int link, const T* fpos, const T* frot,
+                                                                                  T& pos, V3<T>& rot) {
+    constexpr int N = Topo<TOPO>::N;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        if (i == link) {
+            pos = k.o[i] + row_dot(k.R[i], load_v3(fpos));
+            rot = row_mul(k.R[i], load_m3(frot));
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ dynamics
 // Outputs of one dynamics evaluation at (q, qd):
 //   hbias  = ID(q, qd, 0)      (gravity + velocity-product generalised forces: the gravity-compensation torque)
