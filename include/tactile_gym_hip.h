@@ -24,7 +24,7 @@ extern "C" {
 
 #define TG_MAX_DOF 8
 #define TG_MAX_BODIES_PER_LINK 4
-#define TG_ABI_VERSION 14
+#define TG_ABI_VERSION 15
 #define TG_MAX_TRAJ_POINTS 16
 
 /* ---- robot description: the flattened URDF (replaces loadURDF, robots/arms/robot.py:95-112) --------------------- */
@@ -565,6 +565,24 @@ int tg_sample_actions(tg_ctx* ctx, uint64_t seed, uint64_t counter, float* dev_a
  * actions are the context's own buffer (tg_get_actions: device float32 [num_envs][act_dim]); draw k equals tg_sample_actions(seed, k). */
 int tg_step_random(tg_ctx* ctx, uint64_t seed, uint64_t first_draw, int32_t restart);
 int tg_get_actions(tg_ctx* ctx, void** dev_actions);
+
+/* ---- frame stack: stable_baselines3's VecFrameStack(venv, n_stack) on the device (sb3_helpers/rl_utils.py:32, 65; ABI v15) -------------------------
+ * tg_set_frame_stack(n), 2 <= n <= 8: every observation key is also kept as a stack of its last n frames along its last axis, oldest first - tactile
+ * uint8 [num_envs][H][W][n], oracle float32 [num_envs][dim * n] (when tg_enable_oracle_obs was called first), extended_feature float32
+ * [num_envs][feature_dim * n] (push 12, roll 3, surface_follow 6 of the 12-wide rows).  tg_reset zeroes the reset envs' stacks and puts the reset
+ * observation in the newest slot.  Every tg_step / tg_step_random shifts every stack one slot toward the oldest and puts the step's observation in the
+ * newest slot; an env that is done first has its stack zeroed and, with auto_reset, its terminal stack written: the old stack's newest n - 1 slots,
+ * then the terminal observation (rows valid where done).  One launch per step / reset, after the observations.  n = 1 frees the stacks (no launch).
+ * Refused together with tg_set_obs_targets.  TG_STACK_REWRITE_ALL=1 (read once per process) turns off the kernel's unchanged-block skip. */
+#define TG_OBS_KEY_TACTILE 0
+#define TG_OBS_KEY_ORACLE 1
+#define TG_OBS_KEY_FEATURE 2
+int tg_set_frame_stack(tg_ctx* ctx, int32_t n);
+int tg_get_frame_stack(tg_ctx* ctx, int32_t* n);
+int tg_get_obs_stack(tg_ctx* ctx, int32_t key, int32_t terminal, void** dev_ptr);
+int tg_copy_obs_stack(tg_ctx* ctx, int32_t key, int32_t terminal, void* host_dst);                /* synchronises */
+/* The stacks of `count` chosen envs only (the finished envs' terminal stacks): env_ids[k]'s row goes to host_dst + k * row_bytes. */
+int tg_copy_obs_stack_rows(tg_ctx* ctx, int32_t key, int32_t terminal, const int32_t* env_ids, int32_t count, void* host_dst);
 #ifdef __cplusplus
 }
 #endif

@@ -684,6 +684,35 @@ static void bank_refill(tg_ctx* c) {
 
 using namespace tg;
 
+// The frame stack's update after a step (flag = st.done) or a reset (flag = the reset mask, null: every env); tg_stack.hip.  Reads the finished
+// observation buffers of that step / reset, so it is the last launch of the sequence.
+static int feature_dim(const tg_ctx* c) { return c->cfg.env_kind == TG_ENV_OBJECT_ROLL ? 3 : c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO ? 6 : 12; }
+static bool stack_rewrite_all() {
+    static const bool on = [] { const char* e = getenv("TG_STACK_REWRITE_ALL"); return e && e[0] == '1'; }();   // read once per process
+    return on;
+}
+static int stack_update(tg_ctx* c, int mode, const uint8_t* flag) {
+    if (c->stack_n <= 1) return 0;
+    StackArgs a;
+    a.num_envs = c->cfg.num_envs; a.H = c->H; a.W = c->W; a.n = c->stack_n; a.mode = mode; a.rewrite_all = stack_rewrite_all() ? 1 : 0;
+    a.flag = flag;
+    const bool term = mode == kStackStep && c->cfg.auto_reset;
+    a.frame = c->d_obs; a.term_frame = c->d_term; a.tmpl = c->d_tile_tmpl; a.stack = c->d_stack; a.rec = c->d_stack_rec;
+    a.term_stack = term ? c->d_stack_term : nullptr;
+    for (int k = 0; k < 2; ++k) {
+        if (!c->d_stack_vec[k]) continue;
+        StackVec& v = a.vec[k];
+        v.dim = c->stack_vec_dim[k];
+        v.pitch = k == 0 ? v.dim : 12;
+        v.src = k == 0 ? c->d_oracle : c->st.feature;
+        v.term = k == 0 ? c->d_oracle_term : c->st.term_feature;
+        v.stack = c->d_stack_vec[k];
+        v.term_stack = term ? c->d_stack_vec_term[k] : nullptr;
+    }
+    if (launch_frame_stack(a, c->stream) != 0) return fail(-2, "frame stack launch failed");
+    return 0;
+}
+
 extern "C" {
 
 const char* tg_last_error(void) { return g_err.c_str(); }
@@ -1100,6 +1129,8 @@ int tg_destroy(tg_ctx* c) {
                     s.step_count, s.reset_ticks, s.licence, s.sweeps, s.tmpl_stats, s.trig_sc, s.edge_sc, s.rng, s.dir, s.goal, s.heights, s.hsel, s.accum, s.surf_zoff, s.noise_seed, s.body_pos, s.body_rot, s.body_v, s.body_w, s.ext_pos, s.gravity, s.ext_pending, s.ball, s.dish, const_cast<double*>(s.spin_hulls), s.reset_tmpl, s.traj, s.obj_mass, s.goal_id, s.contact_code, s.term_feature, s.mani, const_cast<void*>(s.tip_verts), c->d_nodef_dep, c->d_nodef_gray, c->d_border, c->d_verts, c->d_soup, c->d_tris,
                     c->d_obs, c->d_term, c->d_mask, c->d_actions, c->d_scene_verts, c->d_scene_xf, c->d_scene_spheres, c->d_scene_tris, c->d_scene_attr, c->d_scene_local, c->d_scene_static, c->d_scene_chunks, c->d_vis, c->d_vis_term, c->d_oracle, c->d_oracle_term, c->d_int_idx, c->d_int_rank, c->d_tile_tmpl, c->d_episode, c->d_block_tables};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+    for (void* p : {(void*)c->d_stack, (void*)c->d_stack_term, (void*)c->d_stack_rec, (void*)c->d_stack_vec[0], (void*)c->d_stack_vec[1],
+                    (void*)c->d_stack_vec_term[0], (void*)c->d_stack_vec_term[1]}) if (p) (void)hipFree(p);
     if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
     if (c->bank_stream) { (void)hipStreamSynchronize(c->bank_stream); (void)hipStreamDestroy(c->bank_stream); }
     if (c->ev_bank) (void)hipEventDestroy(c->ev_bank);
@@ -1147,6 +1178,7 @@ int tg_reset(tg_ctx* c, const uint8_t* host_mask) {
     render(c, dmask, false);
     if (c->scene_every_step) scene_draw(c, dmask, false);
     if (c->oracle_every_step) oracle_draw(c, c->d_oracle);
+    if (int rc = stack_update(c, kStackReset, dmask)) return rc;
     TG_HIP(hipGetLastError());
     return 0;
 }
@@ -1266,6 +1298,7 @@ int tg_step(tg_ctx* c, const float* actions, int32_t on_device) {
         d_act = c->d_actions;
     }
     enqueue_step(c, d_act);
+    if (int rc = stack_update(c, kStackStep, c->st.done)) return rc;
     bank_refill(c);
     TG_HIP(hipGetLastError());
     return 0;
@@ -1306,6 +1339,7 @@ int tg_step_random(tg_ctx* c, uint64_t seed, uint64_t first_draw, int32_t restar
     } scope(c, in_kernel);
     if (!in_kernel) sample();
     enqueue_step(c, c->d_actions);
+    if (int rc = stack_update(c, kStackStep, c->st.done)) return rc;
     bank_refill(c);
     TG_HIP(hipGetLastError());
     return 0;
@@ -1314,6 +1348,7 @@ int tg_step_random(tg_ctx* c, uint64_t seed, uint64_t first_draw, int32_t restar
 int tg_set_obs_targets(tg_ctx* c, int32_t count, void* const* dev_ptrs) {
     if (!c || count < 0 || count > 2 || (count > 0 && !dev_ptrs)) return fail(-1, "tg_set_obs_targets: bad argument");
     for (int k = 0; k < count; ++k) if (!dev_ptrs[k]) return fail(-1, "tg_set_obs_targets: NULL target");   // (every argument is checked before anything is changed)
+    if (count > 0 && c->stack_n > 1) return fail(-1, "tg_set_obs_targets: a context with a frame stack (tg_set_frame_stack n > 1) draws into its own buffer only");
     TG_ENTER(c);
     TG_HIP(hipStreamSynchronize(c->stream));
     c->obs_sel = 0;
@@ -1362,6 +1397,7 @@ int tg_unpack_interior(tg_ctx* c, const void* src_dev, int32_t n_images, void* d
 }
 int tg_enable_oracle_obs(tg_ctx* c) {
     if (!c) return fail(-1, "NULL ctx");
+    if (c->stack_n > 1 && !c->oracle_every_step) return fail(-1, "tg_enable_oracle_obs: call it before tg_set_frame_stack");
     TG_ENTER(c);
     if (!c->d_oracle) TG_HIP(hipMalloc(&c->d_oracle, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
     if (!c->d_oracle_term) TG_HIP(hipMalloc(&c->d_oracle_term, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
@@ -1654,6 +1690,85 @@ int tg_copy_obs_rows(tg_ctx* c, int32_t visual, int32_t terminal, const int32_t*
         TG_HIP(hipStreamSynchronize(c->stream));
         memcpy(dst + (size_t)k0 * img, c->h_rows, (size_t)m * img);
     }
+    return 0;
+}
+
+// ---- frame stack (VecFrameStack on the device; tg_stack.hip) ----
+static void free_stack(tg_ctx* c) {
+    for (void** p : {(void**)&c->d_stack, (void**)&c->d_stack_term, (void**)&c->d_stack_rec, (void**)&c->d_stack_vec[0], (void**)&c->d_stack_vec[1],
+                     (void**)&c->d_stack_vec_term[0], (void**)&c->d_stack_vec_term[1]})
+        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    c->stack_vec_dim[0] = c->stack_vec_dim[1] = 0;
+    c->stack_n = 1;
+}
+int tg_set_frame_stack(tg_ctx* c, int32_t n) {
+    if (!c) return fail(-1, "NULL ctx");
+    if (n < 1 || n > kStackMax) return fail(-1, "tg_set_frame_stack: n must be in [1, 8]");
+    if (n > 1 && (c->obs_ext[0] || c->obs_ext[1])) return fail(-1, "tg_set_frame_stack: not with render targets of the caller (tg_set_obs_targets: sharded runs)");
+    TG_ENTER(c);
+    TG_HIP(hipStreamSynchronize(c->stream));
+    free_stack(c);
+    if (n == 1) return 0;
+    const size_t envs = (size_t)c->cfg.num_envs, img = envs * c->H * c->W * n, rec = envs * (c->H / 16) * (c->W / 16);
+    TG_HIP(hipMalloc(&c->d_stack, img)); TG_HIP(hipMalloc(&c->d_stack_term, img)); TG_HIP(hipMalloc(&c->d_stack_rec, rec));
+    TG_HIP(hipMemset(c->d_stack, 0, img)); TG_HIP(hipMemset(c->d_stack_term, 0, img));
+    TG_HIP(hipMemset(c->d_stack_rec, 0, rec));   // no slot holds the template: the first update writes every block
+    c->stack_vec_dim[0] = c->oracle_every_step ? oracle_dim(c) : 0;
+    c->stack_vec_dim[1] = env_has_feature(c->cfg.env_kind) ? feature_dim(c) : 0;
+    for (int k = 0; k < 2; ++k) {
+        if (!c->stack_vec_dim[k]) continue;
+        const size_t b = envs * c->stack_vec_dim[k] * n * sizeof(float);
+        TG_HIP(hipMalloc(&c->d_stack_vec[k], b)); TG_HIP(hipMalloc(&c->d_stack_vec_term[k], b));
+        TG_HIP(hipMemset(c->d_stack_vec[k], 0, b)); TG_HIP(hipMemset(c->d_stack_vec_term[k], 0, b));
+    }
+    c->stack_n = n;
+    TG_HIP(hipDeviceSynchronize());
+    return 0;
+}
+int tg_get_frame_stack(tg_ctx* c, int32_t* n) {
+    if (!c || !n) return fail(-1, "NULL argument");
+    *n = c->stack_n;
+    return 0;
+}
+// key TG_OBS_KEY_*: (device pointer, bytes per env row) of the current or terminal stack
+static int stack_buffer(tg_ctx* c, int32_t key, int32_t terminal, void** p, size_t* row) {
+    if (c->stack_n <= 1) return fail(-1, "no frame stack (tg_set_frame_stack n > 1)");
+    if (key == TG_OBS_KEY_TACTILE) {
+        *p = terminal ? c->d_stack_term : c->d_stack;
+        *row = (size_t)c->H * c->W * c->stack_n;
+        return 0;
+    }
+    const int k = key == TG_OBS_KEY_ORACLE ? 0 : key == TG_OBS_KEY_FEATURE ? 1 : -1;
+    if (k < 0) return fail(-1, "unknown observation key");
+    if (!c->d_stack_vec[k]) return fail(-1, k == 0 ? "no stacked oracle observation (tg_enable_oracle_obs before tg_set_frame_stack)" : "this env has no extended_feature observation");
+    *p = terminal ? c->d_stack_vec_term[k] : c->d_stack_vec[k];
+    *row = (size_t)c->stack_vec_dim[k] * c->stack_n * sizeof(float);
+    return 0;
+}
+int tg_get_obs_stack(tg_ctx* c, int32_t key, int32_t terminal, void** p) {
+    if (!c || !p) return fail(-1, "NULL argument");
+    size_t row = 0;
+    return stack_buffer(c, key, terminal, p, &row);
+}
+int tg_copy_obs_stack(tg_ctx* c, int32_t key, int32_t terminal, void* dst) {
+    if (!c || !dst) return fail(-1, "NULL argument");
+    TG_ENTER(c);
+    void* p = nullptr; size_t row = 0;
+    if (int rc = stack_buffer(c, key, terminal, &p, &row)) return rc;
+    TG_HIP(hipMemcpyAsync(dst, p, row * c->cfg.num_envs, hipMemcpyDeviceToHost, c->stream));
+    TG_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}
+int tg_copy_obs_stack_rows(tg_ctx* c, int32_t key, int32_t terminal, const int32_t* env_ids, int32_t count, void* dst) {
+    if (!c || count < 0 || (count > 0 && (!env_ids || !dst))) return fail(-1, "tg_copy_obs_stack_rows: bad argument");
+    TG_ENTER(c);
+    void* p = nullptr; size_t row = 0;
+    if (int rc = stack_buffer(c, key, terminal, &p, &row)) return rc;
+    for (int32_t k = 0; k < count; ++k)
+        if (env_ids[k] < 0 || env_ids[k] >= c->cfg.num_envs) return fail(-1, "tg_copy_obs_stack_rows: env id out of range");
+    for (int32_t k = 0; k < count; ++k)     // (a finished env's row: a few per step)
+        TG_HIP(hipMemcpyAsync((uint8_t*)dst + (size_t)k * row, (const uint8_t*)p + (size_t)env_ids[k] * row, row, hipMemcpyDeviceToHost, c->stream));
+    TG_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 

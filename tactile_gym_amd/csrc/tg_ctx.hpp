@@ -27,6 +27,7 @@
 #include "tg_raster.h"
 #include "tg_exchange.h"
 #include "tg_broadphase.h"
+#include "tg_stack.h"
 
 
 namespace tg {
@@ -271,6 +272,12 @@ struct tg_ctx {
     unsigned long long* d_kt_acc = nullptr;      // [8][2]
     size_t kt_slots = 0;
     double wall_clock_khz = 100000.0;
+    // frame stack (tg_set_frame_stack; tg_stack.hip): stack_n frames per observation key, oldest slot first; stack_n = 1: nothing allocated, no launch
+    int stack_n = 1;
+    uint8_t *d_stack = nullptr, *d_stack_term = nullptr;       // tactile [n][H][W][stack_n], current and terminal
+    uint8_t* d_stack_rec = nullptr;                            // [n][blocks]: bit s = slot s of the 16 x 16 block holds d_tile_tmpl
+    float *d_stack_vec[2] = {nullptr, nullptr}, *d_stack_vec_term[2] = {nullptr, nullptr};   // oracle, extended_feature [n][dim * stack_n]
+    int stack_vec_dim[2] = {0, 0};
 };
 
 static inline bool env_has_feature(int env_kind) {   // envs with an extended_feature observation (push 12, roll 3, surface_follow -v1 / -v2 6 of the 12-wide rows)

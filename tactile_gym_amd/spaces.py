@@ -65,3 +65,13 @@ except Exception:  # noqa: BLE001
 
             def __repr__(self):
                 return f"Dict({self.spaces})"
+
+
+def stacked(space, n):
+    """The observation space of stable_baselines3's VecFrameStack(venv, n) (StackedObservations): every Box stacked n times along its last axis,
+    low / high repeated there (np.repeat(low, n, axis=-1)); a Dict per key.  n = 1: the space itself."""
+    if n == 1:
+        return space
+    if hasattr(space, "spaces"):
+        return Dict({k: stacked(s, n) for k, s in space.spaces.items()})
+    return Box(low=np.repeat(space.low, n, axis=-1), high=np.repeat(space.high, n, axis=-1), dtype=space.dtype)

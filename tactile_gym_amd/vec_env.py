@@ -91,8 +91,14 @@ class TactileVecEnv(_VecEnvBase):
     metadata = {"render.modes": ["rgb_array"]}
 
     def __init__(self, cfg, robot, sensor_desc, mesh_desc, observation_mode="tactile", obs_mode="numpy", seed=None, act_dim=None,
-                 oracle_dim=10, feature_dim=0, copy_obs=True, scene_spec=None, guard_spec=None):
+                 oracle_dim=10, feature_dim=0, copy_obs=True, scene_spec=None, guard_spec=None, frame_stack=1):
         self._L = capi.lib()
+        # frame_stack=n: every observation is the stack of the last n frames along its last axis, exactly what stable_baselines3's
+        # VecFrameStack(venv, n) hands out (observations, reset observations, info["terminal_observation"]); kept in device memory and updated by
+        # one launch per step (tg_set_frame_stack)
+        if isinstance(frame_stack, bool) or int(frame_stack) != frame_stack or not 1 <= int(frame_stack) <= 8:
+            raise ValueError(f"frame_stack={frame_stack!r}: an integer in [1, 8]")
+        self.frame_stack = int(frame_stack)
         self.num_envs = int(cfg.num_envs)
         self._cfg, self._robot, self._sensor, self._mesh = cfg, robot, sensor_desc, mesh_desc
         self.observation_mode = observation_mode
@@ -105,6 +111,9 @@ class TactileVecEnv(_VecEnvBase):
         self._scene_spec, self._scene = scene_spec, None
         if self._visual and scene_spec is None:
             raise NotImplementedError("visual (RGB scene camera) observations are not built for this env")
+        if self._visual and self.frame_stack > 1:
+            raise NotImplementedError(f"frame_stack={self.frame_stack} with observation_mode {observation_mode!r}: the scene camera's rgb images are not "
+                                      "stacked on the device; wrap the env in VecFrameStack instead")
         self.obs_mode = obs_mode
         # copy_obs=True (default): every observation batch handed out is an array of its own, like the reference's fresh arrays
         # (base_tactile_env.py:247-282).  copy_obs=False: the device -> host copy lands in one of four rotating host buffers, valid for
@@ -130,7 +139,7 @@ class TactileVecEnv(_VecEnvBase):
         if "feature" in observation_mode:
             obs_spaces["extended_feature"] = spaces.Box(low=-np.inf, high=np.inf, shape=(feature_dim,), dtype=np.float32)
         self.feature_dim, self._oracle_dim = feature_dim, oracle_dim
-        self.observation_space = spaces.Dict(obs_spaces)
+        self.observation_space = spaces.stacked(spaces.Dict(obs_spaces), self.frame_stack)
         if _VecEnvBase is not object:     # SB3's constructor records num_envs / spaces (and render_mode in recent versions)
             try:
                 _VecEnvBase.__init__(self, self.num_envs, self.observation_space, self.action_space)
@@ -158,6 +167,8 @@ class TactileVecEnv(_VecEnvBase):
             if os.environ.get("TG_BROADPHASE_GUARD", "") == "1":
                 every = True
             self.set_broadphase_guard(bool(every))
+        if self.frame_stack > 1:
+            capi.check(self._L.tg_set_frame_stack(self._ctx, self.frame_stack))
         if seed is not None:
             self.seed(seed)
 
@@ -229,8 +240,13 @@ class TactileVecEnv(_VecEnvBase):
         self._obs_guard, self._guard_sum = bool(on), {}     # per render target (rank 0's direct mode alternates two of them)
 
     def _guard_checksum(self):
+        torch = __import__("torch")
         t = self.tactile_torch()
-        return int(t.reshape(-1).view(__import__("torch").int64).sum().item())
+        total = int(t.reshape(-1).view(torch.int64).sum().item())
+        if self.frame_stack > 1:                    # the stacks handed out alias the library's buffers as well
+            for key in self._stack_keys():
+                total += int(self._stack_torch(key).reshape(-1).view(torch.int32).to(torch.int64).sum().item())
+        return total
 
     def _guard_before_step(self):
         sel = getattr(self, "_obs_sel", 0)          # the target this step draws into: its buffer must still hold what the library last drew there
@@ -505,6 +521,9 @@ class TactileVecEnv(_VecEnvBase):
             old.close()
         if how == "full":
             self._tile_download = None
+        elif how == "tiles" and self.frame_stack > 1:
+            self._tile_download = None
+            raise ValueError(f"obs_transfer 'tiles' with frame_stack={self.frame_stack}: the tile download carries single frames; use 'full'")
         elif how == "tiles":
             from .host_tiles import TileDownload
             self._tile_download = TileDownload(self)
@@ -527,7 +546,54 @@ class TactileVecEnv(_VecEnvBase):
         capi.check(self._L.tg_copy_obs_visual(self._ctx, buf.ctypes.data_as(C.POINTER(C.c_uint8)), int(terminal)))
         return buf
 
+    # ------------------------------------------------------------------ frame stack (tg_set_frame_stack)
+    def _stack_keys(self):
+        keys = []
+        if "oracle" in self.observation_mode:
+            keys.append("oracle")
+        if "tactile" in self.observation_mode:
+            keys.append("tactile")
+        if "feature" in self.observation_mode:
+            keys.append("extended_feature")
+        return keys
+
+    def _stack_shape(self, key, rows):
+        if key == "tactile":
+            return (rows, self.H, self.W, self.frame_stack), np.uint8, "|u1"
+        dim = self._oracle_dim if key == "oracle" else self.feature_dim
+        return (rows, dim * self.frame_stack), np.float32, "<f4"
+
+    def _stack_torch(self, key, terminal=False):
+        """Zero-copy torch view of the device stack of `key` (read-only contract as tactile_torch)."""
+        vk = ("stack", key, bool(terminal))
+        if vk not in self._views:
+            import torch
+            shape, _, typestr = self._stack_shape(key, self.num_envs)
+            if shape[-1] == 0:
+                self._views[vk] = torch.zeros(shape, dtype=torch.float32, device=f"cuda:{self._cfg.device}")
+            else:
+                p = C.c_void_p()
+                capi.check(self._L.tg_get_obs_stack(self._ctx, capi.OBS_KEY[key], int(terminal), C.byref(p)))
+                self._views[vk] = torch.as_tensor(_DevArray(p.value, shape, typestr), device=f"cuda:{self._cfg.device}")
+        return self._views[vk]
+
+    def _stack_numpy(self, key, terminal=False, idx=None):
+        """Host copy of the stack of `key`: the whole batch, or (idx) the rows of those envs only (tg_copy_obs_stack_rows)."""
+        shape, dtype, _ = self._stack_shape(key, self.num_envs if idx is None else len(idx))
+        out = np.empty(shape, dtype=dtype)
+        if out.size == 0:
+            return out
+        if idx is None:
+            capi.check(self._L.tg_copy_obs_stack(self._ctx, capi.OBS_KEY[key], int(terminal), out.ctypes.data_as(C.c_void_p)))
+        else:
+            ids = np.ascontiguousarray(idx, dtype=np.int32)
+            capi.check(self._L.tg_copy_obs_stack_rows(self._ctx, capi.OBS_KEY[key], int(terminal), ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
+                                                      out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def _observation(self):
+        if self.frame_stack > 1:
+            return {k: self._stack_torch(k) if self.obs_mode == "torch" else self._stack_numpy(k) for k in self._stack_keys()}
         obs = {}
         if "oracle" in self.observation_mode:
             obs["oracle"] = self.oracle_obs()
@@ -563,7 +629,9 @@ class TactileVecEnv(_VecEnvBase):
 
     def _terminal_rows(self, idx, tactile_rows=None):
         """The terminal observation of the envs `idx` only (numpy): images by tg_copy_obs_rows (or `tactile_rows`, what the tile download brought along),
-        the small per-env vectors from their whole-batch copies."""
+        the small per-env vectors from their whole-batch copies.  With a frame stack: the finished envs' terminal stacks."""
+        if self.frame_stack > 1:
+            return {k: self._stack_numpy(k, terminal=True, idx=idx) for k in self._stack_keys()}
         obs = {}
         if "oracle" in self.observation_mode:
             obs["oracle"] = np.array(self.oracle_terminal()[idx])
@@ -576,6 +644,8 @@ class TactileVecEnv(_VecEnvBase):
         return obs
 
     def _terminal_observation(self):
+        if self.frame_stack > 1:
+            return {k: self._stack_torch(k, terminal=True) if self.obs_mode == "torch" else self._stack_numpy(k, terminal=True) for k in self._stack_keys()}
         obs = {}
         if "oracle" in self.observation_mode:
             obs["oracle"] = self.oracle_terminal()
@@ -757,6 +827,9 @@ class SingleTactileEnv(_GymEnvBase):
                  device=0, **kwargs):
         if show_gui or show_tactile:
             raise NotImplementedError("GUI / cv2 windows are not part of the headless device path")
+        if "frame_stack" in kwargs:
+            raise TypeError("frame_stack is an option of the vectorised envs (upstream, frame stacking is the VecEnv wrapper VecFrameStack): pass "
+                            "vec_env_kwargs=dict(frame_stack=n) to make_vec_env(..., vec_env_cls=HipVecEnv), or frame_stack=n to make_vec()")
         if env_modes is None:
             env_modes = self.default_env_modes
         self._vec = self.vec_cls(1, max_steps, image_size, env_modes, physics_dtype, auto_reset=False, device=device, **kwargs)
@@ -814,7 +887,7 @@ class HipVecEnv:
     info["episode"] = {"r", "l", "t"} for the envs that finished (what SB3's logger and EvalCallback read), and with `monitor_dir` the same
     rows go to `<monitor_dir>/tactile_gym_hip.monitor.csv` in SB3's Monitor format (load_results(monitor_dir), which the reference's
     sb3_helpers/rl_plot_utils.py and custom_callbacks.py call, reads every *monitor.csv of the directory).  Extra keyword arguments
-    (vec_env_kwargs: obs_mode, copy_obs, physics_dtype, device, obs_transfer ...) go to the vectorised constructor; start_method is accepted and
+    (vec_env_kwargs: obs_mode, copy_obs, physics_dtype, device, obs_transfer, frame_stack ...) go to the vectorised constructor; start_method is accepted and
     ignored.  The result is a TactileVecEnv (an SB3 VecEnv subclass wherever SB3 is importable), not an instance of this class."""
 
     def __new__(cls, env_fns, start_method=None, **kwargs):
