@@ -24,7 +24,7 @@ extern "C" {
 
 #define TG_MAX_DOF 8
 #define TG_MAX_BODIES_PER_LINK 4
-#define TG_ABI_VERSION 15
+#define TG_ABI_VERSION 16
 #define TG_MAX_TRAJ_POINTS 16
 
 /* ---- robot description: the flattened URDF (replaces loadURDF, robots/arms/robot.py:95-112) --------------------- */
@@ -583,6 +583,20 @@ int tg_get_obs_stack(tg_ctx* ctx, int32_t key, int32_t terminal, void** dev_ptr)
 int tg_copy_obs_stack(tg_ctx* ctx, int32_t key, int32_t terminal, void* host_dst);                /* synchronises */
 /* The stacks of `count` chosen envs only (the finished envs' terminal stacks): env_ids[k]'s row goes to host_dst + k * row_bytes. */
 int tg_copy_obs_stack_rows(tg_ctx* ctx, int32_t key, int32_t terminal, const int32_t* env_ids, int32_t count, void* host_dst);
+
+/* ---- observation layout: stable_baselines3's VecTransposeImage on the device (sb3_helpers/rl_utils.py:33, 66; ABI v16) ---------------------------
+ * tg_set_obs_layout(1): the image stacks are kept channels first, what VecTransposeImage(VecFrameStack(venv, n)) hands out - tactile uint8
+ * [num_envs][n][H][W], visual uint8 [num_envs][3 n][H][W] (plane 3 s + c: stack slot s, oldest first, colour c).  0 (default): channels last,
+ * tactile [num_envs][H][W][n], visual [num_envs][H][W][3 n].  The vector keys are the same in both layouts.
+ * The visual key (TG_OBS_KEY_VISUAL) is stacked when the scene is drawn every step (tg_set_scene with every_step, the visual observation modes) and
+ * n > 1 or channels first; tg_set_scene must come first, and is refused afterwards.  With n = 1 and channels first the tactile "stack" is the
+ * observation buffer itself ([num_envs][H][W] is [num_envs][1][H][W]; tg_get_obs_stack returns it), and only a visual key costs a launch.
+ * tg_set_frame_stack and tg_set_obs_layout may come in either order: each (re)allocates every stack for the current (n, layout), zeroed; call them
+ * before the first tg_reset.  Both updates keep tg_set_frame_stack's rules and call sites: one update per tg_reset and per step, after the step's
+ * tactile and scene renders.  Channels first is refused together with tg_set_obs_targets (sharded runs). */
+#define TG_OBS_KEY_VISUAL 3
+int tg_set_obs_layout(tg_ctx* ctx, int32_t channels_first);
+int tg_get_obs_layout(tg_ctx* ctx, int32_t* channels_first);
 #ifdef __cplusplus
 }
 #endif

@@ -692,7 +692,7 @@ static bool stack_rewrite_all() {
     return on;
 }
 static int stack_update(tg_ctx* c, int mode, const uint8_t* flag) {
-    if (c->stack_n <= 1) return 0;
+    if (c->stack_n <= 1 && !c->d_vstack) return 0;
     StackArgs a;
     a.num_envs = c->cfg.num_envs; a.H = c->H; a.W = c->W; a.n = c->stack_n; a.mode = mode; a.rewrite_all = stack_rewrite_all() ? 1 : 0;
     a.flag = flag;
@@ -709,7 +709,17 @@ static int stack_update(tg_ctx* c, int mode, const uint8_t* flag) {
         v.stack = c->d_stack_vec[k];
         v.term_stack = term ? c->d_stack_vec_term[k] : nullptr;
     }
-    if (launch_frame_stack(a, c->stream) != 0) return fail(-2, "frame stack launch failed");
+    if (!c->d_vstack && !c->obs_cf) {
+        if (launch_frame_stack(a, c->stream) != 0) return fail(-2, "frame stack launch failed");
+        return 0;
+    }
+    if (c->stack_n <= 1) a.frame = nullptr;     // channels first, n = 1: the tactile buffer is its own stack
+    VisStack v;
+    if (c->d_vstack) {
+        v.frame = c->d_vis; v.term_frame = c->d_vis_term; v.stack = c->d_vstack; v.term_stack = term ? c->d_vstack_term : nullptr;
+        v.H = c->scene.H; v.W = c->scene.W;
+    }
+    if (launch_obs_stack(a, v, c->obs_cf, c->stream) != 0) return fail(-2, "observation stack launch failed");
     return 0;
 }
 
@@ -1130,7 +1140,7 @@ int tg_destroy(tg_ctx* c) {
                     c->d_obs, c->d_term, c->d_mask, c->d_actions, c->d_scene_verts, c->d_scene_xf, c->d_scene_spheres, c->d_scene_tris, c->d_scene_attr, c->d_scene_local, c->d_scene_static, c->d_scene_chunks, c->d_vis, c->d_vis_term, c->d_oracle, c->d_oracle_term, c->d_int_idx, c->d_int_rank, c->d_tile_tmpl, c->d_episode, c->d_block_tables};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (void* p : {(void*)c->d_stack, (void*)c->d_stack_term, (void*)c->d_stack_rec, (void*)c->d_stack_vec[0], (void*)c->d_stack_vec[1],
-                    (void*)c->d_stack_vec_term[0], (void*)c->d_stack_vec_term[1]}) if (p) (void)hipFree(p);
+                    (void*)c->d_stack_vec_term[0], (void*)c->d_stack_vec_term[1], (void*)c->d_vstack, (void*)c->d_vstack_term}) if (p) (void)hipFree(p);
     if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
     if (c->bank_stream) { (void)hipStreamSynchronize(c->bank_stream); (void)hipStreamDestroy(c->bank_stream); }
     if (c->ev_bank) (void)hipEventDestroy(c->ev_bank);
@@ -1349,6 +1359,7 @@ int tg_set_obs_targets(tg_ctx* c, int32_t count, void* const* dev_ptrs) {
     if (!c || count < 0 || count > 2 || (count > 0 && !dev_ptrs)) return fail(-1, "tg_set_obs_targets: bad argument");
     for (int k = 0; k < count; ++k) if (!dev_ptrs[k]) return fail(-1, "tg_set_obs_targets: NULL target");   // (every argument is checked before anything is changed)
     if (count > 0 && c->stack_n > 1) return fail(-1, "tg_set_obs_targets: a context with a frame stack (tg_set_frame_stack n > 1) draws into its own buffer only");
+    if (count > 0 && c->obs_cf) return fail(-1, "tg_set_obs_targets: a context with channels-first observations (tg_set_obs_layout 1) draws into its own buffer only");
     TG_ENTER(c);
     TG_HIP(hipStreamSynchronize(c->stream));
     c->obs_sel = 0;
@@ -1541,6 +1552,8 @@ static int set_scene_impl(tg_ctx* c, const tg_scene* sc) {
 
 
 int tg_set_scene(tg_ctx* c, const tg_scene* sc) {
+    if (c && sc && (c->d_vstack || (sc->every_step && (c->stack_n > 1 || c->obs_cf))))
+        return fail(-1, "tg_set_scene: a scene drawn every step is set before tg_set_frame_stack / tg_set_obs_layout, and not replaced after");
     const int rc = set_scene_impl(c, sc);
     if (rc != 0 && c && !c->scene_on) {     // a failed set-up leaves nothing behind: a retry starts from null pointers, nothing leaks
         const std::string keep = tg_last_error();
@@ -1696,33 +1709,58 @@ int tg_copy_obs_rows(tg_ctx* c, int32_t visual, int32_t terminal, const int32_t*
 // ---- frame stack (VecFrameStack on the device; tg_stack.hip) ----
 static void free_stack(tg_ctx* c) {
     for (void** p : {(void**)&c->d_stack, (void**)&c->d_stack_term, (void**)&c->d_stack_rec, (void**)&c->d_stack_vec[0], (void**)&c->d_stack_vec[1],
-                     (void**)&c->d_stack_vec_term[0], (void**)&c->d_stack_vec_term[1]})
+                     (void**)&c->d_stack_vec_term[0], (void**)&c->d_stack_vec_term[1], (void**)&c->d_vstack, (void**)&c->d_vstack_term})
         if (*p) { (void)hipFree(*p); *p = nullptr; }
     c->stack_vec_dim[0] = c->stack_vec_dim[1] = 0;
     c->stack_n = 1;
+}
+// (Re)allocates every stack for n frames in layout cf, all zero.
+static int alloc_stacks(tg_ctx* c, int n, int cf) {
+    if (c->scene_every_step && (n > 1 || cf) && c->scene.W % 16) return fail(-1, "stacked scene images need a width that is a multiple of 16");
+    TG_HIP(hipStreamSynchronize(c->stream));
+    free_stack(c);
+    c->obs_cf = cf;
+    const size_t envs = (size_t)c->cfg.num_envs;
+    if (n > 1) {
+        const size_t img = envs * c->H * c->W * n, rec = envs * (c->H / 16) * (c->W / 16);   // (the same bytes in either layout)
+        TG_HIP(hipMalloc(&c->d_stack, img)); TG_HIP(hipMalloc(&c->d_stack_term, img)); TG_HIP(hipMalloc(&c->d_stack_rec, rec));
+        TG_HIP(hipMemset(c->d_stack, 0, img)); TG_HIP(hipMemset(c->d_stack_term, 0, img));
+        TG_HIP(hipMemset(c->d_stack_rec, 0, rec));   // no slot holds the template: the first update writes every block
+        c->stack_vec_dim[0] = c->oracle_every_step ? oracle_dim(c) : 0;
+        c->stack_vec_dim[1] = env_has_feature(c->cfg.env_kind) ? feature_dim(c) : 0;
+        for (int k = 0; k < 2; ++k) {
+            if (!c->stack_vec_dim[k]) continue;
+            const size_t b = envs * c->stack_vec_dim[k] * n * sizeof(float);
+            TG_HIP(hipMalloc(&c->d_stack_vec[k], b)); TG_HIP(hipMalloc(&c->d_stack_vec_term[k], b));
+            TG_HIP(hipMemset(c->d_stack_vec[k], 0, b)); TG_HIP(hipMemset(c->d_stack_vec_term[k], 0, b));
+        }
+        c->stack_n = n;
+    }
+    if (c->scene_every_step && (n > 1 || cf)) {      // the visual observation modes
+        const size_t b = envs * c->scene.H * c->scene.W * 3 * n;
+        TG_HIP(hipMalloc(&c->d_vstack, b)); TG_HIP(hipMalloc(&c->d_vstack_term, b));
+        TG_HIP(hipMemset(c->d_vstack, 0, b)); TG_HIP(hipMemset(c->d_vstack_term, 0, b));
+    }
+    TG_HIP(hipDeviceSynchronize());
+    return 0;
 }
 int tg_set_frame_stack(tg_ctx* c, int32_t n) {
     if (!c) return fail(-1, "NULL ctx");
     if (n < 1 || n > kStackMax) return fail(-1, "tg_set_frame_stack: n must be in [1, 8]");
     if (n > 1 && (c->obs_ext[0] || c->obs_ext[1])) return fail(-1, "tg_set_frame_stack: not with render targets of the caller (tg_set_obs_targets: sharded runs)");
     TG_ENTER(c);
-    TG_HIP(hipStreamSynchronize(c->stream));
-    free_stack(c);
-    if (n == 1) return 0;
-    const size_t envs = (size_t)c->cfg.num_envs, img = envs * c->H * c->W * n, rec = envs * (c->H / 16) * (c->W / 16);
-    TG_HIP(hipMalloc(&c->d_stack, img)); TG_HIP(hipMalloc(&c->d_stack_term, img)); TG_HIP(hipMalloc(&c->d_stack_rec, rec));
-    TG_HIP(hipMemset(c->d_stack, 0, img)); TG_HIP(hipMemset(c->d_stack_term, 0, img));
-    TG_HIP(hipMemset(c->d_stack_rec, 0, rec));   // no slot holds the template: the first update writes every block
-    c->stack_vec_dim[0] = c->oracle_every_step ? oracle_dim(c) : 0;
-    c->stack_vec_dim[1] = env_has_feature(c->cfg.env_kind) ? feature_dim(c) : 0;
-    for (int k = 0; k < 2; ++k) {
-        if (!c->stack_vec_dim[k]) continue;
-        const size_t b = envs * c->stack_vec_dim[k] * n * sizeof(float);
-        TG_HIP(hipMalloc(&c->d_stack_vec[k], b)); TG_HIP(hipMalloc(&c->d_stack_vec_term[k], b));
-        TG_HIP(hipMemset(c->d_stack_vec[k], 0, b)); TG_HIP(hipMemset(c->d_stack_vec_term[k], 0, b));
-    }
-    c->stack_n = n;
-    TG_HIP(hipDeviceSynchronize());
+    return alloc_stacks(c, n, c->obs_cf);
+}
+int tg_set_obs_layout(tg_ctx* c, int32_t channels_first) {
+    if (!c) return fail(-1, "NULL ctx");
+    if (channels_first != 0 && channels_first != 1) return fail(-1, "tg_set_obs_layout: channels_first must be 0 or 1");
+    if (channels_first && (c->obs_ext[0] || c->obs_ext[1])) return fail(-1, "tg_set_obs_layout: not with render targets of the caller (tg_set_obs_targets: sharded runs)");
+    TG_ENTER(c);
+    return alloc_stacks(c, c->stack_n, channels_first);
+}
+int tg_get_obs_layout(tg_ctx* c, int32_t* channels_first) {
+    if (!c || !channels_first) return fail(-1, "NULL argument");
+    *channels_first = c->obs_cf;
     return 0;
 }
 int tg_get_frame_stack(tg_ctx* c, int32_t* n) {
@@ -1732,6 +1770,17 @@ int tg_get_frame_stack(tg_ctx* c, int32_t* n) {
 }
 // key TG_OBS_KEY_*: (device pointer, bytes per env row) of the current or terminal stack
 static int stack_buffer(tg_ctx* c, int32_t key, int32_t terminal, void** p, size_t* row) {
+    if (key == TG_OBS_KEY_VISUAL) {
+        if (!c->d_vstack) return fail(-1, "no visual stack (a scene drawn every step, with tg_set_frame_stack n > 1 or tg_set_obs_layout 1)");
+        *p = terminal ? c->d_vstack_term : c->d_vstack;
+        *row = (size_t)c->scene.H * c->scene.W * 3 * c->stack_n;
+        return 0;
+    }
+    if (key == TG_OBS_KEY_TACTILE && c->stack_n <= 1 && c->obs_cf) {   // [n][H][W] is [n][1][H][W]: the observation buffers themselves
+        *p = terminal ? c->d_term : c->d_obs;
+        *row = (size_t)c->H * c->W;
+        return 0;
+    }
     if (c->stack_n <= 1) return fail(-1, "no frame stack (tg_set_frame_stack n > 1)");
     if (key == TG_OBS_KEY_TACTILE) {
         *p = terminal ? c->d_stack_term : c->d_stack;

@@ -278,6 +278,11 @@ struct tg_ctx {
     uint8_t* d_stack_rec = nullptr;                            // [n][blocks]: bit s = slot s of the 16 x 16 block holds d_tile_tmpl
     float *d_stack_vec[2] = {nullptr, nullptr}, *d_stack_vec_term[2] = {nullptr, nullptr};   // oracle, extended_feature [n][dim * stack_n]
     int stack_vec_dim[2] = {0, 0};
+    // observation layout (tg_set_obs_layout): obs_cf = 1 keeps the image stacks channels first, tactile [n][stack_n][H][W] in d_stack; the scene
+    // camera's images are stacked when the scene is drawn every step and stack_n > 1 or obs_cf (channels last [n][H][W][3 stack_n], channels first
+    // [n][3 stack_n][H][W]); none: null
+    int obs_cf = 0;
+    uint8_t *d_vstack = nullptr, *d_vstack_term = nullptr;
 };
 
 static inline bool env_has_feature(int env_kind) {   // envs with an extended_feature observation (push 12, roll 3, surface_follow -v1 / -v2 6 of the 12-wide rows)

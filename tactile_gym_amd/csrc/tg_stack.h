@@ -1,4 +1,5 @@
-// tg_stack.h - launch interface of the device frame stack (tg_stack.hip: k_frame_stack; tg_set_frame_stack).
+// tg_stack.h - launch interface of the device frame stack and observation layout (tg_stack.hip: k_frame_stack, k_obs_stack; tg_set_frame_stack,
+// tg_set_obs_layout).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,5 +36,20 @@ struct StackArgs {
     StackVec vec[2];                  // oracle, extended_feature (dim 0: absent)
 };
 int launch_frame_stack(const StackArgs& a, hipStream_t stream);   // 0, or -1 for arguments the kernel is not built for
+
+// The scene camera's images (tg_set_scene every step): uint8 [num_envs][H][W][3] frames, stacked to [num_envs][H][W][3 n] (channels last; slot s at
+// bytes 3 s .. 3 s + 2 of a pixel) or [num_envs][3 n][H][W] (channels first; slot s colour c is plane 3 s + c).  Same update rules as StackArgs.
+struct VisStack {
+    const uint8_t* frame = nullptr;   // d_vis; null: no visual stack
+    const uint8_t* term_frame = nullptr;
+    uint8_t* stack = nullptr;
+    uint8_t* term_stack = nullptr;    // null: no terminal stack
+    int H = 0, W = 0;
+};
+// The stacks with a visual key or channels first (tg_set_obs_layout).  channels_first: ONE launch of k_obs_stack for the tactile image
+// ([num_envs][n][H][W], n >= 2; a.frame null: none), the vectors and the visual image.  n = 1 stacks the visual image only (its planar copy): the
+// tactile image [num_envs][H][W] is already [num_envs][1][H][W].  Channels last: k_frame_stack (a.n >= 2, unchanged), then k_obs_stack for the
+// visual image.  0, or -1 for arguments the kernels are not built for.
+int launch_obs_stack(const StackArgs& a, const VisStack& v, int channels_first, hipStream_t stream);
 
 }  // namespace tg

@@ -103,7 +103,7 @@ def build_config(num_envs, max_steps, image_size, env_modes, physics_dtype="f64"
 
 class EdgeFollowVecEnv(TactileVecEnv):
     def __init__(self, num_envs, max_steps=250, image_size=(64, 64), env_modes=env_modes_default, physics_dtype="f64",
-                 auto_reset=True, device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", fused_step="auto", frame_stack=1):
+                 auto_reset=True, device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", fused_step="auto", frame_stack=1, channels_first=False):
         cfg, robot, sensor, mesh, modes = build_config(num_envs, max_steps, image_size, env_modes, physics_dtype, auto_reset, device)
         cfg.pgs_full_sweeps = int(bool(pgs_full_sweeps))   # run all solver sweeps instead of leaving at convergence
         cfg.solver_residual_threshold = float(solver_residual_threshold)   # btContactSolverInfo::m_leastSquaresResidualThreshold (PARITY A7b): 0 = exit at convergence only, 1e-7 = what PyBullet is believed to run
@@ -112,7 +112,7 @@ class EdgeFollowVecEnv(TactileVecEnv):
         cfg.fused_step = capi.FUSED_STEP[fused_step]   # "on": the step as one launch (csrc/tg_fused.hip; measured slower); default: k_step -> k_reset -> render
         self.env_modes = modes
         self.min_action, self.max_action = cfg.min_action, cfg.max_action
-        super().__init__(cfg, robot, sensor, mesh, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack,
+        super().__init__(cfg, robot, sensor, mesh, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack, channels_first=channels_first,
                          guard_spec={"arm_type": modes["arm_type"], "t_s_core": "no_core",       # edge_follow_env.py:64; the edge: :218-235
                                      "edge": "short_edge" if modes["arm_type"] == "mg400" else "long_edge"},
                          scene_spec={"arm_type": modes["arm_type"], "camera":                     # setup_rgb_obs_camera_params, edge_follow_env.py:176-195

@@ -101,7 +101,7 @@ def build_config(num_envs, max_steps, image_size, env_modes, physics_dtype="f64"
 
 class ObjectRollVecEnv(TactileVecEnv):
     def __init__(self, num_envs, max_steps=1000, image_size=(64, 64), env_modes=env_modes_default, physics_dtype="f64", auto_reset=True,
-                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", solver_iterations=None, frame_stack=1):
+                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", solver_iterations=None, frame_stack=1, channels_first=False):
         cfg, robot, sensor, mesh, modes = build_config(num_envs, max_steps, image_size, env_modes, physics_dtype, auto_reset, device)
         if solver_iterations is not None:
             cfg.solver_iterations = int(solver_iterations)   # numSolverIterations (base_tactile_env.py:128-130: 150); measurements only
@@ -110,7 +110,7 @@ class ObjectRollVecEnv(TactileVecEnv):
         cfg.solver_residual_threshold = float(solver_residual_threshold)   # btContactSolverInfo::m_leastSquaresResidualThreshold (PARITY A7b): 0 = exit at convergence only, 1e-7 = what PyBullet is believed to run
         self.env_modes = modes
         self.min_action, self.max_action = cfg.min_action, cfg.max_action
-        super().__init__(cfg, robot, sensor, mesh, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack,
+        super().__init__(cfg, robot, sensor, mesh, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack, channels_first=channels_first,
                          act_dim=2, oracle_dim=34, feature_dim=3,
                          guard_spec={"arm_type": modes["arm_type"], "t_s_core": "fixed", "obj": "sphere", "every_step": True},   # object_roll_env.py:56
                          scene_spec={"arm_type": modes["arm_type"], "camera": ([0.75, 0.0, 0.00775], 0.01, 90.0, 0.0, 75.0, 0.01, 100.0)})   # :145-154                                # get_extended_feature_array :409-415

@@ -110,7 +110,7 @@ def build_config(num_envs, max_steps, image_size, env_modes, physics_dtype="f64"
 
 class SurfaceFollowAutoVecEnv(TactileVecEnv):
     def __init__(self, num_envs, max_steps=200, image_size=(64, 64), env_modes=env_modes_default, physics_dtype="f64", auto_reset=True,
-                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1):
+                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False):
         cfg, robot, sensor, modes = build_config(num_envs, max_steps, image_size, env_modes, physics_dtype, auto_reset, device)
         cfg.pgs_full_sweeps = int(bool(pgs_full_sweeps))   # run all solver sweeps instead of leaving at convergence
         cfg.solver_residual_threshold = float(solver_residual_threshold)   # btContactSolverInfo::m_leastSquaresResidualThreshold (PARITY A7b): 0 = exit at convergence only, 1e-7 = what PyBullet is believed to run
@@ -119,7 +119,7 @@ class SurfaceFollowAutoVecEnv(TactileVecEnv):
         self.env_modes = modes
         self.min_action, self.max_action = cfg.min_action, cfg.max_action
         act_dim = {"yz": 1, "xyz": 1, "yzRx": 2, "xyzRxRy": 3}[modes["movement_mode"]]          # surface_follow_auto_env.py:96-107
-        super().__init__(cfg, robot, sensor, None, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack,
+        super().__init__(cfg, robot, sensor, None, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack, channels_first=channels_first,
                          act_dim=act_dim, oracle_dim=20,
                          guard_spec={"arm_type": modes["arm_type"], "t_s_core": "fixed"},   # base_surface_env.py:65; the heightfield's collisions are off (:432)
                          scene_spec={"arm_type": modes["arm_type"], "body_rgb": (0, 0, 255), "camera":    # base_surface_env.py:208-232, :431
@@ -151,7 +151,7 @@ class SurfaceFollowGoalVecEnv(SurfaceFollowAutoVecEnv):
     """surface_follow-v1: the agent drives every dimension; `tactile_and_feature` adds [tcp_pos, goal_pos] in the work frame."""
 
     def __init__(self, num_envs, max_steps=200, image_size=(64, 64), env_modes=env_modes_default, physics_dtype="f64", auto_reset=True,
-                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1):
+                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False):
         cfg, robot, sensor, modes = build_config(num_envs, max_steps, image_size, env_modes, physics_dtype, auto_reset, device,
                                                  goal_variant=True)
         cfg.pgs_full_sweeps = int(bool(pgs_full_sweeps))
@@ -161,7 +161,7 @@ class SurfaceFollowGoalVecEnv(SurfaceFollowAutoVecEnv):
         self.env_modes = modes
         self.min_action, self.max_action = cfg.min_action, cfg.max_action
         act_dim = {"yz": 2, "xyz": 3, "yzRx": 3, "xyzRxRy": 5}[modes["movement_mode"]]          # surface_follow_goal_env.py:112-123
-        TactileVecEnv.__init__(self, cfg, robot, sensor, None, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack,
+        TactileVecEnv.__init__(self, cfg, robot, sensor, None, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack, channels_first=channels_first,
                                act_dim=act_dim, oracle_dim=20, feature_dim=6,
                                guard_spec={"arm_type": modes["arm_type"], "t_s_core": "fixed"},   # base_surface_env.py:65; the heightfield's collisions are off (:432)
                                scene_spec={"arm_type": modes["arm_type"], "body_rgb": (0, 0, 255), "camera":    # base_surface_env.py:208-232, :431
@@ -200,7 +200,7 @@ class SurfaceFollowVertVecEnv(SurfaceFollowGoalVecEnv):
     [tcp_pos, goal_pos] in the work frame (surface_follow_vert_env.py:83-100)."""
 
     def __init__(self, num_envs, max_steps=200, image_size=(64, 64), env_modes=env_modes_default_vert, physics_dtype="f64", auto_reset=True,
-                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1):
+                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False):
         cfg, robot, sensor, modes = build_config(num_envs, max_steps, image_size, env_modes, physics_dtype, auto_reset, device)
         cfg.pgs_full_sweeps = int(bool(pgs_full_sweeps))
         cfg.solver_residual_threshold = float(solver_residual_threshold)   # btContactSolverInfo::m_leastSquaresResidualThreshold (PARITY A7b): 0 = exit at convergence only, 1e-7 = what PyBullet is believed to run
@@ -208,7 +208,7 @@ class SurfaceFollowVertVecEnv(SurfaceFollowGoalVecEnv):
         cfg.reset_bank = capi.RESET_BANK[reset_bank]   # "off": every reset on the spot; "sync": the refill is waited for (tests); DESIGN 4.1h
         self.env_modes = modes
         self.min_action, self.max_action = cfg.min_action, cfg.max_action
-        TactileVecEnv.__init__(self, cfg, robot, sensor, None, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack,
+        TactileVecEnv.__init__(self, cfg, robot, sensor, None, observation_mode=modes["observation_mode"], obs_mode=obs_mode, seed=seed, copy_obs=copy_obs, frame_stack=frame_stack, channels_first=channels_first,
                                act_dim=2, oracle_dim=20, feature_dim=6,                          # get_act_dim :102-113
                                guard_spec={"arm_type": modes["arm_type"], "t_s_core": "fixed"},   # base_surface_env.py:65; the heightfield's collisions are off (:432)
                                scene_spec={"arm_type": modes["arm_type"], "body_rgb": (0, 0, 255), "camera":    # base_surface_env.py:208-232, :431

@@ -75,3 +75,20 @@ def stacked(space, n):
     if hasattr(space, "spaces"):
         return Dict({k: stacked(s, n) for k, s in space.spaces.items()})
     return Box(low=np.repeat(space.low, n, axis=-1), high=np.repeat(space.high, n, axis=-1), dtype=space.dtype)
+
+
+def _is_image(space):
+    """stable_baselines3's is_image_space(space) (check_channels=False): a uint8 Box of three axes with bounds 0 and 255."""
+    return (not hasattr(space, "spaces") and len(space.shape) == 3 and np.dtype(space.dtype) == np.uint8
+            and bool(np.all(space.low == 0)) and bool(np.all(space.high == 255)))
+
+
+def transposed(space):
+    """The observation space of stable_baselines3's VecTransposeImage(venv): every image Box (H, W, C) becomes Box(0, 255, (C, H, W), uint8), as
+    VecTransposeImage.transpose_space builds it; other Boxes are unchanged; a Dict per key."""
+    if hasattr(space, "spaces"):
+        return Dict({k: transposed(s) for k, s in space.spaces.items()})
+    if not _is_image(space):
+        return space
+    h, w, c = space.shape
+    return Box(low=0, high=255, shape=(c, h, w), dtype=space.dtype)

@@ -91,7 +91,7 @@ class TactileVecEnv(_VecEnvBase):
     metadata = {"render.modes": ["rgb_array"]}
 
     def __init__(self, cfg, robot, sensor_desc, mesh_desc, observation_mode="tactile", obs_mode="numpy", seed=None, act_dim=None,
-                 oracle_dim=10, feature_dim=0, copy_obs=True, scene_spec=None, guard_spec=None, frame_stack=1):
+                 oracle_dim=10, feature_dim=0, copy_obs=True, scene_spec=None, guard_spec=None, frame_stack=1, channels_first=False):
         self._L = capi.lib()
         # frame_stack=n: every observation is the stack of the last n frames along its last axis, exactly what stable_baselines3's
         # VecFrameStack(venv, n) hands out (observations, reset observations, info["terminal_observation"]); kept in device memory and updated by
@@ -99,6 +99,11 @@ class TactileVecEnv(_VecEnvBase):
         if isinstance(frame_stack, bool) or int(frame_stack) != frame_stack or not 1 <= int(frame_stack) <= 8:
             raise ValueError(f"frame_stack={frame_stack!r}: an integer in [1, 8]")
         self.frame_stack = int(frame_stack)
+        # channels_first=True: the image keys are handed out as stable_baselines3's VecTransposeImage makes them, [N, C * n, H, W] (stack slot s,
+        # oldest first, then colour: visual channel 3 s + rgb), C-contiguous; the vector keys are unchanged (tg_set_obs_layout)
+        if not isinstance(channels_first, (bool, np.bool_)):
+            raise ValueError(f"channels_first={channels_first!r}: True or False")
+        self.channels_first = bool(channels_first)
         self.num_envs = int(cfg.num_envs)
         self._cfg, self._robot, self._sensor, self._mesh = cfg, robot, sensor_desc, mesh_desc
         self.observation_mode = observation_mode
@@ -111,9 +116,11 @@ class TactileVecEnv(_VecEnvBase):
         self._scene_spec, self._scene = scene_spec, None
         if self._visual and scene_spec is None:
             raise NotImplementedError("visual (RGB scene camera) observations are not built for this env")
-        if self._visual and self.frame_stack > 1:
-            raise NotImplementedError(f"frame_stack={self.frame_stack} with observation_mode {observation_mode!r}: the scene camera's rgb images are not "
-                                      "stacked on the device; wrap the env in VecFrameStack instead")
+        # the scene is drawn on the device every step (and stacked there with frame_stack > 1 or channels_first) from the spec's arm and camera:
+        # a spec without them has no image to hand out or stack
+        if self._visual and not {"arm_type", "camera"} <= set(scene_spec):
+            raise NotImplementedError(f"observation_mode {observation_mode!r} (frame_stack={self.frame_stack}, channels_first={self.channels_first}): "
+                                      f"this env's scene spec has no scene camera (needs 'arm_type' and 'camera', has {sorted(scene_spec)})")
         self.obs_mode = obs_mode
         # copy_obs=True (default): every observation batch handed out is an array of its own, like the reference's fresh arrays
         # (base_tactile_env.py:247-282).  copy_obs=False: the device -> host copy lands in one of four rotating host buffers, valid for
@@ -140,6 +147,8 @@ class TactileVecEnv(_VecEnvBase):
             obs_spaces["extended_feature"] = spaces.Box(low=-np.inf, high=np.inf, shape=(feature_dim,), dtype=np.float32)
         self.feature_dim, self._oracle_dim = feature_dim, oracle_dim
         self.observation_space = spaces.stacked(spaces.Dict(obs_spaces), self.frame_stack)
+        if self.channels_first:
+            self.observation_space = spaces.transposed(self.observation_space)
         if _VecEnvBase is not object:     # SB3's constructor records num_envs / spaces (and render_mode in recent versions)
             try:
                 _VecEnvBase.__init__(self, self.num_envs, self.observation_space, self.action_space)
@@ -167,6 +176,8 @@ class TactileVecEnv(_VecEnvBase):
             if os.environ.get("TG_BROADPHASE_GUARD", "") == "1":
                 every = True
             self.set_broadphase_guard(bool(every))
+        if self.channels_first:
+            capi.check(self._L.tg_set_obs_layout(self._ctx, 1))
         if self.frame_stack > 1:
             capi.check(self._L.tg_set_frame_stack(self._ctx, self.frame_stack))
         if seed is not None:
@@ -243,8 +254,8 @@ class TactileVecEnv(_VecEnvBase):
         torch = __import__("torch")
         t = self.tactile_torch()
         total = int(t.reshape(-1).view(torch.int64).sum().item())
-        if self.frame_stack > 1:                    # the stacks handed out alias the library's buffers as well
-            for key in self._stack_keys():
+        if self._layout_on():                       # the stacks handed out alias the library's buffers as well
+            for key in filter(self._device_stacked, self._stack_keys()):
                 total += int(self._stack_torch(key).reshape(-1).view(torch.int32).to(torch.int64).sum().item())
         return total
 
@@ -524,6 +535,9 @@ class TactileVecEnv(_VecEnvBase):
         elif how == "tiles" and self.frame_stack > 1:
             self._tile_download = None
             raise ValueError(f"obs_transfer 'tiles' with frame_stack={self.frame_stack}: the tile download carries single frames; use 'full'")
+        elif how == "tiles" and self.channels_first and self._visual:
+            self._tile_download = None
+            raise ValueError("obs_transfer 'tiles' with channels_first and a visual key: the tile download carries the tactile image only; use 'full'")
         elif how == "tiles":
             from .host_tiles import TileDownload
             self._tile_download = TileDownload(self)
@@ -547,19 +561,30 @@ class TactileVecEnv(_VecEnvBase):
         return buf
 
     # ------------------------------------------------------------------ frame stack (tg_set_frame_stack)
+    def _layout_on(self):
+        return self.frame_stack > 1 or self.channels_first
+
+    def _device_stacked(self, key):
+        """Whether `key` is handed out from a device stack (tg_get_obs_stack).  channels_first with n = 1: the visual key only; the tactile
+        image [N, H, W, 1] is the observation buffer itself seen as [N, 1, H, W], the vectors are the plain observations."""
+        return self.frame_stack > 1 or (key == "visual" and self.channels_first)
+
     def _stack_keys(self):
         keys = []
         if "oracle" in self.observation_mode:
             keys.append("oracle")
         if "tactile" in self.observation_mode:
             keys.append("tactile")
+        if self._visual:
+            keys.append("visual")
         if "feature" in self.observation_mode:
             keys.append("extended_feature")
         return keys
 
     def _stack_shape(self, key, rows):
-        if key == "tactile":
-            return (rows, self.H, self.W, self.frame_stack), np.uint8, "|u1"
+        if key in ("tactile", "visual"):
+            c = (3 if key == "visual" else 1) * self.frame_stack
+            return ((rows, c, self.H, self.W) if self.channels_first else (rows, self.H, self.W, c)), np.uint8, "|u1"
         dim = self._oracle_dim if key == "oracle" else self.feature_dim
         return (rows, dim * self.frame_stack), np.float32, "<f4"
 
@@ -573,7 +598,7 @@ class TactileVecEnv(_VecEnvBase):
                 self._views[vk] = torch.zeros(shape, dtype=torch.float32, device=f"cuda:{self._cfg.device}")
             else:
                 p = C.c_void_p()
-                capi.check(self._L.tg_get_obs_stack(self._ctx, capi.OBS_KEY[key], int(terminal), C.byref(p)))
+                capi.check(self._L.tg_get_obs_stack(self._ctx, capi.OBS_STACK_KEY[key], int(terminal), C.byref(p)))
                 self._views[vk] = torch.as_tensor(_DevArray(p.value, shape, typestr), device=f"cuda:{self._cfg.device}")
         return self._views[vk]
 
@@ -584,16 +609,32 @@ class TactileVecEnv(_VecEnvBase):
         if out.size == 0:
             return out
         if idx is None:
-            capi.check(self._L.tg_copy_obs_stack(self._ctx, capi.OBS_KEY[key], int(terminal), out.ctypes.data_as(C.c_void_p)))
+            capi.check(self._L.tg_copy_obs_stack(self._ctx, capi.OBS_STACK_KEY[key], int(terminal), out.ctypes.data_as(C.c_void_p)))
         else:
             ids = np.ascontiguousarray(idx, dtype=np.int32)
-            capi.check(self._L.tg_copy_obs_stack_rows(self._ctx, capi.OBS_KEY[key], int(terminal), ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
+            capi.check(self._L.tg_copy_obs_stack_rows(self._ctx, capi.OBS_STACK_KEY[key], int(terminal), ids.ctypes.data_as(C.POINTER(C.c_int32)), len(ids),
                                                       out.ctypes.data_as(C.c_void_p)))
         return out
 
+    def _layout_obs(self, key, terminal=False):
+        """One key of the observation (or terminal observation) batch with a frame stack or channels first."""
+        torch_mode = self.obs_mode == "torch"
+        if self._device_stacked(key):
+            return self._stack_torch(key, terminal) if torch_mode else self._stack_numpy(key, terminal)
+        if key == "tactile":                        # channels first, n = 1: [N, H, W, 1] and [N, 1, H, W] are the same bytes
+            if torch_mode:
+                vk = ("cf1", bool(terminal))
+                if vk not in self._views:
+                    self._views[vk] = self.tactile_torch(terminal).view(self.num_envs, 1, self.H, self.W)
+                return self._views[vk]
+            return self.tactile_numpy(terminal).reshape(self.num_envs, 1, self.H, self.W)
+        if key == "oracle":
+            return self.oracle_terminal() if terminal else self.oracle_obs()
+        return self.feature_torch(terminal) if torch_mode else self.feature_numpy(terminal)
+
     def _observation(self):
-        if self.frame_stack > 1:
-            return {k: self._stack_torch(k) if self.obs_mode == "torch" else self._stack_numpy(k) for k in self._stack_keys()}
+        if self._layout_on():
+            return {k: self._layout_obs(k) for k in self._stack_keys()}
         obs = {}
         if "oracle" in self.observation_mode:
             obs["oracle"] = self.oracle_obs()
@@ -630,8 +671,19 @@ class TactileVecEnv(_VecEnvBase):
     def _terminal_rows(self, idx, tactile_rows=None):
         """The terminal observation of the envs `idx` only (numpy): images by tg_copy_obs_rows (or `tactile_rows`, what the tile download brought along),
         the small per-env vectors from their whole-batch copies.  With a frame stack: the finished envs' terminal stacks."""
-        if self.frame_stack > 1:
-            return {k: self._stack_numpy(k, terminal=True, idx=idx) for k in self._stack_keys()}
+        if self._layout_on():
+            obs = {}
+            for k in self._stack_keys():
+                if self._device_stacked(k):
+                    obs[k] = self._stack_numpy(k, terminal=True, idx=idx)
+                elif k == "tactile":
+                    rows = tactile_rows if tactile_rows is not None else self._image_rows(idx, False)
+                    obs[k] = np.ascontiguousarray(rows).reshape(len(idx), 1, self.H, self.W)
+                elif k == "oracle":
+                    obs[k] = np.array(self.oracle_terminal()[idx])
+                else:
+                    obs[k] = np.array(self.feature_numpy(True)[idx])
+            return obs
         obs = {}
         if "oracle" in self.observation_mode:
             obs["oracle"] = np.array(self.oracle_terminal()[idx])
@@ -644,8 +696,8 @@ class TactileVecEnv(_VecEnvBase):
         return obs
 
     def _terminal_observation(self):
-        if self.frame_stack > 1:
-            return {k: self._stack_torch(k, terminal=True) if self.obs_mode == "torch" else self._stack_numpy(k, terminal=True) for k in self._stack_keys()}
+        if self._layout_on():
+            return {k: self._layout_obs(k, terminal=True) for k in self._stack_keys()}
         obs = {}
         if "oracle" in self.observation_mode:
             obs["oracle"] = self.oracle_terminal()
@@ -830,6 +882,9 @@ class SingleTactileEnv(_GymEnvBase):
         if "frame_stack" in kwargs:
             raise TypeError("frame_stack is an option of the vectorised envs (upstream, frame stacking is the VecEnv wrapper VecFrameStack): pass "
                             "vec_env_kwargs=dict(frame_stack=n) to make_vec_env(..., vec_env_cls=HipVecEnv), or frame_stack=n to make_vec()")
+        if "channels_first" in kwargs:
+            raise TypeError("channels_first is an option of the vectorised envs (upstream, it is the VecEnv wrapper VecTransposeImage): pass "
+                            "vec_env_kwargs=dict(channels_first=True) to make_vec_env(..., vec_env_cls=HipVecEnv), or channels_first=True to make_vec()")
         if env_modes is None:
             env_modes = self.default_env_modes
         self._vec = self.vec_cls(1, max_steps, image_size, env_modes, physics_dtype, auto_reset=False, device=device, **kwargs)
@@ -887,7 +942,7 @@ class HipVecEnv:
     info["episode"] = {"r", "l", "t"} for the envs that finished (what SB3's logger and EvalCallback read), and with `monitor_dir` the same
     rows go to `<monitor_dir>/tactile_gym_hip.monitor.csv` in SB3's Monitor format (load_results(monitor_dir), which the reference's
     sb3_helpers/rl_plot_utils.py and custom_callbacks.py call, reads every *monitor.csv of the directory).  Extra keyword arguments
-    (vec_env_kwargs: obs_mode, copy_obs, physics_dtype, device, obs_transfer, frame_stack ...) go to the vectorised constructor; start_method is accepted and
+    (vec_env_kwargs: obs_mode, copy_obs, physics_dtype, device, obs_transfer, frame_stack, channels_first ...) go to the vectorised constructor; start_method is accepted and
     ignored.  The result is a TactileVecEnv (an SB3 VecEnv subclass wherever SB3 is importable), not an instance of this class."""
 
     def __new__(cls, env_fns, start_method=None, **kwargs):
