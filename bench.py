@@ -12,14 +12,16 @@ inside the timed region whenever K + W crosses a multiple of 200; reported separ
 Observations stay resident in HBM (device tensors); the PCIe-inclusive rate is quoted in DESIGN.md, never here.
 The rollout is device resident: steps are enqueued on a torch stream (TorchShard(pipelined=True)) and their outputs consumed on it,
 the host does not wait per step (--sync-steps restores the blocking VecEnv.step_wait path).
-Extra fields: roofline (dominant kernel, HIP-event durations, PMC traffic), cpu_baseline (the CPU oracle on all host cores),
-literal_solver (the same workload with exactly 150 PGS sweeps in every tick), without_full_batch_reset, other_configs (one short
-companion run per remaining BASELINE config at 1024 envs on this GPU), roofline_16384 (the dominant kernel at 16 384 envs),
-staggered_episodes (the headline workload with the envs' episodes out of phase, as in an RL run: some env finishes in nearly every step,
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; every other figure is measured after the
+timed steps with --full only (its fields are null without it).  Fields of --full: window (fill and drain of a K-step window), roofline
+(dominant kernel, HIP-event durations, PMC traffic), broadphase_guard, separate_policy_launch, cpu_baseline (the CPU oracle on all host
+cores), literal_solver (the same workload with exactly 150 PGS sweeps in every tick), without_full_batch_reset, other_configs (one short
+companion run per remaining BASELINE config at 1024 envs on this GPU), residual_threshold_1e-7, roofline_16384 (the dominant kernel at
+16 384 envs), staggered_episodes (the headline workload with the envs' episodes out of phase, as in an RL run: some env finishes in nearly every step,
 whereas the timed region starts all envs together and sees one full-batch reset per 200 steps; tools/desync_rate.py).
 Weak scaling: every rank owns --num-envs envs; rank 0 receives all observations / rewards / dones once per step (--payload: what the
 message carries, --transport: how it travels; parallel.py), started asynchronously so that it overlaps the next step's simulation
-(SURVEY 8e); the last exchange is waited for inside the timed region.  `no_gather` is the same K steps without the exchange (per-rank
+(SURVEY 8e); the last exchange is waited for inside the timed region.  `no_gather` (--full) is the same K steps without the exchange (per-rank
 learners): compute scaling apart from the link bound.  With the default --transport auto --payload auto the transport is chosen by a
 short probe of both (exchange.probe); an ipc exchange that reports an error falls back to the RCCL gather (exchange.fallback).
 Prints ONE JSON line on rank 0, and nothing else on stdout (native libraries' writes to fd 1 are sent to stderr).
@@ -534,6 +536,10 @@ def main():
     ap.add_argument("--num-envs", type=int, default=1024, help="envs per GPU (BASELINE configs[1]: 1024)")
     ap.add_argument("--image-size", type=int, default=128)
     ap.add_argument("--physics", default="f64", choices=["f64", "f32"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beside the headline: window, broadphase_guard, roofline (per-kernel profile), "
+                         "without_full_batch_reset, separate_policy_launch, no_gather, literal_solver, other_configs, residual_threshold_1e-7, "
+                         "roofline.at_16384_envs, staggered_episodes and cpu_baseline (the three options below skip some of them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-literal", action="store_true", help="skip the literal-solver companion run (keeps a rocprofv3 trace of this command to one solver mode)")
     ap.add_argument("--no-companions", action="store_true", help="skip other_configs / roofline_16384 (same purpose)")
@@ -717,7 +723,7 @@ def main():
         dump_outputs(args.dump_outputs, obs, rew, done)
     with w.on_stream():
         no_gather = None
-        if gathered and world > 1:               # the same K steps without the exchange: what per-rank learners would see
+        if args.full and gathered and world > 1:     # the same K steps without the exchange: what per-rank learners would see
             dt_ng = allmax(w.timed(shard, args.steps, barrier))
             no_gather = {"value": round(n * world * args.steps / dt_ng, 1), "unit": "env-steps/s", "ms_per_step": round(1e3 * dt_ng / args.steps, 4),
                          "what": "the same K steps on every rank without the per-step exchange to rank 0 (observations consumed where they are produced)"}
@@ -725,7 +731,7 @@ def main():
         # synchronisation (pipeline fill + drain) are paid once per window - at the driver's K = 20 they are ~2.5 us of every step, at K = 2000
         # nothing.  Measured here, outside the timed region: single-step windows, and (for short runs) a 1000-step window as the steady state.
         window = None
-        if dist is None:
+        if args.full and dist is None:
             ones = sorted(w.timed(env, 1, barrier) for _ in range(7))
             one_ms = 1e3 * ones[len(ones) // 2]
             long_k = 1000
@@ -736,12 +742,12 @@ def main():
                       "explained_ms_per_step": round(long_ms + (one_ms - long_ms) / args.steps, 4),
                       "what": "ms_per_step of a K-step window = steady state + (fill + drain) / K: a window starts on an idle queue (launch latency of its first "
                               "step) and ends in a host synchronisation (completion latency); one_step_window_ms is a window of K = 1 (median of 7)"}
-        guard = guard_report(w, env, max(20, min(args.steps, 300)), barrier) if dist is None else None
-        prof = w.profile(env, min(args.steps, 50), barrier, clock=dist is None)
+        guard = guard_report(w, env, max(20, min(args.steps, 300)), barrier) if args.full and dist is None else None
+        prof = w.profile(env, min(args.steps, 50), barrier, clock=dist is None) if args.full else None
         # SURVEY 8d asks for the rate with and without episode resets: a window that starts right after a reset of every env and
         # ends before any env can reach max_steps (an env that meets its goal early is still reset, as in any rollout)
         no_reset = None
-        if dist is None:
+        if args.full and dist is None:
             env.reset()
             for _ in range(10):
                 w.step(env)
@@ -750,7 +756,7 @@ def main():
             no_reset = {"value": round(n * k_nr / dt_nr, 1), "unit": "env-steps/s", "steps": k_nr, "ms_per_step": round(1e3 * dt_nr / k_nr, 4),
                         "what": "window between full-batch resets (no env reaches max_steps inside it)"}
         separate = None
-        if dist is None and Workload.fused_policy and hasattr(env, "step_random"):
+        if args.full and dist is None and Workload.fused_policy and hasattr(env, "step_random"):
             # the same K steps with the policy's draw as its own launch in front of every step (what a torch policy would be: separate kernels)
             Workload.fused_policy = False
             for _ in range(10):
@@ -769,7 +775,7 @@ def main():
 
     solo = world == 1 and not force
     literal = None
-    if solo and not args.full_sweeps and not args.no_literal:
+    if args.full and solo and not args.full_sweeps and not args.no_literal:
         # the same workload with the literal solver (every tick: dynamics + all 150 PGS sweeps), for comparison; short run
         lw = Workload(args.env, n, args.image_size, args.physics, rank, local_rank, full_sweeps=True, observation_mode=args.observation_mode,
                       pipelined=False, **extra)
@@ -786,7 +792,7 @@ def main():
         lw.close()
     others, big, staggered, thr_runs = None, None, None, None
     headline = args.env == "edge_follow-v0" and n == 1024 and args.image_size == 128 and not args.observation_mode and not args.full_sweeps
-    if solo and headline and not args.no_companions:
+    if args.full and solo and headline and not args.no_companions:
         # one driver-visible line per remaining BASELINE config, 1024 envs on this GPU (the configs' own sharding puts 1024 on each GPU)
         k = max(20, min(args.steps, 200))
         others = [companion("surface_follow-v0", 128, 1024, args.physics, k, barrier, " (BASELINE configs[2])"),
@@ -813,12 +819,14 @@ def main():
     if rank == 0:
         total_envs = n * world
         value = total_envs * args.steps / dt
-        roof = w.roofline(prof, traffic_ok=not args.full_sweeps and args.physics == "f64", ms_per_step=1e3 * dt / args.steps)
-        roof["note"] = ("HBM roofline in form only: the step is bound by per-workgroup latency chains (render) and by the serial solver "
-                        "(k_step), not by bytes; frac = the dominant kernel alone, step_frac = the whole step (its dependent launches and the gaps "
-                        "between them); kernel_ms by the kernels' own clock, their sum per step fits inside ms_per_step; see DESIGN.md 4.3")
-        if big is not None:
-            roof["at_16384_envs"] = big
+        roof = None
+        if prof is not None:
+            roof = w.roofline(prof, traffic_ok=not args.full_sweeps and args.physics == "f64", ms_per_step=1e3 * dt / args.steps)
+            roof["note"] = ("HBM roofline in form only: the step is bound by per-workgroup latency chains (render) and by the serial solver "
+                            "(k_step), not by bytes; frac = the dominant kernel alone, step_frac = the whole step (its dependent launches and the gaps "
+                            "between them); kernel_ms by the kernels' own clock, their sum per step fits inside ms_per_step; see DESIGN.md 4.3")
+            if big is not None:
+                roof["at_16384_envs"] = big
         par = f"env-shard x{world}"
         if exchange is not None:
             par += " + " + exchange["what"]
@@ -853,10 +861,10 @@ def main():
         }
         if args.no_gather and world > 1:
             out["config"]["parallelism"] = f"env-shard x{world}, no exchange (--no-gather)"
-        if prof["scene"][1]:    # --observation-mode visual / visuotactile: the scene camera's two kernels (eye<-frame transforms + raster), per draw
+        if prof is not None and prof["scene"][1]:    # --observation-mode visual / visuotactile: the scene camera's two kernels (eye<-frame transforms + raster), per draw
             out["scene_camera"] = {"observation_mode": modes["observation_mode"], "ms_per_draw": round(prof["scene"][0] / prof["scene"][1], 4),
                                    "draws": prof["scene"][1]}
-        if solo and not args.no_cpu_baseline and args.env == "edge_follow-v0":
+        if args.full and solo and not args.no_cpu_baseline and args.env == "edge_follow-v0":
             out["cpu_baseline"] = cpu_baseline()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     if gathered and hasattr(env, "close"):

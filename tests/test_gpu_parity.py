@@ -1304,7 +1304,7 @@ def test_bench_launches_under_torchrun_on_the_rccl_gather_path(env_id, size, por
     env = dict(os.environ, TG_BENCH_FORCE_COLLECTIVE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "60", "--warmup", "10", "--num-envs", "256",
-           "--env", env_id, "--image-size", str(size), "--no-cpu-baseline", "--no-literal", "--transport", transport, "--payload", payload]
+           "--env", env_id, "--image-size", str(size), "--full", "--no-cpu-baseline", "--no-literal", "--transport", transport, "--payload", payload]
     out = _run_bench(cmd, root, env, f"{port}")
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -1385,6 +1385,22 @@ def test_bench_dumps_the_same_outputs_whatever_the_spin_up(tmp_path):
         total += a.nbytes
     assert total <= 64 << 20
     assert np.load(runs[0] / "reward.npy").shape == (256,) and np.load(runs[0] / "tactile.npy").std() > 0
+
+
+def test_bench_plain_run_measures_the_headline_only():
+    """Without --full a run sets up, warms up, times its K steps and prints the line: every figure that takes runs of its own (the
+    window arithmetic, the per-kernel profile, the companion configs, the CPU baseline) stays null, the headline fields are all there."""
+    import json, os, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = _run_bench([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "5"], root, dict(os.environ), "plain")
+    assert out.returncode == 0, out.stderr[-12000:]
+    d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 40 and d["warmup"] == 5 and d["pre_warm_steps"] > 0
+    assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["metric"].startswith("env-steps/sec")
+    for k in ("window", "roofline", "broadphase_guard", "without_full_batch_reset", "separate_policy_launch", "literal_solver", "other_configs",
+              "residual_threshold_1e-7", "staggered_episodes"):
+        assert d[k] is None, k
+    assert "cpu_baseline" not in d
 
 
 def test_sample_actions_is_a_counter_based_uniform_box_sample(edge_modes):

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Evidence run (rounds 3 - 6: TG_PROFILE_TAG names the output set) on the MI355X box (one gpurun call): the default bench line (headline + other_configs + literal + CPU baseline),
+# Evidence run (rounds 3 - 6: TG_PROFILE_TAG names the output set) on an MI355X in one command: the full bench line (--full: headline + other_configs + literal + CPU baseline),
 # one bench line per env, rocprofv3 kernel stats and SQ counters of the default command and of object_push / object_balance /
 # surface_follow-v2 (MG400, eight-sweep blocks) / the literal solver, HBM traffic (FETCH_SIZE / WRITE_SIZE in separate passes) of
 # edge_follow, object_push and object_balance.  Outputs under gpurun_out/<tag>/; copied to profiles/<tag>_* afterwards (tools/profile_collect.py).
@@ -9,11 +9,11 @@ O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
 python -c "import bench; print(bench.source_hash())" > $O/source_sha16.txt     # what every file of this run was measured on
-timeout 500 python bench.py 2>$O/bench_edge.err | grep metric > $O/bench_edge.json
-# the driver's own command (W = 5, K = 20), three times: what BENCH_rNN.json will hold; bench_driver_like.json = the first
-for k in 1 2 3; do timeout 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | grep metric > $O/bench_driver_like_$k.json; done
+timeout 500 python bench.py --full 2>$O/bench_edge.err | grep metric > $O/bench_edge.json
+# the short benchmark command (W = 5, K = 20) with --full, three times: its headline is what BENCH_rNN.json will hold; bench_driver_like.json = the first
+for k in 1 2 3; do timeout 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | grep metric > $O/bench_driver_like_$k.json; done
 cp $O/bench_driver_like_1.json $O/bench_driver_like.json
-B="timeout 200 python bench.py --no-cpu-baseline --no-companions"
+B="timeout 200 python bench.py --full --no-cpu-baseline --no-companions"
 $B --sync-steps --no-literal 2>/dev/null | grep metric > $O/bench_edge_syncsteps.json
 $B --env surface_follow-v0 2>/dev/null | grep metric > $O/bench_surface_follow-v0.json
 $B --env surface_follow-v2 2>/dev/null | grep metric > $O/bench_surface_follow-v2.json
@@ -38,7 +38,7 @@ TG_BENCH_FORCE_COLLECTIVE=1 $B --no-literal --transport ipc --payload tiles 2>/d
 TG_NO_DIRECT_BATCH=1 TG_BENCH_FORCE_COLLECTIVE=1 $B --no-literal --transport ipc --payload tiles 2>/dev/null | grep metric > $O/bench_edge_ipc_tiles_1rank_copy_into_batch.json   # round 4's path: rank 0 copies its shard into the batch
 TG_BENCH_FORCE_COLLECTIVE=1 $B --no-literal --transport collective --payload interior 2>/dev/null | grep metric > $O/bench_edge_rccl_interior_1rank.json
 cd /tmp; export TMPDIR=/tmp
-P="python $R/bench.py --no-cpu-baseline --no-literal --no-companions"
+P="python $R/bench.py --full --no-cpu-baseline --no-literal --no-companions"
 prof() {   # prof <name> <bench flags...>
     local name=$1; shift
     timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -- $P "$@" > $O/prof_$name.log 2>&1
