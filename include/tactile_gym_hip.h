@@ -597,6 +597,20 @@ int tg_copy_obs_stack_rows(tg_ctx* ctx, int32_t key, int32_t terminal, const int
 #define TG_OBS_KEY_VISUAL 3
 int tg_set_obs_layout(tg_ctx* ctx, int32_t channels_first);
 int tg_get_obs_layout(tg_ctx* ctx, int32_t* channels_first);
+
+/* ---- image augmentation: RAD's kornia RandomAffine(degrees=0, translate=[ax, ay], scale=[1, 1], p) (sb3_helpers/params/<task>_params.py:7-9) ----
+ * Context free.  in_dev: a [B][C][H][W] (channels_first = 1) or [B][H][W][C] (0) batch of uint8 or float32 images (TG_AUGMENT_*) in device
+ * memory; out_dev: float32, same shape and layout, not overlapping the input, which is only read.  Sample b is warped with probability p by a
+ * shift of tx ~ U(-ax W, ax W), ty ~ U(-ay H, ay H) pixels as kornia's warp_affine (bilinear, zero padding, align_corners=False) applies it:
+ * out[y][x] = bilinear(in, x - tx W / (W - 1), y - ty H / (H - 1)), every tap outside the image 0, all channels alike; otherwise out = in.
+ * The draws are element 3 b + k of tg_sample_actions' generator at (seed, counter); params_in_dev (nullable): float32 [B][3] (apply, tx, ty)
+ * used instead of the draws; params_out_dev (nullable): receives them.  H, W >= 2, 0 <= ax, ay, p <= 1; B = 0 does nothing.  Enqueued on
+ * hip_stream; nothing is allocated or synchronised.  The arithmetic, bit for bit: DESIGN.md 4.8. */
+#define TG_AUGMENT_UINT8 0
+#define TG_AUGMENT_FLOAT32 1
+int tg_random_translate(const void* in_dev, void* out_dev, int32_t in_dtype, int32_t channels_first, int64_t B, int32_t C, int32_t H, int32_t W,
+                        double ax, double ay, float p, uint64_t seed, uint64_t counter, const float* params_in_dev, float* params_out_dev,
+                        void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

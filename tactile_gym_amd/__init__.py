@@ -7,9 +7,19 @@
 The per-step arithmetic (rigid-body tick x24, tactile depth raster) runs in hand-written HIP kernels behind the C ABI
 declared in include/tactile_gym_hip.h; importing the package never touches the GPU, constructing an env does and fails
 loudly when the HIP library or a GPU is missing.
+
+    K = tg.augment                                   # RAD's kornia RandomAffine translate on device tensors (imports torch)
+    aug = torch.nn.Sequential(K.RandomAffine(degrees=0, translate=[0.05, 0.05], scale=[1.0, 1.0], p=0.5))
 """
 from . import rl_envs  # noqa: F401  (registers the env ids)
 from .registry import make, make_vec, register, registered_ids  # noqa: F401
 from .vec_env import HipVecEnv  # noqa: F401  (vec_env_cls for stable_baselines3's make_vec_env)
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    if name == "augment":   # imported on first use: it needs torch, the rest of the package does not
+        import importlib
+        return importlib.import_module(".augment", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,0 +1,268 @@
+// tg_augment.hip - RAD's image augmentation on the device: kornia's RandomAffine(degrees=0, translate=(ax, ay), scale=(1, 1), p) with its
+// defaults (bilinear, zero padding, align_corners=False) over uint8 or float32 image batches (tg_random_translate).  Compiled with
+// -ffp-contract=off: the arithmetic below is the bit-exact specification the tests restate (tests/augment_ref.py).
+//
+// Per sample b: apply = u0 < p, tx = (float)(ax W) (2 u1 - 1), ty = (float)(ay H) (2 u2 - 1), u_k = 24 bits of tg_sample_actions' generator at
+// element 3 b + k of draw `counter` (or the caller's [B][3] (apply, tx, ty)).  kornia's warp_affine normalises with W - 1 and grid_sample
+// unnormalises with W, so the shift in pixels is sx = tx W / (W - 1): out[y][x] = bilinear(in, x - sx, y - sy) with every tap outside the image 0.
+// With o = floor(-s) and f = -s - o that is a 2 x 2 stencil of constant weights at a constant integer offset per sample.
+//
+// Mapping: a sample is P planes of H rows of R elements (channels first: P = C, R = W, the right-hand tap one element on; channels last: P = 1,
+// R = W C, the right-hand tap C elements on).  One workgroup per (sample, plane, 4096 output elements): the parameters are computed once per
+// workgroup, the source span that the chunk's four taps can reach - one contiguous range of the plane, the chunk plus one row and one tap -
+// is staged into LDS as float32 with aligned 16-byte loads, and every lane then writes 4 x 16 bytes of output (aligned, each wavefront store
+// 1 KiB contiguous) from aligned 16-byte LDS reads.  The column offset of a tap is the same for every lane of the launch modulo 4, so the
+// unaligned window is two aligned float4 reads and a selection by that uniform remainder.  Samples that are not applied take a plain
+// convert-copy.  Shapes whose planes are not 16-byte multiples, or rows too long for the LDS span, take a per-element path with the same
+// arithmetic.
+#include "tg_augment.h"
+
+#include "../../include/tactile_gym_hip.h"
+#include "tg_exchange.h"   // report_error
+#include "tg_kernels.hpp"  // mix64, kGolden: tg_sample_actions' counter-based generator
+
+namespace tg {
+
+constexpr int kTrThreads = 256;
+constexpr int kTrChunk = 4096;    // output elements per workgroup: 4 float4 per lane
+constexpr int kTrMaxRow = 8192;   // R + S of the staged path: LDS <= (4096 + 8192 + 44) * 4 B = 48.2 KiB
+
+struct TrSample {
+    bool apply;
+    int ox, oy;
+    float fx, fy;
+};
+
+__device__ __forceinline__ float draw_u24(uint64_t seed, uint64_t counter, uint64_t i) {
+    const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (i + 1));
+    return (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
+}
+
+// o = floor(-s), f = (float)(-s - o) for s = t n / (n - 1).  -s is clamped to [-(n + 2), n + 2] first (NaN goes to -(n + 2)): beyond that
+// every tap is outside the image whatever f is.
+__device__ __forceinline__ void split_shift(float t, int n, int& o, float& f) {
+    const double s = (double)t * n / (n - 1);
+    const double m = fmin(fmax(-s, -(double)(n + 2)), (double)(n + 2));
+    const double fl = floor(m);
+    o = (int)fl;
+    f = (float)(m - fl);
+}
+
+__device__ __forceinline__ TrSample sample_params(const TranslateArgs& a, int64_t b, bool write) {
+    bool apply;
+    float tx, ty;
+    if (a.params_in) {
+        apply = a.params_in[3 * b] != 0.f;
+        tx = a.params_in[3 * b + 1];
+        ty = a.params_in[3 * b + 2];
+    } else {
+        const uint64_t i = 3 * (uint64_t)b;
+        apply = draw_u24(a.seed, a.counter, i) < a.p;
+        tx = a.ax_w * (2.f * draw_u24(a.seed, a.counter, i + 1) - 1.f);
+        ty = a.ay_h * (2.f * draw_u24(a.seed, a.counter, i + 2) - 1.f);
+    }
+    if (write && a.params_out && threadIdx.x == 0) {   // one lane of one workgroup per sample
+        a.params_out[3 * b] = apply ? 1.f : 0.f;
+        a.params_out[3 * b + 1] = tx;
+        a.params_out[3 * b + 2] = ty;
+    }
+    TrSample s;
+    s.apply = apply;
+    split_shift(tx, a.W, s.ox, s.fx);
+    split_shift(ty, a.H, s.oy, s.fy);
+    return s;
+}
+
+// Element k of the 8 floats (w0, w1) from position r + k, r in 0..3 the same in every lane (selects, no indexed register array).
+__device__ __forceinline__ float pick(const float4& w0, const float4& w1, int r, int k) {
+    const float w[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
+    return r == 0 ? w[k] : r == 1 ? w[k + 1] : r == 2 ? w[k + 2] : w[k + 3];
+}
+
+// The two aligned float4 of LDS that hold floats [al, al + 8); al = local - r clamped into the allocation (lanes whose taps are all outside
+// the image read something harmless; a tap inside the image never needs the clamp).
+__device__ __forceinline__ void window(const float* lds, int local, int r, int lds_floats, float4& w0, float4& w1) {
+    int al = local - r;
+    al = al < 0 ? 0 : (al > lds_floats - 8 ? lds_floats - 8 : al);
+    w0 = *reinterpret_cast<const float4*>(lds + al);
+    w1 = *reinterpret_cast<const float4*>(lds + al + 4);
+}
+
+// One aligned 16-byte load of input converted to float32 at d: 4 floats, or 16 from uint8.  (4-byte uint8 loads, which would keep every lane's
+// float4 next to its neighbour's, measured 10 % slower.)
+__device__ __forceinline__ void store16(float* d, const float* p) { *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(p); }
+__device__ __forceinline__ void store16(float* d, const uint8_t* p) {
+    const uint4 u = *reinterpret_cast<const uint4*>(p);
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        *reinterpret_cast<float4*>(d + 4 * q) = make_float4((float)(w[q] & 0xffu), (float)((w[q] >> 8) & 0xffu), (float)((w[q] >> 16) & 0xffu),
+                                                            (float)(w[q] >> 24));
+}
+
+__device__ __forceinline__ float blend(float a, float b, float c, float d, float fx, float fy) {
+    const float h0 = (1.f - fx) * a + fx * b;
+    const float h1 = (1.f - fx) * c + fx * d;
+    return (1.f - fy) * h0 + fy * h1;
+}
+
+// vec: the plane is a multiple of 16 bytes of input and of 4 floats of output, both pointers are 16-byte aligned and R + S <= kTrMaxRow.
+template <typename TIN, bool CF>
+__global__ __launch_bounds__(kTrThreads) void k_random_translate(TranslateArgs a, int64_t b0, int nchunk, int vec, int lds_floats) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int P = CF ? a.C : 1, R = CF ? a.W : a.W * a.C, S = CF ? 1 : a.C, H = a.H;
+    const int HR = H * R;
+    const int per_sample = P * nchunk;
+    const int bl = (int)(blockIdx.x / (unsigned)per_sample), rem = (int)blockIdx.x - bl * per_sample;
+    const int64_t b = b0 + bl;
+    const int pl = rem / nchunk, f0 = (rem - pl * nchunk) * kTrChunk;
+    const int fend = HR - f0 < kTrChunk ? HR : f0 + kTrChunk;
+    const TrSample sp = sample_params(a, b, rem == 0);
+    const int64_t base = (b * P + pl) * (int64_t)HR;
+    const TIN* __restrict__ in = reinterpret_cast<const TIN*>(a.in) + base;
+    float* __restrict__ out = a.out + base;
+    const int tid = threadIdx.x;
+
+    if (!sp.apply) {   // convert-copy
+        if (vec) {
+            if (sizeof(TIN) == 1) {
+                const int f = f0 + 16 * tid;
+                if (f < fend) store16(out + f, in + f);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int f = f0 + 4 * tid + 1024 * k;
+                    if (f < fend) store16(out + f, in + f);
+                }
+            }
+        } else {
+            for (int f = f0 + tid; f < fend; f += kTrThreads) out[f] = (float)in[f];
+        }
+        return;
+    }
+
+    const int dx = sp.ox * S, oy = sp.oy;
+    const float fx = sp.fx, fy = sp.fy;
+    if (!vec) {   // per element, taps read from global memory
+        for (int f = f0 + tid; f < fend; f += kTrThreads) {
+            const int y = f / R, j = f - y * R;
+            const int ya = y + oy, xa = j + dx;
+            const bool r0 = ya >= 0 && ya < H, r1 = ya + 1 >= 0 && ya + 1 < H;
+            const bool c0 = xa >= 0 && xa < R, c1 = xa + S >= 0 && xa + S < R;
+            const int64_t t = (int64_t)ya * R + xa;
+            const float va = r0 && c0 ? (float)in[t] : 0.f, vb = r0 && c1 ? (float)in[t + S] : 0.f;
+            const float vc = r1 && c0 ? (float)in[t + R] : 0.f, vd = r1 && c1 ? (float)in[t + R + S] : 0.f;
+            out[f] = blend(va, vb, vc, vd, fx, fy);
+        }
+        return;
+    }
+
+    // Stage the source span [s_lo, s_hi) of the plane (clamped to it, widened to 16-byte vectors) at lds[src - a_lo + 4].
+    constexpr int V = 16 / (int)sizeof(TIN);
+    const int D = oy * R + dx;                                       // |oy| <= H + 2, |dx| <= (W + 2) S: fits, the span ends may not
+    const int64_t lo64 = (int64_t)f0 + D, hi64 = (int64_t)fend + D + R + S;
+    const int lo = lo64 < 0 ? 0 : (lo64 > HR ? HR : (int)lo64), hi = hi64 > HR ? HR : (hi64 < 0 ? 0 : (int)hi64);
+    const int a_lo = lo / V * V;
+    if (lo < hi) {
+        const int a_hi = (hi + V - 1) / V * V;
+        for (int v = a_lo + V * tid; v < a_hi; v += V * kTrThreads) store16(lds + (v - a_lo + 4), in + v);
+    }
+    __syncthreads();
+
+    // Tap shifts: a at D, b at D + S, c at D + R, d at D + R + S; the window remainder of each is the shift mod 4 (f and a_lo are multiples of 4).
+    const int ra = D & 3, rc = (D + R) & 3, rb = (D + S) & 3, rd = (D + R + S) & 3;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int f = f0 + 4 * tid + 1024 * k;
+        if (f >= fend) break;
+        const int local = f - a_lo + 4;
+        float4 a0, a1, c0, c1, b0w, b1w, d0w, d1w;
+        window(lds, local + D, ra, lds_floats, a0, a1);
+        window(lds, local + D + R, rc, lds_floats, c0, c1);
+        if (!CF) {
+            window(lds, local + D + S, rb, lds_floats, b0w, b1w);
+            window(lds, local + D + R + S, rd, lds_floats, d0w, d1w);
+        }
+        int y = f / R, j = f - y * R;
+        float o[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i > 0 && ++j == R) { j = 0; ++y; }
+            const int ya = y + oy, xa = j + dx;
+            const bool r0 = ya >= 0 && ya < H, r1 = ya + 1 >= 0 && ya + 1 < H;
+            const bool cl0 = xa >= 0 && xa < R, cl1 = xa + S >= 0 && xa + S < R;
+            const float ea = pick(a0, a1, ra, i), ec = pick(c0, c1, rc, i);
+            const float eb = CF ? pick(a0, a1, ra, i + 1) : pick(b0w, b1w, rb, i);
+            const float ed = CF ? pick(c0, c1, rc, i + 1) : pick(d0w, d1w, rd, i);
+            o[i] = blend(r0 && cl0 ? ea : 0.f, r0 && cl1 ? eb : 0.f, r1 && cl0 ? ec : 0.f, r1 && cl1 ? ed : 0.f, fx, fy);
+        }
+        *reinterpret_cast<float4*>(out + f) = make_float4(o[0], o[1], o[2], o[3]);
+    }
+}
+
+template <typename TIN, bool CF>
+static int launch_typed(const TranslateArgs& a, hipStream_t stream) {
+    const int P = CF ? a.C : 1, R = CF ? a.W : a.W * a.C, S = CF ? 1 : a.C;
+    const int64_t HR = (int64_t)a.H * R;
+    const int nchunk = (int)((HR + kTrChunk - 1) / kTrChunk);
+    constexpr int V = 16 / (int)sizeof(TIN);
+    const int vec = HR % V == 0 && !(((uintptr_t)a.in | (uintptr_t)a.out) & 15) && R + S <= kTrMaxRow;
+    const int lds_floats = vec ? (kTrChunk + R + S + 2 * V + 12 + 3) / 4 * 4 : 0;
+    const int64_t per_sample = (int64_t)P * nchunk;
+    const int64_t max_blocks = 1 << 23;                       // grid x * 256 lanes stays below 2^32
+    const int64_t spl = max_blocks / per_sample;
+    if (spl < 1) return -1;
+    for (int64_t b0 = 0; b0 < a.B; b0 += spl) {
+        const int64_t nb = a.B - b0 < spl ? a.B - b0 : spl;
+        hipLaunchKernelGGL((k_random_translate<TIN, CF>), dim3((unsigned)(nb * per_sample)), dim3(kTrThreads), (size_t)lds_floats * 4, stream,
+                           a, b0, nchunk, vec, lds_floats);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_random_translate(const TranslateArgs& a, int in_dtype, int channels_first, hipStream_t stream) {
+    if (a.B <= 0) return a.B == 0 ? 0 : -1;
+    if (!a.in || !a.out || a.C < 1 || a.H < 2 || a.W < 2 || (int64_t)a.C * a.H * a.W > (1 << 30)) return -1;
+    if (in_dtype == kTranslateU8)
+        return channels_first ? launch_typed<uint8_t, true>(a, stream) : launch_typed<uint8_t, false>(a, stream);
+    if (in_dtype == kTranslateF32)
+        return channels_first ? launch_typed<float, true>(a, stream) : launch_typed<float, false>(a, stream);
+    return -1;
+}
+
+}  // namespace tg
+
+extern "C" int tg_random_translate(const void* in_dev, void* out_dev, int32_t in_dtype, int32_t channels_first, int64_t B, int32_t C, int32_t H,
+                                   int32_t W, double ax, double ay, float p, uint64_t seed, uint64_t counter, const float* params_in_dev,
+                                   float* params_out_dev, void* hip_stream) {
+    using tg::report_error;
+    if (in_dtype != TG_AUGMENT_UINT8 && in_dtype != TG_AUGMENT_FLOAT32) return report_error(-1, "tg_random_translate: unknown input dtype");
+    if (B < 0 || C < 1 || H < 2 || W < 2) return report_error(-1, "tg_random_translate: need B >= 0, C >= 1, H >= 2, W >= 2");
+    if ((int64_t)C * H * W > (1 << 30)) return report_error(-1, "tg_random_translate: more than 2^30 elements per image");
+    if (!(ax >= 0.0 && ax <= 1.0 && ay >= 0.0 && ay <= 1.0)) return report_error(-1, "tg_random_translate: translate must lie in [0, 1]");
+    if (!(p >= 0.f && p <= 1.f)) return report_error(-1, "tg_random_translate: p must lie in [0, 1]");
+    if (B == 0) return 0;
+    if (!in_dev || !out_dev) return report_error(-1, "tg_random_translate: NULL image pointer");
+    const uint64_t n = (uint64_t)B * C * H * W, ib = (uint64_t)(uintptr_t)in_dev, ob = (uint64_t)(uintptr_t)out_dev;
+    const uint64_t in_bytes = n * (in_dtype == TG_AUGMENT_UINT8 ? 1 : 4), out_bytes = n * 4;
+    if (ib < ob + out_bytes && ob < ib + in_bytes) return report_error(-1, "tg_random_translate: the output overlaps the input (out of place only)");
+    tg::TranslateArgs a;
+    a.in = in_dev;
+    a.out = (float*)out_dev;
+    a.params_in = params_in_dev;
+    a.params_out = params_out_dev;
+    a.B = B;
+    a.C = C;
+    a.H = H;
+    a.W = W;
+    a.ax_w = (float)(ax * W);
+    a.ay_h = (float)(ay * H);
+    a.p = p;
+    a.seed = seed;
+    a.counter = counter;
+    const int rc = tg::launch_random_translate(a, in_dtype == TG_AUGMENT_UINT8 ? tg::kTranslateU8 : tg::kTranslateF32, channels_first,
+                                               (hipStream_t)hip_stream);
+    if (rc == -2) return report_error(-2, "tg_random_translate: the kernel launch failed");
+    if (rc) return report_error(rc, "tg_random_translate: arguments the kernel is not built for");
+    return 0;
+}
