@@ -611,6 +611,42 @@ int tg_get_obs_layout(tg_ctx* ctx, int32_t* channels_first);
 int tg_random_translate(const void* in_dev, void* out_dev, int32_t in_dtype, int32_t channels_first, int64_t B, int32_t C, int32_t H, int32_t W,
                         double ax, double ay, float p, uint64_t seed, uint64_t counter, const float* params_in_dev, float* params_out_dev,
                         void* hip_stream);
+/* tg_random_translate with a row-indexed source: rows_dev (nullable; device memory, int64 [B]) names the source sample of every output sample -
+ * sample b reads source sample rows_dev[b] of in_dev; draws, params_in_dev / params_out_dev and the output stay indexed by b.  With p = 0 it is
+ * the plain gather-and-convert to float32.  NULL rows_dev is tg_random_translate itself.  With rows the caller guarantees that every entry names
+ * a sample inside in_dev's allocation and that out_dev does not overlap it (the extent of the source is not known here). */
+int tg_random_translate_rows(const void* in_dev, void* out_dev, int32_t in_dtype, int32_t channels_first, int64_t B, int32_t C, int32_t H,
+                             int32_t W, double ax, double ay, float p, uint64_t seed, uint64_t counter, const float* params_in_dev,
+                             float* params_out_dev, const int64_t* rows_dev, void* hip_stream);
+
+/* ---- device rollout buffer: stable_baselines3's RolloutBuffer / DictRolloutBuffer over step-major [T][N][...] device arrays ----
+ * Context free; every call is ONE launch enqueued on hip_stream, nothing is allocated or synchronised.  The pointer / size tables are host arrays
+ * of n_arrays <= TG_ROLLOUT_MAX_ARRAYS entries, read before the call returns; the pointers in them are device memory.
+ *
+ * tg_rollout_add: array i copies bytes[i] bytes from src_dev[i] to dst_dev[i] (TG_ROLLOUT_COPY), or reads bytes[i] uint8 flags and writes as
+ * many float32 0.0 / 1.0 (TG_ROLLOUT_FLAG_U8; dst 4-byte aligned): the observation keys and per-env rows of one step into their slot.  16-byte
+ * accesses where both pointers and the byte count allow, 4-byte or single bytes otherwise.  No destination may overlap its source.
+ *
+ * tg_rollout_gae: SB3's GAE(lambda) over float32 [T][N] rewards / values / episode_starts, float32 [N] last_values and [N] dones (uint8 or
+ * float32, non-zero = done), writing float32 [T][N] advantages and returns.  Per env, t = T-1 ... 0, float32, one rounding per operation, no fused
+ * multiply-add, g = (float)gamma, gl = (float)(gamma * gae_lambda):
+ *     nnt = 1 - (t == T-1 ? dones : episode_starts[t+1]);   nv = t == T-1 ? last_values : values[t+1]
+ *     delta = (rewards[t] + (g * nv) * nnt) - values[t];    last = delta + (gl * nnt) * last   (last = 0 before t = T-1)
+ *     advantages[t] = last;                                 returns[t] = last + values[t]
+ *
+ * tg_rollout_gather: for every array i and b < B, row b of dst_dev[i] = row rows_dev[b] of src_dev[i], rows of row_bytes[i] bytes (one minibatch
+ * of every array that is not an image key).  rows_dev: device memory, int64 [B], every entry a row inside each source (not checked). */
+#define TG_ROLLOUT_MAX_ARRAYS 16
+#define TG_ROLLOUT_COPY 0
+#define TG_ROLLOUT_FLAG_U8 1
+#define TG_ROLLOUT_DONES_UINT8 0
+#define TG_ROLLOUT_DONES_FLOAT32 1
+int tg_rollout_add(int32_t n_arrays, const void* const* src_dev, void* const* dst_dev, const int64_t* bytes, const int32_t* kinds, void* hip_stream);
+int tg_rollout_gae(const float* rewards_dev, const float* values_dev, const float* episode_starts_dev, const float* last_values_dev,
+                   const void* dones_dev, int32_t dones_dtype, float* advantages_dev, float* returns_dev, int64_t T, int64_t N, double gamma,
+                   double gae_lambda, void* hip_stream);
+int tg_rollout_gather(int32_t n_arrays, const void* const* src_dev, void* const* dst_dev, const int64_t* row_bytes, const int64_t* rows_dev,
+                      int64_t B, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

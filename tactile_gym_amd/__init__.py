@@ -10,6 +10,8 @@ loudly when the HIP library or a GPU is missing.
 
     K = tg.augment                                   # RAD's kornia RandomAffine translate on device tensors (imports torch)
     aug = torch.nn.Sequential(K.RandomAffine(degrees=0, translate=[0.05, 0.05], scale=[1.0, 1.0], p=0.5))
+    buf = tg.DeviceRolloutBuffer.for_env(venv, n_steps, gamma=0.95, gae_lambda=0.9)   # SB3's rollout buffer in device memory (tg.rollout; imports torch)
+    for batch in buf.get(64, augment=aug): ...
 """
 from . import rl_envs  # noqa: F401  (registers the env ids)
 from .registry import make, make_vec, register, registered_ids  # noqa: F401
@@ -19,7 +21,10 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name == "augment":   # imported on first use: it needs torch, the rest of the package does not
+    if name in ("augment", "rollout"):   # imported on first use: they need torch, the rest of the package does not
         import importlib
-        return importlib.import_module(".augment", __name__)
+        return importlib.import_module("." + name, __name__)
+    if name == "DeviceRolloutBuffer":
+        import importlib
+        return importlib.import_module(".rollout", __name__).DeviceRolloutBuffer
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

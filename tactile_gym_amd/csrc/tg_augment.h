@@ -13,6 +13,7 @@ struct TranslateArgs {
     float* out = nullptr;
     const float* params_in = nullptr;   // [B][3] (apply, tx, ty) in pixels; null: drawn from (seed, counter)
     float* params_out = nullptr;        // [B][3] written by one lane per sample; may be null
+    const int64_t* rows = nullptr;      // [B] source sample of every output sample (tg_random_translate_rows); null: sample b reads sample b
     int64_t B = 0;
     int C = 0, H = 0, W = 0;
     float ax_w = 0.f, ay_h = 0.f, p = 0.f;   // (float)(ax * W), (float)(ay * H), p

@@ -14,7 +14,8 @@
 // 1 KiB contiguous) from aligned 16-byte LDS reads.  The column offset of a tap is the same for every lane of the launch modulo 4, so the
 // unaligned window is two aligned float4 reads and a selection by that uniform remainder.  Samples that are not applied take a plain
 // convert-copy.  Shapes whose planes are not 16-byte multiples, or rows too long for the LDS span, take a per-element path with the same
-// arithmetic.
+// arithmetic.  tg_random_translate_rows gives the source a row table (sample b reads source sample rows[b]: the minibatch gather of the device
+// rollout buffer): the workgroup's source base is the only thing that changes.
 #include "tg_augment.h"
 
 #include "../../include/tactile_gym_hip.h"
@@ -118,9 +119,9 @@ __global__ __launch_bounds__(kTrThreads) void k_random_translate(TranslateArgs a
     const int pl = rem / nchunk, f0 = (rem - pl * nchunk) * kTrChunk;
     const int fend = HR - f0 < kTrChunk ? HR : f0 + kTrChunk;
     const TrSample sp = sample_params(a, b, rem == 0);
-    const int64_t base = (b * P + pl) * (int64_t)HR;
-    const TIN* __restrict__ in = reinterpret_cast<const TIN*>(a.in) + base;
-    float* __restrict__ out = a.out + base;
+    const int64_t bsrc = a.rows ? a.rows[b] : b;   // row-indexed source: only the workgroup's source base moves
+    const TIN* __restrict__ in = reinterpret_cast<const TIN*>(a.in) + (bsrc * P + pl) * (int64_t)HR;
+    float* __restrict__ out = a.out + (b * P + pl) * (int64_t)HR;
     const int tid = threadIdx.x;
 
     if (!sp.apply) {   // convert-copy
@@ -232,9 +233,9 @@ int launch_random_translate(const TranslateArgs& a, int in_dtype, int channels_f
 
 }  // namespace tg
 
-extern "C" int tg_random_translate(const void* in_dev, void* out_dev, int32_t in_dtype, int32_t channels_first, int64_t B, int32_t C, int32_t H,
-                                   int32_t W, double ax, double ay, float p, uint64_t seed, uint64_t counter, const float* params_in_dev,
-                                   float* params_out_dev, void* hip_stream) {
+extern "C" int tg_random_translate_rows(const void* in_dev, void* out_dev, int32_t in_dtype, int32_t channels_first, int64_t B, int32_t C, int32_t H,
+                                        int32_t W, double ax, double ay, float p, uint64_t seed, uint64_t counter, const float* params_in_dev,
+                                        float* params_out_dev, const int64_t* rows_dev, void* hip_stream) {
     using tg::report_error;
     if (in_dtype != TG_AUGMENT_UINT8 && in_dtype != TG_AUGMENT_FLOAT32) return report_error(-1, "tg_random_translate: unknown input dtype");
     if (B < 0 || C < 1 || H < 2 || W < 2) return report_error(-1, "tg_random_translate: need B >= 0, C >= 1, H >= 2, W >= 2");
@@ -245,12 +246,13 @@ extern "C" int tg_random_translate(const void* in_dev, void* out_dev, int32_t in
     if (!in_dev || !out_dev) return report_error(-1, "tg_random_translate: NULL image pointer");
     const uint64_t n = (uint64_t)B * C * H * W, ib = (uint64_t)(uintptr_t)in_dev, ob = (uint64_t)(uintptr_t)out_dev;
     const uint64_t in_bytes = n * (in_dtype == TG_AUGMENT_UINT8 ? 1 : 4), out_bytes = n * 4;
-    if (ib < ob + out_bytes && ob < ib + in_bytes) return report_error(-1, "tg_random_translate: the output overlaps the input (out of place only)");
+    if (!rows_dev && ib < ob + out_bytes && ob < ib + in_bytes) return report_error(-1, "tg_random_translate: the output overlaps the input (out of place only)");
     tg::TranslateArgs a;
     a.in = in_dev;
     a.out = (float*)out_dev;
     a.params_in = params_in_dev;
     a.params_out = params_out_dev;
+    a.rows = rows_dev;
     a.B = B;
     a.C = C;
     a.H = H;
@@ -265,4 +267,11 @@ extern "C" int tg_random_translate(const void* in_dev, void* out_dev, int32_t in
     if (rc == -2) return report_error(-2, "tg_random_translate: the kernel launch failed");
     if (rc) return report_error(rc, "tg_random_translate: arguments the kernel is not built for");
     return 0;
+}
+
+extern "C" int tg_random_translate(const void* in_dev, void* out_dev, int32_t in_dtype, int32_t channels_first, int64_t B, int32_t C, int32_t H,
+                                   int32_t W, double ax, double ay, float p, uint64_t seed, uint64_t counter, const float* params_in_dev,
+                                   float* params_out_dev, void* hip_stream) {
+    return tg_random_translate_rows(in_dev, out_dev, in_dtype, channels_first, B, C, H, W, ax, ay, p, seed, counter, params_in_dev, params_out_dev,
+                                    nullptr, hip_stream);
 }

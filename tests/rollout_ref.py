@@ -1,0 +1,96 @@
+"""Reference of tactile_gym_amd.rollout (csrc/tg_rollout.hip): stable_baselines3's RolloutBuffer / DictRolloutBuffer semantics restated in numpy.
+
+SB3 (common/buffers.py) stores [T, N, ...] arrays, computes GAE(lambda) in compute_returns_and_advantage
+
+    for step in reversed(range(T)):
+        next_non_terminal = 1 - (dones if step == T - 1 else episode_starts[step + 1])
+        next_values       =      last_values if step == T - 1 else values[step + 1]
+        delta        = rewards[step] + gamma * next_values * next_non_terminal - values[step]
+        last_gae_lam = delta + gamma * gae_lambda * next_non_terminal * last_gae_lam
+        advantages[step] = last_gae_lam
+    returns = advantages + values
+
+and hands out minibatches of swap_and_flatten(arr) = arr.swapaxes(0, 1).reshape(T * N, ...) indexed by a permutation: flat sample i = n T + t.
+
+gae_f64: that recurrence in float64 (what SB3 computes up to its mixed float32 / float64 intermediates).  gae_f32: the device arithmetic, every
+operation one float32 rounding, no fused multiply-add, g = float32(gamma), gl = float32(gamma * gae_lambda) with the product formed in double;
+the device output must equal it bit for bit.
+"""
+import numpy as np
+
+
+def _flags(x):
+    return (np.asarray(x) != 0)
+
+
+def gae_f64(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda):
+    """(advantages, returns), float64 [T, N]: SB3's recurrence."""
+    r, v, es = (np.asarray(a, dtype=np.float64) for a in (rewards, values, episode_starts))
+    T, N = r.shape
+    lv, d = np.asarray(last_values, dtype=np.float64).reshape(N), _flags(dones).reshape(N).astype(np.float64)
+    adv = np.zeros((T, N))
+    last = np.zeros(N)
+    for t in reversed(range(T)):
+        nnt = 1.0 - (d if t == T - 1 else es[t + 1])
+        nv = lv if t == T - 1 else v[t + 1]
+        delta = r[t] + gamma * nv * nnt - v[t]
+        last = delta + gamma * gae_lambda * nnt * last
+        adv[t] = last
+    return adv, adv + v
+
+
+def gae_f32(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda, starts_offset=1):
+    """(advantages, returns), float32 [T, N]: the device arithmetic.  starts_offset=0 is a deliberately wrong recurrence (episode_starts[t] in
+    place of [t + 1]) for the test that shows the error bound is not vacuous."""
+    f = np.float32
+    r, v, es = (np.ascontiguousarray(a, dtype=f) for a in (rewards, values, episode_starts))
+    T, N = r.shape
+    lv, d = np.asarray(last_values, dtype=f).reshape(N), _flags(dones).reshape(N).astype(f)
+    g, gl, one = f(gamma), f(float(gamma) * float(gae_lambda)), f(1)
+    adv, ret = np.zeros((T, N), f), np.zeros((T, N), f)
+    last = np.zeros(N, f)
+    for t in reversed(range(T)):
+        if starts_offset == 1:
+            nnt = one - (d if t == T - 1 else es[t + 1])
+        else:
+            nnt = one - es[t]
+        nv = lv if t == T - 1 else v[t + 1]
+        delta = (r[t] + (g * nv) * nnt) - v[t]
+        last = delta + (gl * nnt) * last
+        adv[t] = last
+        ret[t] = last + v[t]
+    assert adv.dtype == f and ret.dtype == f and last.dtype == f
+    return adv, ret
+
+
+def gae_bound(rewards, values, last_values, adv_f64, gamma, gae_lambda):
+    """Bound of max |gae_f32 - gae_f64|: six float32 roundings per step (8 with slack), each at most 2^-24 of a term bounded by
+    A = max|r| + (1 + gamma) max|v| + gamma lambda max|adv|, summed over the steps with the damping gamma lambda: A / (1 - gamma lambda), or
+    A T when gamma lambda = 1."""
+    T = np.asarray(rewards).shape[0]
+    vmax = max(np.abs(values).max(), np.abs(last_values).max())
+    A = np.abs(rewards).max() + (1 + gamma) * vmax + gamma * gae_lambda * np.abs(adv_f64).max()
+    gl = gamma * gae_lambda
+    return 8 * 2.0 ** -24 * A * (T if gl >= 1 else 1 / (1 - gl))
+
+
+def flat_rows(indices, T, N):
+    """Storage rows t N + n of SB3's flat sample indices i = n T + t."""
+    i = np.asarray(indices, dtype=np.int64)
+    return (i % T) * N + i // T
+
+
+def swap_and_flatten(arr):
+    """SB3's swap_and_flatten: [T, N, ...] -> [T N, ...] with sample i = n T + t."""
+    a = np.asarray(arr)
+    T, N = a.shape[:2]
+    return a.swapaxes(0, 1).reshape((T * N,) + a.shape[2:])
+
+
+def minibatches(storage, indices, batch_size):
+    """SB3's get(): `storage` {name: [T, N, ...]}; yields {name: swap_and_flatten(array)[indices[start:start + batch_size]]}."""
+    flat = {k: swap_and_flatten(v) for k, v in storage.items()}
+    idx = np.asarray(indices, dtype=np.int64)
+    for start in range(0, len(idx), batch_size):
+        sel = idx[start:start + batch_size]
+        yield {k: v[sel] for k, v in flat.items()}
