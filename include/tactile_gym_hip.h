@@ -179,7 +179,9 @@ typedef struct {
     /* object_push / object_roll: how the contact solve of stepSimulation (robot.py:141; 150 PGS sweeps, base_tactile_env.py:127-130) is
      * mapped onto the GPU.  TG_CONTACT_MAP_WAVE: one 64-lane wavefront per env, one solver row per lane (fills the chip at ~1024 envs);
      * TG_CONTACT_MAP_LANE: one lane per env (fewer instructions per env, better once every SIMD is busy); AUTO picks by num_envs.
-     * Same solver, same row order; results agree to rounding (f64), contact sets exactly. */
+     * Same solver, same row order; results agree to rounding (f64), contact sets exactly.  The wave kernels are built for f64 with cone
+     * friction (object_roll: the UR5; a tip hull that fits LDS); tg_create decides once per context, and any other combination steps AND resets
+     * on the lane mapping whatever this field asks for (tg_get_step_mode: envs_per_wavefront 64). */
     int32_t contact_mapping;                /* TG_CONTACT_MAP_* */
     /* edge_follow / surface_follow with auto_reset: the reset of these envs (edge_follow_env.py:311-336, base_surface_env.py:616-662,
      * robot.py:114-125) is a pure function of the env's RNG stream, so every env's NEXT post-reset state is computed ahead of time on a
@@ -309,7 +311,8 @@ int tg_set_obs_targets(tg_ctx* ctx, int32_t count, void* const* dev_ptrs);
 int tg_select_obs_target(tg_ctx* ctx, int32_t index);
 /* How tg_step runs on this context: *mode = 1 one launch per step (tg_config.fused_step; csrc/tg_fused.hip), 0 separate step / reset / render
  * launches; *envs_per_wavefront = envs one wavefront steps and draws in the one-launch form; in the separate form, envs one wavefront of the
- * last arm step launch stepped (16: k_step_quad, a quad of lanes per env; 64: a lane per env), 0 before the first such launch. */
+ * context's step kernel steps (16: k_step_quad, a quad of lanes per env; 64: a lane per env; 1: a wavefront per env).  The step kernel is chosen
+ * once, by tg_create, from tg_config, the robot and the stimulus: the answer is the same before and after the first step. */
 int tg_get_step_mode(tg_ctx* ctx, int32_t* mode, int32_t* envs_per_wavefront);
 int tg_pack_interior(tg_ctx* ctx, void* dst_dev);
 int tg_unpack_interior(tg_ctx* ctx, const void* src_dev, int32_t n_images, void* dst_dev);

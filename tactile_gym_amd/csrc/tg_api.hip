@@ -290,144 +290,107 @@ struct Timer {
 };
 
 
-// reset_phase >= 0: the finished envs' auto-reset (k_reset's body, phase `reset_phase`) runs inside the step's launch (k_step<T, TOPO, true>;
-// the UR5 only - on the MG400 a step is 0.7 ms of full ticks and the launch it would save is noise); returns whether it did
-template <typename T, int TOPO> static bool launch_step_t(tg_ctx* c, const float* d_actions, int reset_phase = -1) {
-    const int n = c->cfg.num_envs;
-    c->step_envs_per_wave = 64;
-    if (c->cfg.control_mode == TG_CONTROL_TCP_POSITION) {
-        hipLaunchKernelGGL((k_step_pos<T, TOPO>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                           (const EnvConst<T>*)c->d_const, c->st, d_actions);
-        return false;
+static const BankDev* bank_dev(const tg_ctx* c) { return c->bank_mode != 0 ? (const BankDev*)c->d_bank : nullptr; }
+
+// The launch functions below stand in the order draws, resets, bank refill, steps: the compiler lays the kernels out in tg_api's code object in
+// the order in which this file first names them, and the step kernels at other addresses measured 0.25 - 0.4 % slower in device-bound rollouts
+// (profiles/step_dispatch_refactor.txt, section 4).  tools/dev/compare_device_code.py against the previous build shows a changed layout.
+static int oracle_dim(const tg_ctx* c) {
+    switch (c->cfg.env_kind) {
+        case TG_ENV_EDGE_FOLLOW: return 10;
+        case TG_ENV_SURFACE_FOLLOW_AUTO: return 20;
+        case TG_ENV_OBJECT_BALANCE: return 26;
+        case TG_ENV_OBJECT_PUSH: return 30;
+        default: return 34;
     }
-    if constexpr (TOPO == 0 && std::is_same<T, double>::value) {   // (f64 physics: the configuration every BASELINE config runs)
-        if (c->kstep_quad) {   // a quad of lanes per env (k_step_quad): 4 n threads
-            const dim3 grid((unsigned)((4 * (size_t)n + 63) / 64));
-            c->step_envs_per_wave = 16;
-            if (reset_phase >= 0)
-                hipLaunchKernelGGL((k_step_quad<T, true>), grid, dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot, (const EnvConst<T>*)c->d_const,
-                                   c->st, d_actions, reset_phase, c->bank_mode != 0 ? (const BankDev*)c->d_bank : (const BankDev*)nullptr);
-            else
-                hipLaunchKernelGGL((k_step_quad<T, false>), grid, dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot, (const EnvConst<T>*)c->d_const,
-                                   c->st, d_actions, -1, (const BankDev*)nullptr);
-            return reset_phase >= 0;
-        }
-        if (reset_phase >= 0) {
-            hipLaunchKernelGGL((k_step<T, TOPO, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                               (const EnvConst<T>*)c->d_const, c->st, d_actions, reset_phase, c->bank_mode != 0 ? (const BankDev*)c->d_bank : (const BankDev*)nullptr);
-            return true;
-        }
-    }
-    hipLaunchKernelGGL((k_step<T, TOPO>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st, d_actions, -1, (const BankDev*)nullptr);
-    return false;
 }
-template <typename T, int TOPO> static void launch_reset_t(tg_ctx* c, const uint8_t* d_mask, int phase, bool bank = false) {
-    const int n = c->cfg.num_envs;
-    hipLaunchKernelGGL((k_reset<T, TOPO>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st, d_mask, phase, bank ? (const BankDev*)c->d_bank : (const BankDev*)nullptr);
-    if (c->st.kt) c->st.kt += 2 * (size_t)((n + 63) / 64);   // profiling: a second k_reset of the same scope (surface_follow's phase 2) stamps its own slots
+static void oracle_draw(tg_ctx* c, float* dst) {
+    dispatch(c, [&](auto p) { launch_env(c, k_oracle_obs<typename decltype(p)::T, decltype(p)::TOPO>, 0, oracle_dim(c), dst); });
 }
-template <typename T, int TOPO> static void launch_bank_refill_t(tg_ctx* c, int phase) {
-    const int n = c->cfg.num_envs;
-    hipLaunchKernelGGL((k_bank_refill<T, TOPO>), dim3((n + 63) / 64), dim3(64), 0, c->bank_stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st, c->bk, c->aux, phase);
+// get_visual_obs for the whole batch (or the masked envs; save_prev keeps their previous image as the terminal observation)
+static void scene_draw(tg_ctx* c, const uint8_t* d_mask, bool save_prev) {
+    Timer t(c, 4);
+    dispatch(c, [&](auto p) {
+        launch_env(c, k_scene_xf<typename decltype(p)::T, decltype(p)::TOPO>, 0, c->scene_view, d_mask, c->d_scene_xf, c->d_scene_spheres, c->scene.n_spheres);
+    });
+    launch_scene(c->scene, c->d_scene_xf, c->cfg.num_envs, d_mask, c->d_vis, save_prev ? c->d_vis_term : nullptr, c->stream);
 }
 
-template <typename T> static void launch_step_body_t(tg_ctx* c, const float* d_actions) {
-    const int n = c->cfg.num_envs;
-    if (c->cfg.balance_object == TG_BALANCE_BALL_ON_PLATE) {
-        if (c->cfg.control_mode == TG_CONTROL_TCP_POSITION)
-            hipLaunchKernelGGL((k_step_body<T, 0, true, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                               (const EnvConst<T>*)c->d_const, c->st, d_actions);
-        else
-            hipLaunchKernelGGL((k_step_body<T, 0, false, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                               (const EnvConst<T>*)c->d_const, c->st, d_actions);
-        return;
-    }
-    if (c->cfg.control_mode == TG_CONTROL_TCP_POSITION)
-        hipLaunchKernelGGL((k_step_body<T, 0, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                           (const EnvConst<T>*)c->d_const, c->st, d_actions);
-    else
-        hipLaunchKernelGGL((k_step_body<T, 0, false>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                           (const EnvConst<T>*)c->d_const, c->st, d_actions);
+// ---- resets
+static void launch_reset_arm(tg_ctx* c, const uint8_t* d_mask, int phase, bool bank) {
+    dispatch(c, [&](auto p) { launch_env(c, k_reset<typename decltype(p)::T, decltype(p)::TOPO>, 0, d_mask, phase, bank ? (const BankDev*)c->d_bank : nullptr); });
+    if (c->st.kt) c->st.kt += 2 * (size_t)((c->cfg.num_envs + 63) / 64);   // profiling: a second k_reset of the same scope (surface_follow's phase 2) stamps its own slots
 }
+// k_reset_body: every object_balance family (the UR5 chain only: tg_create)
 template <typename T> static void launch_reset_body_t(tg_ctx* c, const uint8_t* d_mask) {
-    const int n = c->cfg.num_envs;
-    if (c->cfg.balance_object == TG_BALANCE_SPINNING_PLATE) {   // (the template is always there in this mode: tg_create)
-        if (c->tmpl_ready)
-            hipLaunchKernelGGL((k_reset_body<T, 0, false, true, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                               (const EnvConst<T>*)c->d_const, c->st, d_mask);
-        else
-            hipLaunchKernelGGL((k_reset_body<T, 0, false, false, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                               (const EnvConst<T>*)c->d_const, c->st, d_mask);
-        return;
-    }
-    if (c->tmpl_ready) {   // a reset that covered env 0 has been enqueued before this one: the template is there when this launch runs
-        if (c->cfg.balance_object == TG_BALANCE_BALL_ON_PLATE)
-            hipLaunchKernelGGL((k_reset_body<T, 0, true, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                               (const EnvConst<T>*)c->d_const, c->st, d_mask);
-        else
-            hipLaunchKernelGGL((k_reset_body<T, 0, false, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                               (const EnvConst<T>*)c->d_const, c->st, d_mask);
-        return;
-    }
-    if (c->cfg.balance_object == TG_BALANCE_BALL_ON_PLATE) {
-        hipLaunchKernelGGL((k_reset_body<T, 0, true>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                           (const EnvConst<T>*)c->d_const, c->st, d_mask);
-        return;
-    }
-    hipLaunchKernelGGL((k_reset_body<T, 0>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st, d_mask);
+    // fast: a reset that covered env 0 has been enqueued before this one - the template is there when this launch runs (spinning_plate: always there
+    // by then, tg_create)
+    const bool fast = c->tmpl_ready, ball = c->cfg.balance_object == TG_BALANCE_BALL_ON_PLATE;
+    if (c->cfg.balance_object == TG_BALANCE_SPINNING_PLATE) launch_env(c, fast ? k_reset_body<T, 0, false, true, true> : k_reset_body<T, 0, false, false, true>, 0, d_mask);
+    else if (fast) launch_env(c, ball ? k_reset_body<T, 0, true, true> : k_reset_body<T, 0, false, true>, 0, d_mask);
+    else launch_env(c, ball ? k_reset_body<T, 0, true> : k_reset_body<T, 0>, 0, d_mask);
+}
+static void launch_reset_body(tg_ctx* c, const uint8_t* d_mask) {
+    if (c->cfg.physics_dtype == TG_PHYSICS_F64) launch_reset_body_t<double>(c, d_mask);
+    else launch_reset_body_t<float>(c, d_mask);
+}
+// StepFamily::LanePush / LaneRoll: the solver's tables live in dynamic LDS
+template <typename T> constexpr size_t kLaneContactLds = (size_t)kPushLdsWords * 64 * sizeof(T);
+static void launch_reset_lane_contact(tg_ctx* c, const uint8_t* d_mask) {
+    if (c->plan.family == StepFamily::LaneRoll)
+        dispatch(c, [&](auto p) { using T = typename decltype(p)::T; launch_env(c, k_reset_roll<T, decltype(p)::TOPO>, kLaneContactLds<T>, d_mask); });
+    else
+        dispatch(c, [&](auto p) { using T = typename decltype(p)::T; launch_env(c, k_reset_push<T, decltype(p)::TOPO>, kLaneContactLds<T>, d_mask); });
+}
+static void launch_bank_refill(tg_ctx* c, int phase) {
+    dispatch(c, [&](auto p) { launch_env_on(c, c->bank_stream, 1, k_bank_refill<typename decltype(p)::T, decltype(p)::TOPO>, 0, c->bk, c->aux, phase); });
 }
 
-template <typename T, int TOPO> static void launch_step_push_t(tg_ctx* c, const float* d_actions) {
-    const int n = c->cfg.num_envs;
-    constexpr size_t lds_bytes = (size_t)kPushLdsWords * 64 * sizeof(T);
-    static bool attr_set = false;   // one context per (process, GPU): set once per instantiation
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_push<T, TOPO, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_push<T, TOPO, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        attr_set = true;
-    }
-    if (c->cfg.control_mode == TG_CONTROL_TCP_POSITION)
-        hipLaunchKernelGGL((k_step_push<T, TOPO, true>), dim3((n + 63) / 64), dim3(64), lds_bytes, c->stream, (const DevRobot<T>*)c->d_robot,
-                           (const EnvConst<T>*)c->d_const, c->st, d_actions);
+// ---- steps
+// StepFamily::LaneBody
+template <typename T> static void launch_step_body_t(tg_ctx* c, const float* d_actions) {
+    const bool pos = c->cfg.control_mode == TG_CONTROL_TCP_POSITION;
+    if (c->cfg.balance_object == TG_BALANCE_BALL_ON_PLATE) launch_env(c, pos ? k_step_body<T, 0, true, true> : k_step_body<T, 0, false, true>, 0, d_actions);
+    else launch_env(c, pos ? k_step_body<T, 0, true> : k_step_body<T, 0, false>, 0, d_actions);
+}
+static void launch_step_body(tg_ctx* c, const float* d_actions) {
+    if (c->cfg.physics_dtype == TG_PHYSICS_F64) launch_step_body_t<double>(c, d_actions);
+    else launch_step_body_t<float>(c, d_actions);
+}
+static void launch_step_lane_contact(tg_ctx* c, const float* d_actions) {
+    const bool vel = c->cfg.control_mode != TG_CONTROL_TCP_POSITION;
+    if (c->plan.family == StepFamily::LaneRoll)
+        dispatch(c, [&](auto p) {
+            using T = typename decltype(p)::T;
+            launch_env(c, vel ? k_step_roll<T, decltype(p)::TOPO, false> : k_step_roll<T, decltype(p)::TOPO, true>, kLaneContactLds<T>, d_actions);
+        });
     else
-        hipLaunchKernelGGL((k_step_push<T, TOPO, false>), dim3((n + 63) / 64), dim3(64), lds_bytes, c->stream, (const DevRobot<T>*)c->d_robot,
-                           (const EnvConst<T>*)c->d_const, c->st, d_actions);
+        dispatch(c, [&](auto p) {
+            using T = typename decltype(p)::T;
+            launch_env(c, vel ? k_step_push<T, decltype(p)::TOPO, false> : k_step_push<T, decltype(p)::TOPO, true>, kLaneContactLds<T>, d_actions);
+        });
 }
-template <typename T, int TOPO> static void launch_step_roll_t(tg_ctx* c, const float* d_actions) {
-    const int n = c->cfg.num_envs;
-    constexpr size_t lds_bytes = (size_t)kPushLdsWords * 64 * sizeof(T);
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_roll<T, TOPO, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_step_roll<T, TOPO, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        attr_set = true;
-    }
-    if (c->cfg.control_mode == TG_CONTROL_TCP_POSITION)
-        hipLaunchKernelGGL((k_step_roll<T, TOPO, true>), dim3((n + 63) / 64), dim3(64), lds_bytes, c->stream, (const DevRobot<T>*)c->d_robot,
-                           (const EnvConst<T>*)c->d_const, c->st, d_actions);
-    else
-        hipLaunchKernelGGL((k_step_roll<T, TOPO, false>), dim3((n + 63) / 64), dim3(64), lds_bytes, c->stream, (const DevRobot<T>*)c->d_robot,
-                           (const EnvConst<T>*)c->d_const, c->st, d_actions);
-}
-template <typename T, int TOPO> static void launch_reset_roll_t(tg_ctx* c, const uint8_t* d_mask) {
-    const int n = c->cfg.num_envs;
-    constexpr size_t lds_bytes = (size_t)kPushLdsWords * 64 * sizeof(T);
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reset_roll<T, TOPO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); attr_set = true; }
-    hipLaunchKernelGGL((k_reset_roll<T, TOPO>), dim3((n + 63) / 64), dim3(64), lds_bytes, c->stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st, d_mask);
-}
-template <typename T, int TOPO> static void launch_reset_push_t(tg_ctx* c, const uint8_t* d_mask) {
-    const int n = c->cfg.num_envs;
-    constexpr size_t lds_bytes = (size_t)kPushLdsWords * 64 * sizeof(T);
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_reset_push<T, TOPO>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes); attr_set = true; }
-    hipLaunchKernelGGL((k_reset_push<T, TOPO>), dim3((n + 63) / 64), dim3(64), lds_bytes, c->stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st, d_mask);
+// StepFamily::LaneArm.  reset_phase >= 0: the finished envs' auto-reset (k_reset's body, phase `reset_phase`) runs inside the step's launch
+// (k_step<T, TOPO, true> / k_step_quad<T, true>; the UR5 in f64 only - on the MG400 a step is 0.7 ms of full ticks and the launch it would save
+// is noise); returns whether it did
+static bool launch_step_arm(tg_ctx* c, const float* d_actions, int reset_phase) {
+    bool reset_inlined = false;
+    dispatch(c, [&](auto p) {
+        using T = typename decltype(p)::T;
+        constexpr int TOPO = decltype(p)::TOPO;
+        if (c->cfg.control_mode == TG_CONTROL_TCP_POSITION) { launch_env(c, k_step_pos<T, TOPO>, 0, d_actions); return; }
+        if constexpr (TOPO == 0 && std::is_same<T, double>::value) {   // (f64 physics: the configuration every BASELINE config runs)
+            reset_inlined = reset_phase >= 0;
+            if (c->plan.envs_per_wave == 16) {   // a quad of lanes per env: 4 n threads
+                if (reset_inlined) launch_env_on(c, c->stream, 4, k_step_quad<T, true>, 0, d_actions, reset_phase, bank_dev(c));
+                else launch_env_on(c, c->stream, 4, k_step_quad<T, false>, 0, d_actions, -1, nullptr);
+                return;
+            }
+            if (reset_inlined) { launch_env(c, k_step<T, TOPO, true>, 0, d_actions, reset_phase, bank_dev(c)); return; }
+        }
+        launch_env(c, k_step<T, TOPO>, 0, d_actions, -1, nullptr);
+    });
+    return reset_inlined;
 }
 
 static void render(tg_ctx* c, const uint8_t* d_mask, bool save_prev) {
@@ -443,8 +406,6 @@ static void render_fused(tg_ctx* c) {
 }
 
 
-
-// env.reset() for the masked envs: task randomisation, (surface generation), robot reset.
 // tg_sample_actions: element i of draw `counter`: 24 random bits of splitmix64 over (seed, counter, i) -> lo + (hi - lo) u, u in [0, 1)
 __global__ void k_sample_actions(int total, uint64_t seed, uint64_t counter, float lo, float hi, float* __restrict__ out, unsigned long long* tl) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -474,63 +435,55 @@ __global__ void k_sample_actions_ctr(int total, unsigned long long* __restrict__
     }
 }
 
-template <typename T, int TOPO> static void launch_oracle_obs_t(tg_ctx* c, int dim, float* dst) {
-    const int n = c->cfg.num_envs;
-    hipLaunchKernelGGL((k_oracle_obs<T, TOPO>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st, dim, dst);
-}
-static int oracle_dim(const tg_ctx* c);
-static void oracle_draw(tg_ctx* c, float* dst) {
-    const int d = oracle_dim(c);
-#define CALL(T, TOPO) launch_oracle_obs_t<T, TOPO>(c, d, dst)
-    TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-}
-static int oracle_dim(const tg_ctx* c) {
-    switch (c->cfg.env_kind) {
-        case TG_ENV_EDGE_FOLLOW: return 10;
-        case TG_ENV_SURFACE_FOLLOW_AUTO: return 20;
-        case TG_ENV_OBJECT_BALANCE: return 26;
-        case TG_ENV_OBJECT_PUSH: return 30;
-        default: return 34;
-    }
-}
-template <typename T, int TOPO> static void launch_scene_xf_t(tg_ctx* c, const uint8_t* d_mask) {
-    const int n = c->cfg.num_envs;
-    hipLaunchKernelGGL((k_scene_xf<T, TOPO>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st, c->scene_view, d_mask, c->d_scene_xf, c->d_scene_spheres, c->scene.n_spheres);
-}
-// get_visual_obs for the whole batch (or the masked envs; save_prev keeps their previous image as the terminal observation)
-static void scene_draw(tg_ctx* c, const uint8_t* d_mask, bool save_prev) {
-    Timer t(c, 4);
-#define CALL(T, TOPO) launch_scene_xf_t<T, TOPO>(c, d_mask)
-    TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-    launch_scene(c->scene, c->d_scene_xf, c->cfg.num_envs, d_mask, c->d_vis, save_prev ? c->d_vis_term : nullptr, c->stream);
-}
-
 // Which mapping steps the contact envs (tg_config.contact_mapping).  One wavefront per env takes the whole register file of its SIMD (one
 // wavefront per SIMD, 1024 per chip), so its rate is flat in the batch size - object_push: 0.52 M env-steps/s from 1024 envs up - while one
 // lane per env scales with the batch until the chip is full: measured 1024 envs 2.0 ms (wave) against 7.4 ms (lane) per step, 2048 envs
 // 3.9 against 7.5, 4096 envs 7.8 against 7.7, 8192 envs 15.5 against 7.9 (1.04 M env-steps/s).
-static bool use_contact_wave(const tg_ctx* c) {
-    if (c->cfg.env_kind != TG_ENV_OBJECT_PUSH && c->cfg.env_kind != TG_ENV_OBJECT_ROLL && c->cfg.env_kind != TG_ENV_OBJECT_BALANCE) return false;
-    if (c->cfg.physics_dtype != TG_PHYSICS_F64) return false;
-    if (c->cfg.env_kind == TG_ENV_OBJECT_BALANCE && c->cfg.balance_object == TG_BALANCE_BALL_ON_PLATE) return false;   // lane mapping only (tg_create refuses WAVE)
-    if (c->cfg.contact_mapping == TG_CONTACT_MAP_LANE) return false;
-    if (c->cfg.contact_mapping == TG_CONTACT_MAP_WAVE || c->cfg.narrowphase != TG_NARROW_CLOSED_FORM) return true;
-    return c->cfg.num_envs < 4096;
+static bool wants_contact_wave(const tg_config& cfg) {
+    if (cfg.contact_mapping == TG_CONTACT_MAP_LANE) return false;
+    if (cfg.contact_mapping == TG_CONTACT_MAP_WAVE || cfg.narrowphase != TG_NARROW_CLOSED_FORM) return true;
+    return cfg.num_envs < 4096;
 }
 
-// Contact-free arm tasks on the wave mapping (k_step_arm_wave: every tick a full tick on the env's own wavefront).  Measured on an MI355X at
-// 1024 envs it does NOT beat the lane mapping: UR5 literal solver k_step 0.886 ms against 0.512 ms, MG400 (surface_follow-v2) 1.05 ms against
-// ~0.95 ms - a wave64 instruction costs its 4 cycles whether 6 or 64 lanes do useful work, so the 150 sweeps (~190 issue cycles each on the
-// wave mapping, 144 for 64 envs on the lane mapping) and the dynamics are a wash between 1024 half-empty wavefronts and 16 full ones
-// (DESIGN.md 4.1g).  Kept for TG_CONTACT_MAP_WAVE only; AUTO stays on the lane mapping.
-static bool use_arm_wave(const tg_ctx* c) {
-    if (c->cfg.env_kind != TG_ENV_EDGE_FOLLOW && c->cfg.env_kind != TG_ENV_SURFACE_FOLLOW_AUTO) return false;
-    if (c->cfg.physics_dtype != TG_PHYSICS_F64 || c->cfg.control_mode != TG_CONTROL_TCP_VELOCITY) return false;
-    return c->cfg.contact_mapping == TG_CONTACT_MAP_WAVE;
+// The one place that says which kernel family steps and resets a context (StepFamily, tg_ctx.hpp): tg_create stores the answer in c->plan
+// before it sets up the reset bank, and nothing else tests dtype, topology or control mode for it.  What is instantiated, and within which LDS
+// and hull limits, is asked of the can_run_* predicate beside each launcher; a configuration that asks for a wave mapping it cannot have (the
+// MG400's object_roll, pyramid friction, f32, a tip hull too large for LDS, position control in object_balance) is a lane context from here on.
+static StepPlan choose_step_plan(const tg_ctx* c) {
+    const tg_config& cfg = c->cfg;
+    const int topo = c->robot.topology;
+    const bool f64 = cfg.physics_dtype == TG_PHYSICS_F64, velocity = cfg.control_mode == TG_CONTROL_TCP_VELOCITY;
+    StepPlan p;
+    switch (cfg.env_kind) {
+        case TG_ENV_OBJECT_BALANCE:
+            if (cfg.balance_object == TG_BALANCE_SPINNING_PLATE) p.family = StepFamily::Spin;   // (one wavefront per env, tg_spin.hip: its only mapping)
+            else if (cfg.balance_object != TG_BALANCE_BALL_ON_PLATE /* lane mapping only: tg_create refuses WAVE */ && wants_contact_wave(cfg) &&
+                     can_run_body_wave(cfg.physics_dtype, topo, cfg.control_mode)) {
+                p.family = StepFamily::BodyWave;
+                p.draws_actions = true;
+            } else p.family = StepFamily::LaneBody;
+            break;
+        case TG_ENV_OBJECT_PUSH:
+        case TG_ENV_OBJECT_ROLL:
+            if (wants_contact_wave(cfg) && can_run_contact_wave(cfg.env_kind, cfg.physics_dtype, topo, cfg.cone_friction, cfg.n_tip_verts, cfg.narrowphase))
+                p.family = StepFamily::ContactWave;
+            else p.family = cfg.env_kind == TG_ENV_OBJECT_PUSH ? StepFamily::LanePush : StepFamily::LaneRoll;
+            break;
+        default:   // edge_follow, surface_follow
+            // Contact-free arm tasks on the wave mapping (k_step_arm_wave: every tick a full tick on the env's own wavefront).  Measured on an
+            // MI355X at 1024 envs it does NOT beat the lane mapping: UR5 literal solver k_step 0.886 ms against 0.512 ms, MG400 (surface_follow-v2)
+            // 1.05 ms against ~0.95 ms - a wave64 instruction costs its 4 cycles whether 6 or 64 lanes do useful work, so the 150 sweeps (~190
+            // issue cycles each on the wave mapping, 144 for 64 envs on the lane mapping) and the dynamics are a wash between 1024 half-empty
+            // wavefronts and 16 full ones.  Kept for TG_CONTACT_MAP_WAVE only; AUTO stays on the lane mapping.
+            if (cfg.contact_mapping == TG_CONTACT_MAP_WAVE && can_run_arm_wave(cfg.physics_dtype, cfg.control_mode)) { p.family = StepFamily::ArmWave; break; }
+            p.family = StepFamily::LaneArm;
+            p.draws_actions = velocity;                          // k_step / k_step_quad; not k_step_pos
+            p.fusable = cfg.env_kind == TG_ENV_EDGE_FOLLOW && f64 && velocity;
+            if (f64 && topo == 0 && velocity && c->kstep_quad) p.envs_per_wave = 16;   // k_step_quad: the UR5's f64 step on a quad of lanes per env
+            break;
+    }
+    if (p.family == StepFamily::ArmWave || p.family == StepFamily::ContactWave || p.family == StepFamily::BodyWave || p.family == StepFamily::Spin) p.envs_per_wave = 1;
+    return p;
 }
 
 // The env step as ONE launch (tg_fused.hip: k_step_render, the wavefront that steps an env draws it): edge_follow with the lane-mapped k_step
@@ -541,8 +494,7 @@ static bool use_arm_wave(const tg_ctx* c) {
 // other down by 1.7x).  Byte-identical images / rewards / dones (tests/test_gpu_fused_step.py).
 bool use_fused_step(const tg_ctx* c) {
     if (c->fused_pref <= 0) return false;   // TG_FUSED_AUTO: off (see above)
-    if (c->cfg.env_kind != TG_ENV_EDGE_FOLLOW || c->cfg.physics_dtype != TG_PHYSICS_F64 || c->cfg.control_mode != TG_CONTROL_TCP_VELOCITY) return false;
-    if (use_arm_wave(c) || c->scene_every_step || c->oracle_every_step) return false;   // (the scene / oracle draws sit between the step and the reset)
+    if (!c->plan.fusable || c->scene_every_step || c->oracle_every_step) return false;   // (the scene / oracle draws sit between the step and the reset)
     if (c->stim.kind != 0 || c->stim.n_tris > 32 || c->stim.fills_view || c->rp.blockmax == nullptr || c->rp.tmpl == nullptr) return false;
     if (c->rp.W % 128 != 0 || c->rp.H % 128 != 0) return false;
     static const bool blocks_off = getenv("TG_NO_BLOCK_RASTER") != nullptr;
@@ -556,66 +508,39 @@ static int surf_gen_mode(const tg_ctx* c) {
            : (c->cfg.movement_mode == TG_SMOVE_YZ || c->cfg.movement_mode == TG_SMOVE_YZRX) ? TG_SURF_SIMPLEX_1D : TG_SURF_SIMPLEX_2D;
 }
 
+// env.reset() for the masked envs: task randomisation, (surface generation), robot reset - by the kernels of the context's step family.
 // bank: the auto-reset of tg_step with the reset bank on (k_reset mode 1): finished envs take their precomputed state, the rest (aux.late)
 // are reset by the launches that follow
-static void reset_sequence(tg_ctx* c, const uint8_t* d_mask, bool bank = false, bool phase1_done = false /* surface_follow: k_step<.., true> has run phase 1 */) {
+static int reset_sequence(tg_ctx* c, const uint8_t* d_mask, bool bank = false, bool phase1_done = false /* surface_follow: k_step<.., true> has run phase 1 */) {
     Timer t(c, 2);
-    if (bank && c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) {
-        if (!phase1_done) {
-#define CALL(T, TOPO) launch_reset_t<T, TOPO>(c, d_mask, 1, true)
-            TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
+    const tg_config& cfg = c->cfg;
+    switch (c->plan.family) {
+        case StepFamily::BodyWave: case StepFamily::LaneBody: case StepFamily::Spin:
+            launch_reset_body(c, d_mask);
+            return 0;
+        case StepFamily::ContactWave: {
+            const int rc = launch_reset_contact_wave(cfg.env_kind, cfg.physics_dtype, c->robot.topology, cfg.cone_friction, cfg.num_envs, cfg.n_tip_verts, c->stream, c->d_robot,
+                                                     c->d_const, c->st, d_mask, cfg.narrowphase);
+            if (rc != 0) return fail(-3, "k_reset_contact_wave is not built for this context (internal: the step family was chosen wrongly)");
+            break;
         }
-        launch_gen_surface(c->cfg.num_envs, c->aux.late, c->st.noise_seed, c->cfg.surf_rows, c->cfg.surf_cols, c->cfg.surf_interp,
-                           c->cfg.surf_height_range, c->cfg.surf_center_z, surf_gen_mode(c), c->st.heights, c->st.surf_zoff, c->stream,
-                           c->aux.swapped, c->st.hsel);
-#define CALL(T, TOPO) launch_reset_t<T, TOPO>(c, c->aux.late, 2, true)
-        TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-        return;
+        case StepFamily::LanePush: case StepFamily::LaneRoll:
+            launch_reset_lane_contact(c, d_mask);
+            break;
+        case StepFamily::LaneArm: case StepFamily::ArmWave:
+            if (cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) {
+                const uint8_t* rest = bank ? c->aux.late : d_mask;   // with the bank: the envs that found no entry
+                if (!phase1_done) launch_reset_arm(c, d_mask, 1, bank);
+                launch_gen_surface(cfg.num_envs, rest, c->st.noise_seed, cfg.surf_rows, cfg.surf_cols, cfg.surf_interp, cfg.surf_height_range, cfg.surf_center_z,
+                                   surf_gen_mode(c), c->st.heights, c->st.surf_zoff, c->stream, bank ? c->aux.swapped : nullptr, c->st.hsel);
+                launch_reset_arm(c, rest, 2, bank);
+            } else launch_reset_arm(c, d_mask, 0, bank);
+            return 0;
     }
-    if (bank && c->cfg.env_kind == TG_ENV_EDGE_FOLLOW) {
-#define CALL(T, TOPO) launch_reset_t<T, TOPO>(c, d_mask, 0, true)
-        TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-        return;
-    }
-    if (c->cfg.env_kind == TG_ENV_OBJECT_BALANCE) {
-        if (c->cfg.physics_dtype == TG_PHYSICS_F64) launch_reset_body_t<double>(c, d_mask);
-        else launch_reset_body_t<float>(c, d_mask);
-    } else if (c->cfg.env_kind == TG_ENV_OBJECT_ROLL) {
-        if (!(use_contact_wave(c) && launch_reset_contact_wave(c->cfg.env_kind, c->cfg.physics_dtype, c->robot.topology, c->cfg.cone_friction, c->cfg.num_envs,
-                                                               c->cfg.n_tip_verts, c->stream, c->d_robot, c->d_const, c->st, d_mask) == 0)) {
-#define CALL(T, TOPO) launch_reset_roll_t<T, TOPO>(c, d_mask)
-            TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-        }
-    } else if (c->cfg.env_kind == TG_ENV_OBJECT_PUSH) {
-        if (!(use_contact_wave(c) && launch_reset_contact_wave(c->cfg.env_kind, c->cfg.physics_dtype, c->robot.topology, c->cfg.cone_friction, c->cfg.num_envs,
-                                                               c->cfg.n_tip_verts, c->stream, c->d_robot, c->d_const, c->st, d_mask, c->cfg.narrowphase) == 0)) {
-#define CALL(T, TOPO) launch_reset_push_t<T, TOPO>(c, d_mask)
-            TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-        }
-        if (c->cfg.traj_type == TG_TRAJ_SIMPLEX)
-            launch_gen_traj(c->cfg.num_envs, d_mask, c->st.noise_seed, c->cfg.traj_n_points, c->cfg.traj_spacing, c->cfg.traj_max_perturb,
-                            c->cfg.traj_init_offset, c->cfg.reset_goal_id, c->st.traj, c->st.feature, c->stream);
-    } else if (c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) {
-        if (!phase1_done) {
-#define CALL(T, TOPO) launch_reset_t<T, TOPO>(c, d_mask, 1)
-            TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-        }
-        launch_gen_surface(c->cfg.num_envs, d_mask, c->st.noise_seed, c->cfg.surf_rows, c->cfg.surf_cols, c->cfg.surf_interp,
-                           c->cfg.surf_height_range, c->cfg.surf_center_z, surf_gen_mode(c), c->st.heights, c->st.surf_zoff, c->stream, nullptr, c->st.hsel);
-#define CALL(T, TOPO) launch_reset_t<T, TOPO>(c, d_mask, 2)
-        TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-    } else {
-#define CALL(T, TOPO) launch_reset_t<T, TOPO>(c, d_mask, 0)
-        TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-    }
+    if (cfg.env_kind == TG_ENV_OBJECT_PUSH && cfg.traj_type == TG_TRAJ_SIMPLEX)
+        launch_gen_traj(cfg.num_envs, d_mask, c->st.noise_seed, cfg.traj_n_points, cfg.traj_spacing, cfg.traj_max_perturb, cfg.traj_init_offset, cfg.reset_goal_id,
+                        c->st.traj, c->st.feature, c->stream);
+    return 0;
 }
 
 // The refill of the reset bank: after the step's launches, on the bank's low-priority stream, paced by a marker on the step stream (so the host
@@ -661,19 +586,11 @@ static void bank_refill(tg_ctx* c) {
         }
     }
     if (c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) {
-#define CALL(T, TOPO) launch_bank_refill_t<T, TOPO>(c, 1)
-        TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
+        launch_bank_refill(c, 1);
         launch_gen_surface(c->cfg.num_envs, c->aux.need, c->bk.noise_seed, c->cfg.surf_rows, c->cfg.surf_cols, c->cfg.surf_interp,
                            c->cfg.surf_height_range, c->cfg.surf_center_z, surf_gen_mode(c), c->bk.heights, c->bk.surf_zoff, c->bank_stream, nullptr, c->bk.hsel);
-#define CALL(T, TOPO) launch_bank_refill_t<T, TOPO>(c, 2)
-        TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-    } else {
-#define CALL(T, TOPO) launch_bank_refill_t<T, TOPO>(c, 0)
-        TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-    }
+        launch_bank_refill(c, 2);
+    } else launch_bank_refill(c, 0);
     if (c->bank_mode == 2) {   // tests: every finished env finds its entry ready (the step stream waits for the refill)
         (void)hipEventRecord(c->ev_bank_done, c->bank_stream);
         (void)hipStreamWaitEvent(c->stream, c->ev_bank_done, 0);
@@ -1034,6 +951,9 @@ static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sen
     if (const char* e = getenv("TG_FUSED_STEP")) c->fused_pref = e[0] == '0' ? -1 : 1;   // A/B switch (tests, measurements)
     c->no_inline_reset = getenv("TG_NO_INLINE_RESET") != nullptr;
     { const char* e = getenv("TG_KSTEP_QUAD"); c->kstep_quad = !(e != nullptr && e[0] == '0'); }
+    c->plan = choose_step_plan(c);
+    if (c->plan.family == StepFamily::Spin && !can_run_spin(cfg->physics_dtype, robot->topology, cfg->spin_n_dish))
+        return fail(-3, "tg_create: object_balance spinning_plate has no step kernel for this combination (k_step_spin: f64, the UR5 chain, dish hull <= 1152 vertices)");
 #ifdef TG_TL_STAMPS
     c->rp.tl = s.tl;
 #endif
@@ -1047,8 +967,7 @@ static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sen
         int want = cfg->reset_bank == TG_BANK_OFF ? 0 : cfg->reset_bank == TG_BANK_SYNC ? 2 : 1;
         if (const char* e = getenv("TG_RESET_BANK")) want = (e[0] == '0') ? 0 : (e[0] == 's') ? 2 : 1;
         if (const char* e = getenv("TG_RESET_BANK_EVERY")) { const int k = atoi(e); if (k >= 1) c->bank_every = k; }
-        const bool kind_ok = cfg->env_kind == TG_ENV_EDGE_FOLLOW || cfg->env_kind == TG_ENV_SURFACE_FOLLOW_AUTO;
-        if (want && kind_ok && cfg->auto_reset && !use_arm_wave(c)) {
+        if (want && cfg->auto_reset && c->plan.family == StepFamily::LaneArm) {
             State& b = c->bk;
             auto grab = [&](auto*& ptr, size_t bytes) -> int {
                 void* p_ = nullptr;
@@ -1181,7 +1100,7 @@ int tg_reset(tg_ctx* c, const uint8_t* host_mask) {
         TG_HIP(hipMemcpyAsync(c->d_mask, host_mask, c->cfg.num_envs, hipMemcpyHostToDevice, c->stream));
         dmask = c->d_mask;
     }
-    reset_sequence(c, dmask);
+    if (int rc = reset_sequence(c, dmask)) return rc;
     if (c->cfg.env_kind == TG_ENV_OBJECT_BALANCE && c->st.reset_tmpl != nullptr && (host_mask == nullptr || host_mask[0] != 0))
         c->tmpl_ready = true;   // env 0 went through the full reset just enqueued: later launches (stream order) take the template-only kernel
     hipLaunchKernelGGL(tg::k_episode_clear, dim3((c->cfg.num_envs + 255) / 256), dim3(256), 0, c->stream, c->st.ep_return, dmask, c->cfg.num_envs);
@@ -1199,61 +1118,64 @@ int tg_reset(tg_ctx* c, const uint8_t* host_mask) {
 // against ~2.8 us per kernel launch.  The steps here are 2 - 4 launches (the policy draw and the auto-reset live inside k_step), so the stream
 // wins up to ~16 launches per step: headline 42.2 -> 37.2 us per step (24.3 -> 27.5 M env-steps/s), episodes out of phase 47.8 -> 42.8 us,
 // surface_follow-v0 100.4 -> 95.8 us, object_balance 117 -> 112.5 us (tools/desync_rate.py, same box, alternating).
-static void enqueue_step(tg_ctx* c, const float* d_act) {
+static int enqueue_step(tg_ctx* c, const float* d_act) {
     if (c->profile) { Timer t(c, 5); }   // an empty event pair: what every per-kernel figure of this mode carries on top of its kernel
-    bool reset_inlined = false;          // object_balance: k_step_body_wave has reset its finished envs itself
+    const tg_config& cfg = c->cfg;
+    const bool draws_between = c->scene_every_step || c->oracle_every_step;   // scene / oracle observations show the pre-reset state
     if (use_fused_step(c)) {
         Timer t(c, 1);
-        const int rc = launch_step_render(c->robot.topology, c->cfg.num_envs, c->stream, c->d_robot, c->d_const, c->st, d_act, c->cfg.auto_reset,
-                                          c->bank_mode != 0 ? c->d_bank : nullptr, raster_params(c), c->stim, c->d_nodef_dep, c->d_nodef_gray, c->d_border, obs_buf(c),
-                                          c->d_term);
-        if (rc == 0) return;
+        const int rc = launch_step_render(c->robot.topology, cfg.num_envs, c->stream, c->d_robot, c->d_const, c->st, d_act, cfg.auto_reset, bank_dev(c), raster_params(c),
+                                          c->stim, c->d_nodef_dep, c->d_nodef_gray, c->d_border, obs_buf(c), c->d_term);
+        if (rc != 0) return fail(-3, "k_step_render is not built for this context (internal: use_fused_step and launch_step_render disagree)");
+        return 0;
     }
+    bool reset_inlined = false;          // the step's launch has reset its finished envs itself (surface_follow: run their reset's phase 1)
     {
         Timer t(c, 0);
-        if (c->cfg.env_kind == TG_ENV_OBJECT_BALANCE) {
-            // the reset of finished envs inside the step's launch: auto-reset with a valid template, the pole, no scene / oracle draw between
-            // the step and the reset (they show the pre-reset state)
-            const int inline_reset = (c->cfg.auto_reset && c->st.reset_tmpl != nullptr && c->tmpl_ready && c->cfg.balance_object == TG_BALANCE_POLE &&
-                                      !c->scene_every_step && !c->oracle_every_step && !c->no_inline_reset) ? 1 : 0;
-            if (c->cfg.balance_object == TG_BALANCE_SPINNING_PLATE) {
-                (void)launch_step_spin(c->cfg.physics_dtype, c->robot.topology, c->cfg.control_mode, c->cfg.num_envs, c->cfg.spin_n_dish, c->stream, c->d_robot,
-                                       c->d_const, c->st, d_act);   // one wavefront per env (tg_spin.hip); tg_create has checked the combination
-            } else if (use_contact_wave(c) && launch_step_body_wave(c->cfg.physics_dtype, c->robot.topology, c->cfg.control_mode, c->cfg.num_envs, c->stream, c->d_robot,
-                                                             c->d_const, c->st, d_act, inline_reset) == 0) {
-                reset_inlined = inline_reset != 0;
-                // one wavefront per env: the env's own licence, full ticks on the wave mapping (tg_contact_wave.hip)
-            } else if (c->cfg.physics_dtype == TG_PHYSICS_F64) launch_step_body_t<double>(c, d_act);
-            else launch_step_body_t<float>(c, d_act);
-        } else if (use_contact_wave(c) && launch_step_contact_wave(c->cfg.env_kind, c->cfg.physics_dtype, c->robot.topology, c->cfg.control_mode, c->cfg.cone_friction,
-                                                                  c->cfg.num_envs, c->cfg.n_tip_verts, c->stream, c->d_robot, c->d_const, c->st, d_act, c->cfg.narrowphase) == 0) {
-            // object_push / object_roll with one wavefront per env (tg_contact_wave.hip)
-        } else if (c->cfg.env_kind == TG_ENV_OBJECT_ROLL) {
-#define CALL(T, TOPO) launch_step_roll_t<T, TOPO>(c, d_act)
-            TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-        } else if (c->cfg.env_kind == TG_ENV_OBJECT_PUSH) {
-#define CALL(T, TOPO) launch_step_push_t<T, TOPO>(c, d_act)
-            TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-        } else if (use_arm_wave(c) && launch_step_arm_wave(c->cfg.physics_dtype, c->robot.topology, c->cfg.control_mode, c->cfg.num_envs, c->stream, c->d_robot,
-                                                           c->d_const, c->st, d_act) == 0) {
-            // edge_follow / surface_follow with one wavefront per env (tg_contact_wave.hip: k_step_arm_wave)
-        } else {
-            // edge_follow / surface_follow: the auto-reset's first launch (edge_follow: its only one) inside the step kernel, unless something
-            // is drawn or checked between the step and the reset (scene / oracle observations, the broadphase guard: the pre-reset state)
-            const bool fused_render_path = c->cfg.env_kind == TG_ENV_EDGE_FOLLOW || c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO;
-            // Only with the reset bank on: the swap-in is a copy, identical wherever it runs; a reset computed on the spot (IK, blocking move) inside
-            // k_step<.., true> is another instantiation of reset_env than k_reset's, and the compiler contracts each one's f64 expressions into FMAs
-            // on its own - measured: one build in which a bank-off rollout differed from the k_reset launch's in the last bits of q (12 grey levels
-            // of one image sum).  With the bank off the reset is 90 us on the spot anyway, and it stays the k_reset launch.  (With the bank on, an env
-            // that finds no entry - none in any measured rollout - is reset on the spot in here, as k_step_render does.)
-            const int reset_phase = (c->cfg.auto_reset && fused_render_path && c->bank_mode != 0 && !c->no_inline_reset && !c->scene_every_step && !c->oracle_every_step && !(c->d_bp && c->bp_every_step))
-                                        ? (c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO ? 1 : 0) : -1;
-#define CALL(T, TOPO) reset_inlined = launch_step_t<T, TOPO>(c, d_act, reset_phase)
-            TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
+        int rc = 0;
+        const char* kernel = "";
+        switch (c->plan.family) {
+            case StepFamily::Spin:       // one wavefront per env (tg_spin.hip)
+                kernel = "k_step_spin";
+                rc = launch_step_spin(cfg.physics_dtype, c->robot.topology, cfg.control_mode, cfg.num_envs, cfg.spin_n_dish, c->stream, c->d_robot, c->d_const, c->st, d_act);
+                break;
+            case StepFamily::BodyWave:   // one wavefront per env: the env's own licence, full ticks on the wave mapping (tg_contact_wave.hip)
+                // the reset of finished envs inside the step's launch: auto-reset with a valid template, the pole, no scene / oracle draw between
+                // the step and the reset
+                reset_inlined = cfg.auto_reset && c->st.reset_tmpl != nullptr && c->tmpl_ready && cfg.balance_object == TG_BALANCE_POLE && !draws_between && !c->no_inline_reset;
+                kernel = "k_step_body_wave";
+                rc = launch_step_body_wave(cfg.physics_dtype, c->robot.topology, cfg.control_mode, cfg.num_envs, c->stream, c->d_robot, c->d_const, c->st, d_act,
+                                           reset_inlined ? 1 : 0);
+                break;
+            case StepFamily::LaneBody:
+                launch_step_body(c, d_act);
+                break;
+            case StepFamily::ContactWave:   // object_push / object_roll with one wavefront per env (tg_contact_wave.hip)
+                kernel = "k_step_contact_wave";
+                rc = launch_step_contact_wave(cfg.env_kind, cfg.physics_dtype, c->robot.topology, cfg.control_mode, cfg.cone_friction, cfg.num_envs, cfg.n_tip_verts, c->stream,
+                                              c->d_robot, c->d_const, c->st, d_act, cfg.narrowphase);
+                break;
+            case StepFamily::LanePush: case StepFamily::LaneRoll:
+                launch_step_lane_contact(c, d_act);
+                break;
+            case StepFamily::ArmWave:    // edge_follow / surface_follow with one wavefront per env (tg_contact_wave.hip: k_step_arm_wave)
+                kernel = "k_step_arm_wave";
+                rc = launch_step_arm_wave(cfg.physics_dtype, c->robot.topology, cfg.control_mode, cfg.num_envs, c->stream, c->d_robot, c->d_const, c->st, d_act);
+                break;
+            case StepFamily::LaneArm: {
+                // edge_follow / surface_follow: the auto-reset's first launch (edge_follow: its only one) inside the step kernel, unless something
+                // is drawn or checked between the step and the reset (scene / oracle observations, the broadphase guard: the pre-reset state)
+                // Only with the reset bank on: the swap-in is a copy, identical wherever it runs; a reset computed on the spot (IK, blocking move) inside
+                // k_step<.., true> is another instantiation of reset_env than k_reset's, and the compiler contracts each one's f64 expressions into FMAs
+                // on its own - measured: one build in which a bank-off rollout differed from the k_reset launch's in the last bits of q (12 grey levels
+                // of one image sum).  With the bank off the reset is 90 us on the spot anyway, and it stays the k_reset launch.  (With the bank on, an env
+                // that finds no entry - none in any measured rollout - is reset on the spot in here, as k_step_render does.)
+                const bool in_step = cfg.auto_reset && c->bank_mode != 0 && !c->no_inline_reset && !draws_between && !(c->d_bp && c->bp_every_step);
+                reset_inlined = launch_step_arm(c, d_act, !in_step ? -1 : cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO ? 1 : 0);
+                break;
+            }
         }
+        if (rc != 0) return fail(-3, std::string(kernel) + " is not built for this context (internal: the step family was chosen wrongly)");
     }
     // broadphase guard: the state the step kernel left, before any reset teleports a finished env (tg_set_broadphase, every_step)
     if (c->d_bp && c->bp_every_step) (void)launch_broadphase(c->cfg.physics_dtype, c->robot.topology, c->cfg.num_envs, c->stream, c->d_robot, c->d_bp, c->st, c->d_bp_out, c->d_bp_tot);
@@ -1264,8 +1186,10 @@ static void enqueue_step(tg_ctx* c, const float* d_act) {
     if (c->cfg.auto_reset && (c->cfg.env_kind == TG_ENV_EDGE_FOLLOW || c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO || (c->cfg.env_kind == TG_ENV_OBJECT_BALANCE && c->st.reset_tmpl != nullptr))) {
         // (object_balance with the reset template: k_reset_body is a few microseconds - teleport, draws, one forward kinematics - so it runs
         //  in line like edge_follow's, without the fork / join of the branch below and without the masked second render: 236 -> 20x us per step)
-        if (!reset_inlined) reset_sequence(c, c->st.done, c->bank_mode != 0); // k_reset keeps the terminal camera transform of the envs it resets
-        else if (c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) reset_sequence(c, c->st.done, c->bank_mode != 0, true);   // phase 1 ran inside k_step
+        // (k_reset keeps the terminal camera transform of the envs it resets; surface_follow with the reset in the step: phase 1 ran inside k_step)
+        if (!reset_inlined || c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) {
+            if (int rc = reset_sequence(c, c->st.done, c->bank_mode != 0, reset_inlined)) return rc;
+        }
         render_fused(c);               // one launch draws the terminal and the post-reset observations
     } else if (c->cfg.auto_reset && c->aux_stream) {
         // object_balance: a pole falls somewhere in the batch on nearly every step, and its reset (rest pose, blocking move, settling: a
@@ -1277,8 +1201,9 @@ static void enqueue_step(tg_ctx* c, const float* d_act) {
         {
             hipStream_t main_stream = c->stream;
             c->stream = c->aux_stream;
-            reset_sequence(c, c->st.done);
+            const int rc = reset_sequence(c, c->st.done);
             c->stream = main_stream;
+            if (rc != 0) return rc;
         }
         (void)hipEventRecord(c->ev_join, c->aux_stream);
         {
@@ -1291,12 +1216,13 @@ static void enqueue_step(tg_ctx* c, const float* d_act) {
     } else {
         render(c, nullptr, false);
         if (c->cfg.auto_reset) {
-            reset_sequence(c, c->st.done, c->bank_mode != 0);
+            if (int rc = reset_sequence(c, c->st.done, c->bank_mode != 0)) return rc;
             render(c, c->st.done, true);   // terminal observation is saved, then the post-reset observation is drawn
         }
     }
     if (c->scene_every_step && c->cfg.auto_reset) scene_draw(c, c->st.done, true);
     if (c->oracle_every_step && c->cfg.auto_reset) oracle_draw(c, c->d_oracle);                       // after the resets: what the next step starts from
+    return 0;
 }
 
 int tg_step(tg_ctx* c, const float* actions, int32_t on_device) {
@@ -1307,7 +1233,7 @@ int tg_step(tg_ctx* c, const float* actions, int32_t on_device) {
         TG_HIP(hipMemcpyAsync(c->d_actions, actions, (size_t)c->cfg.num_envs * c->act_dim * sizeof(float), hipMemcpyHostToDevice, c->stream));
         d_act = c->d_actions;
     }
-    enqueue_step(c, d_act);
+    if (int rc = enqueue_step(c, d_act)) return rc;
     if (int rc = stack_update(c, kStackStep, c->st.done)) return rc;
     bank_refill(c);
     TG_HIP(hipGetLastError());
@@ -1337,18 +1263,15 @@ int tg_step_random(tg_ctx* c, uint64_t seed, uint64_t first_draw, int32_t restar
     };
     // the lane-mapped k_step (edge_follow / surface_follow, TCP_velocity_control) draws its own actions: no sampler launch at all - a dependent
     // kernel costs its dispatch floor whatever it computes (profiles/r4_exp_reset_launch.txt)
-    // (round 5: so does object_balance's k_step_body_wave - the conditions of launch_step_body_wave)
-    const bool in_kernel = ((c->cfg.env_kind == TG_ENV_EDGE_FOLLOW || c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) &&
-                            c->cfg.control_mode == TG_CONTROL_TCP_VELOCITY && !use_arm_wave(c)) ||
-                           (c->cfg.env_kind == TG_ENV_OBJECT_BALANCE && use_contact_wave(c) && c->cfg.physics_dtype == TG_PHYSICS_F64 &&
-                            c->robot.topology == 0 && c->cfg.control_mode == TG_CONTROL_TCP_VELOCITY && !use_fused_step(c));
+    // (round 5: so does object_balance's k_step_body_wave)
+    const bool in_kernel = c->plan.draws_actions;
     struct DrawScope {                   // c->st carries the counter only while this call enqueues
         tg_ctx* c; bool on;
         DrawScope(tg_ctx* c_, bool on_) : c(c_), on(on_) { if (on) { c->st.draw = c->d_draw; c->st.act_out = c->d_actions; } }
         ~DrawScope() { if (on) { c->st.draw = nullptr; c->st.act_out = nullptr; } }
     } scope(c, in_kernel);
     if (!in_kernel) sample();
-    enqueue_step(c, c->d_actions);
+    if (int rc = enqueue_step(c, c->d_actions)) return rc;
     if (int rc = stack_update(c, kStackStep, c->st.done)) return rc;
     bank_refill(c);
     TG_HIP(hipGetLastError());
@@ -1436,11 +1359,7 @@ int tg_get_obs_oracle(tg_ctx* c, void** p, int32_t* dim) {
     TG_ENTER(c);
     const int d = oracle_dim(c);
     if (!c->d_oracle) TG_HIP(hipMalloc(&c->d_oracle, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
-    if (!c->oracle_every_step) {     // (enabled: tg_step / tg_reset have already written it)
-#define CALL(T, TOPO) launch_oracle_obs_t<T, TOPO>(c, d, c->d_oracle)
-        TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
-    }
+    if (!c->oracle_every_step) oracle_draw(c, c->d_oracle);     // (enabled: tg_step / tg_reset have already written it)
     TG_HIP(hipGetLastError());
     *p = c->d_oracle;
     if (dim) *dim = d;

@@ -3,17 +3,6 @@
 #include "tg_ctx.hpp"
 
 namespace tg {
-template <typename T, int TOPO> static void launch_refresh_t(tg_ctx* c) {
-    const int n = c->cfg.num_envs;
-    hipLaunchKernelGGL((k_refresh<T, TOPO>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st);
-}
-
-template <typename T, int TOPO> static void launch_refresh_rpy_t(tg_ctx* c) {
-    const int n = c->cfg.num_envs;
-    hipLaunchKernelGGL((k_refresh_rpy<T, TOPO>), dim3((n + 63) / 64), dim3(64), 0, c->stream, (const DevRobot<T>*)c->d_robot,
-                       (const EnvConst<T>*)c->d_const, c->st);
-}
 // tg_pack_done_rows: one 256-thread workgroup per env; a finished env's slot is the number of finished envs before it (a prefix count over the
 // done flags: deterministic ascending order, no atomics), workgroup 0 also writes the header.  Everything goes straight into pinned host memory.
 // tg_get_state, surface_follow: each env's live surface (State::hsel) out of the three thirds, [n][cells]; workgroup x = env
@@ -135,7 +124,7 @@ int tg_get_broadphase_totals(tg_ctx* c, int64_t* checks, int64_t* pairs, int64_t
 int tg_get_step_mode(tg_ctx* c, int32_t* mode, int32_t* envs_per_wavefront) {
     if (!c || !mode) return fail(-1, "NULL argument");
     *mode = use_fused_step(c) ? 1 : 0;
-    if (envs_per_wavefront) *envs_per_wavefront = *mode ? fused_envs_per_wave(c->cfg.num_envs) : c->step_envs_per_wave;
+    if (envs_per_wavefront) *envs_per_wavefront = *mode ? fused_envs_per_wave(c->cfg.num_envs) : c->plan.envs_per_wave;
     return 0;
 }
 
@@ -192,9 +181,7 @@ int tg_get_state(tg_ctx* c, const tg_state_view* v) {
     if (v->qd && (rc = fetch_soa(c, c->st.qd, nd, v->qd))) return rc;
     if (v->qd_target && (rc = fetch_soa(c, c->st.qd_target, nd, v->qd_target))) return rc;
     if (v->tcp_rpy && (c->cfg.env_kind == TG_ENV_EDGE_FOLLOW || c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO)) {   // k_step leaves this read-back to be recomputed on demand
-#define CALL(T, TOPO) launch_refresh_rpy_t<T, TOPO>(c)
-        TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
+        dispatch(c, [&](auto p) { launch_env(c, k_refresh_rpy<typename decltype(p)::T, decltype(p)::TOPO>, 0); });
     }
     if (v->tcp_pos && (rc = fetch_soa(c, c->st.tcp_pos, 3, v->tcp_pos))) return rc;
     if (v->tcp_rpy && (rc = fetch_soa(c, c->st.tcp_rpy, 3, v->tcp_rpy))) return rc;
@@ -290,9 +277,7 @@ int tg_set_joint_state(tg_ctx* c, const double* q, const double* qd) {
     TG_HIP(hipMemcpyAsync(c->st.q, a.data(), a.size() * 8, hipMemcpyHostToDevice, c->stream));
     TG_HIP(hipMemcpyAsync(c->st.qd, b.data(), b.size() * 8, hipMemcpyHostToDevice, c->stream));
     TG_HIP(hipMemsetAsync(c->st.licence, 0, (size_t)n * 4, c->stream));   // new configuration: full solve and exact sines / cosines next
-#define CALL(T, TOPO) launch_refresh_t<T, TOPO>(c)
-    TG_DISPATCH(c->cfg.physics_dtype, c->robot.topology, CALL);
-#undef CALL
+    dispatch(c, [&](auto p) { launch_env(c, k_refresh<typename decltype(p)::T, decltype(p)::TOPO>, 0); });
     launch_render(raster_params(c), c->stim, c->st.stim_xform, 1, c->cfg.num_envs, nullptr, c->d_nodef_dep, c->d_nodef_gray, c->d_border, obs_buf(c),
                   nullptr, nullptr, nullptr, nullptr, c->stream);          // the observation of the new configuration
     TG_HIP(hipStreamSynchronize(c->stream));

@@ -2260,59 +2260,67 @@ __global__ __launch_bounds__(64) void k_reset_contact_wave(const DevRobot<T>* __
     else finish_push<T, TOPO>(m, c, st, env, q, b, 0, false);
 }
 
+// dynamic LDS of the push / roll kernels: env state + per-tick hand-offs + the tip-core hull (+ the GJK / EPA scratch and the manifold)
+constexpr size_t contact_lds_words(int shape, int n_tip, int narrowphase) { return (size_t)(kLHull + (shape == 1 ? 0 : 3 * n_tip) + (narrowphase ? kXWords : 0)); }
+
 template <typename T, int TOPO, int SHAPE>
-int launch_wave_t(int control_mode, int cone, int n, int n_tip, hipStream_t stream, const void* d_robot, const void* d_const, const State& st, const float* d_actions,
-                  int narrowphase = 0) {
-    const size_t lds_bytes = (size_t)(kLHull + (SHAPE == 1 ? 0 : 3 * n_tip) + (narrowphase ? kXWords : 0)) * sizeof(T);   // env state + per-tick hand-offs + the tip-core hull
-    if (lds_bytes > 60 * 1024) return -1;                                                   // (1089 vertices: 31 KB; 4 envs per CU fit 160 KB)
-    if (!cone) return -1;                // pyramid friction (enableConeFriction = 0, not what the reference sets): the lane-per-env kernels
+void launch_wave_t(int control_mode, int n, int n_tip, hipStream_t stream, const void* d_robot, const void* d_const, const State& st, const float* d_actions,
+                   int narrowphase = 0) {
+    const size_t lds_bytes = contact_lds_words(SHAPE, n_tip, narrowphase) * sizeof(T);
     if constexpr (SHAPE == 0 && sizeof(T) == 8) {
         if (narrowphase) {               // GJK / EPA + manifold: the four-slot variant of the same kernel
-            if (n_tip > 64 * narrow::kSlots) return -1;
             if (control_mode == TG_CONTROL_TCP_POSITION)
                 hipLaunchKernelGGL((k_step_contact_wave<T, TOPO, true, 0, true, 4>), dim3(n), dim3(64), lds_bytes, stream, (const DevRobot<T>*)d_robot,
                                    (const EnvConst<T>*)d_const, st, d_actions);
             else
                 hipLaunchKernelGGL((k_step_contact_wave<T, TOPO, false, 0, true, 4>), dim3(n), dim3(64), lds_bytes, stream, (const DevRobot<T>*)d_robot,
                                    (const EnvConst<T>*)d_const, st, d_actions);
-            return 0;
+            return;
         }
     }
-    if (narrowphase) return -1;
     if (control_mode == TG_CONTROL_TCP_POSITION)
         hipLaunchKernelGGL((k_step_contact_wave<T, TOPO, true, SHAPE, true>), dim3(n), dim3(64), lds_bytes, stream, (const DevRobot<T>*)d_robot,
                            (const EnvConst<T>*)d_const, st, d_actions);
     else
         hipLaunchKernelGGL((k_step_contact_wave<T, TOPO, false, SHAPE, true>), dim3(n), dim3(64), lds_bytes, stream, (const DevRobot<T>*)d_robot,
                            (const EnvConst<T>*)d_const, st, d_actions);
-    return 0;
 }
 
 template <typename T, int TOPO, int SHAPE>
-int launch_reset_wave_t(int cone, int n, int n_tip, hipStream_t stream, const void* d_robot, const void* d_const, const State& st, const uint8_t* d_mask,
-                        int narrowphase = 0) {
-    const size_t lds_bytes = (size_t)(kLHull + (SHAPE == 1 ? 0 : 3 * n_tip) + (narrowphase ? kXWords : 0)) * sizeof(T);
-    if (lds_bytes > 60 * 1024 || !cone) return -1;
+void launch_reset_wave_t(int n, int n_tip, hipStream_t stream, const void* d_robot, const void* d_const, const State& st, const uint8_t* d_mask, int narrowphase = 0) {
+    const size_t lds_bytes = contact_lds_words(SHAPE, n_tip, narrowphase) * sizeof(T);
     if constexpr (SHAPE == 0 && sizeof(T) == 8) {
         if (narrowphase) {
-            if (n_tip > 64 * narrow::kSlots) return -1;
             hipLaunchKernelGGL((k_reset_contact_wave<T, TOPO, 0, true, 4>), dim3(n), dim3(64), lds_bytes, stream, (const DevRobot<T>*)d_robot,
                                (const EnvConst<T>*)d_const, st, d_mask, 0);
-            return 0;
+            return;
         }
     }
-    if (narrowphase) return -1;
     const int optimistic = getenv("TG_LITERAL_RESET") == nullptr ? 1 : 0;             // TG_LITERAL_RESET: every reset tick a full contact tick (A/B, tests)
     hipLaunchKernelGGL((k_reset_contact_wave<T, TOPO, SHAPE, true>), dim3(n), dim3(64), lds_bytes, stream, (const DevRobot<T>*)d_robot,
                        (const EnvConst<T>*)d_const, st, d_mask, optimistic);
-    return 0;
 }
 
 }  // namespace
 
+// ---- what is instantiated (tg_contact_wave.h): each predicate is the one place that knows, and its launcher's first line
+bool can_run_contact_wave(int env_kind, int physics_dtype, int topology, int cone_friction, int n_tip_verts, int narrowphase) {
+    if (physics_dtype != TG_PHYSICS_F64) return false;      // the f32 variant keeps the lane-per-env mapping
+    if (!cone_friction) return false;                       // pyramid friction (enableConeFriction = 0, not what the reference sets): the lane-per-env kernels
+    if (env_kind != TG_ENV_OBJECT_PUSH && env_kind != TG_ENV_OBJECT_ROLL) return false;
+    const int shape = env_kind == TG_ENV_OBJECT_ROLL ? 1 : 0;
+    if (shape == 1 && (topology != 0 || narrowphase)) return false;   // the marble: UR5, closed forms
+    if (narrowphase && n_tip_verts > 64 * narrow::kSlots) return false;
+    return contact_lds_words(shape, shape == 1 ? 0 : n_tip_verts, narrowphase) * sizeof(double) <= 60 * 1024;   // (1089 vertices: 31 KB; 4 envs per CU fit 160 KB)
+}
+bool can_run_body_wave(int physics_dtype, int topology, int control_mode) {
+    return physics_dtype == TG_PHYSICS_F64 && topology == 0 && control_mode == TG_CONTROL_TCP_VELOCITY;
+}
+bool can_run_arm_wave(int physics_dtype, int control_mode) { return physics_dtype == TG_PHYSICS_F64 && control_mode == TG_CONTROL_TCP_VELOCITY; }
+
 int launch_step_body_wave(int physics_dtype, int topology, int control_mode, int num_envs, hipStream_t stream, const void* d_robot, const void* d_const,
                           const State& st, const float* d_actions, int inline_reset) {
-    if (physics_dtype != TG_PHYSICS_F64 || topology != 0 || control_mode != TG_CONTROL_TCP_VELOCITY) return -1;
+    if (!can_run_body_wave(physics_dtype, topology, control_mode)) return -3;
     hipLaunchKernelGGL((k_step_body_wave<double, 0>), dim3(num_envs), dim3(64), (size_t)kLHull * sizeof(double), stream, (const DevRobot<double>*)d_robot,
                        (const EnvConst<double>*)d_const, st, d_actions, inline_reset);
     return 0;
@@ -2320,7 +2328,7 @@ int launch_step_body_wave(int physics_dtype, int topology, int control_mode, int
 
 int launch_step_arm_wave(int physics_dtype, int topology, int control_mode, int num_envs, hipStream_t stream, const void* d_robot, const void* d_const,
                          const State& st, const float* d_actions) {
-    if (physics_dtype != TG_PHYSICS_F64 || control_mode != TG_CONTROL_TCP_VELOCITY) return -1;
+    if (!can_run_arm_wave(physics_dtype, control_mode)) return -3;
     if (topology == 0)
         hipLaunchKernelGGL((k_step_arm_wave<double, 0>), dim3(num_envs), dim3(64), (size_t)kLHull * sizeof(double), stream, (const DevRobot<double>*)d_robot,
                            (const EnvConst<double>*)d_const, st, d_actions);
@@ -2332,15 +2340,11 @@ int launch_step_arm_wave(int physics_dtype, int topology, int control_mode, int 
 
 int launch_reset_contact_wave(int env_kind, int physics_dtype, int topology, int cone_friction, int num_envs, int n_tip_verts, hipStream_t stream,
                               const void* d_robot, const void* d_const, const State& st, const uint8_t* d_mask, int narrowphase) {
-    if (physics_dtype != TG_PHYSICS_F64) return -1;
-    if (env_kind == TG_ENV_OBJECT_PUSH) {
-        if (topology == 0) return launch_reset_wave_t<double, 0, 0>(cone_friction, num_envs, n_tip_verts, stream, d_robot, d_const, st, d_mask, narrowphase);
-        return launch_reset_wave_t<double, 1, 0>(cone_friction, num_envs, n_tip_verts, stream, d_robot, d_const, st, d_mask, narrowphase);
-    }
-    if (narrowphase) return -1;
-    if (env_kind == TG_ENV_OBJECT_ROLL && topology == 0)
-        return launch_reset_wave_t<double, 0, 1>(cone_friction, num_envs, 0, stream, d_robot, d_const, st, d_mask);
-    return -1;
+    if (!can_run_contact_wave(env_kind, physics_dtype, topology, cone_friction, n_tip_verts, narrowphase)) return -3;
+    if (env_kind == TG_ENV_OBJECT_ROLL) launch_reset_wave_t<double, 0, 1>(num_envs, 0, stream, d_robot, d_const, st, d_mask);
+    else if (topology == 0) launch_reset_wave_t<double, 0, 0>(num_envs, n_tip_verts, stream, d_robot, d_const, st, d_mask, narrowphase);
+    else launch_reset_wave_t<double, 1, 0>(num_envs, n_tip_verts, stream, d_robot, d_const, st, d_mask, narrowphase);
+    return 0;
 }
 
 int launch_step_contact_wave(int env_kind, int physics_dtype, int topology, int control_mode, int cone_friction, int num_envs, int n_tip_verts, hipStream_t stream,
@@ -2359,15 +2363,11 @@ int launch_step_contact_wave(int env_kind, int physics_dtype, int topology, int 
         }
     }
 #endif
-    if (physics_dtype != TG_PHYSICS_F64) return -1;       // the f32 variant keeps the lane-per-env mapping
-    if (env_kind == TG_ENV_OBJECT_PUSH) {
-        if (topology == 0) return launch_wave_t<double, 0, 0>(control_mode, cone_friction, num_envs, n_tip_verts, stream, d_robot, d_const, st, d_actions, narrowphase);
-        return launch_wave_t<double, 1, 0>(control_mode, cone_friction, num_envs, n_tip_verts, stream, d_robot, d_const, st, d_actions, narrowphase);
-    }
-    if (narrowphase) return -1;
-    if (env_kind == TG_ENV_OBJECT_ROLL && topology == 0)
-        return launch_wave_t<double, 0, 1>(control_mode, cone_friction, num_envs, 0, stream, d_robot, d_const, st, d_actions);
-    return -1;
+    if (!can_run_contact_wave(env_kind, physics_dtype, topology, cone_friction, n_tip_verts, narrowphase)) return -3;
+    if (env_kind == TG_ENV_OBJECT_ROLL) launch_wave_t<double, 0, 1>(control_mode, num_envs, 0, stream, d_robot, d_const, st, d_actions);
+    else if (topology == 0) launch_wave_t<double, 0, 0>(control_mode, num_envs, n_tip_verts, stream, d_robot, d_const, st, d_actions, narrowphase);
+    else launch_wave_t<double, 1, 0>(control_mode, num_envs, n_tip_verts, stream, d_robot, d_const, st, d_actions, narrowphase);
+    return 0;
 }
 
 }  // namespace tg

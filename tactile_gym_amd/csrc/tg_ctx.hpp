@@ -1,5 +1,5 @@
-// tg_ctx.hpp - what the translation units of the C ABI share: the context behind a tg_ctx*, error reporting, the device-selection / dispatch macros,
-// the host -> device translation of a robot description.  tg_api.hip (configuration, creation, the step / reset launch sequences, the reset
+// tg_ctx.hpp - what the translation units of the C ABI share: the context behind a tg_ctx*, error reporting, the device-selection macro, the
+// dispatch on the physics variant and the env-kernel launch helper, the host -> device translation of a robot description.  tg_api.hip (configuration, creation, the step / reset launch sequences, the reset
 // bank), tg_api_state.hip (state read-back, inspection, profiling, the broadphase guard's entry points) and tg_api_ops.hip (the
 // context-free function-level entry points) include it; round 6 split them out of one 2 400-line file.
 #pragma once
@@ -186,6 +186,26 @@ static int check_robot(const tg_robot* r) {
     if (r->tcp_link < 0 || r->tcp_link >= r->ndof || r->sensor_link < 0 || r->sensor_link >= r->ndof) return fail(-1, "frame link out of range");
     return 0;
 }
+
+// Which kernels step and reset a context's envs.  Fixed by tg_config, the robot and the stimulus: tg_create evaluates choose_step_plan
+// (tg_api.hip) once and every reader - the step and reset sequences, tg_step_random, the reset bank's set-up, tg_get_step_mode - takes the
+// answer from tg_ctx::plan, so an env's step and reset cannot end up on different mappings.
+enum class StepFamily {
+    LaneArm,       // edge_follow / surface_follow, a lane per env: k_step / k_step_quad (a quad of lanes) / k_step_pos; resets by k_reset
+    ArmWave,       // ... a wavefront per env: k_step_arm_wave (contact_mapping = wave only); resets by k_reset, no reset bank
+    ContactWave,   // object_push / object_roll, a wavefront per env: k_step_contact_wave / k_reset_contact_wave
+    LanePush,      // object_push, a lane per env: k_step_push / k_reset_push
+    LaneRoll,      // object_roll, a lane per env: k_step_roll / k_reset_roll
+    BodyWave,      // object_balance, a wavefront per env: k_step_body_wave; resets by k_reset_body (or inside the step)
+    LaneBody,      // object_balance, a lane per env: k_step_body / k_reset_body
+    Spin,          // object_balance spinning_plate, a wavefront per env: k_step_spin; resets by k_reset_body
+};
+struct StepPlan {
+    StepFamily family = StepFamily::LaneArm;
+    int envs_per_wave = 64;        // envs one wavefront of the step kernel steps: 64 a lane per env, 16 k_step_quad, 1 the wave families (tg_get_step_mode)
+    bool draws_actions = false;    // the step kernel samples tg_step_random's actions itself (State::draw): no sampler launch
+    bool fusable = false;          // k_step_render (tg_fused.hip) is built for this context; whether a step takes it: use_fused_step, per call
+};
 }  // namespace tg
 
 struct tg_ctx {
@@ -265,7 +285,7 @@ struct tg_ctx {
     // one launch per step (tg_fused.hip): -1 = TG_FUSED_STEP=0, 1 = TG_FUSED_STEP=1, 0 = where it measures faster (use_fused_step)
     int fused_pref = 0;
     bool no_inline_reset = false;  // TG_NO_INLINE_RESET (tests, measurements): finished envs are reset by the k_reset launch, never inside the step's launch
-    int step_envs_per_wave = 0;    // envs per wavefront of the last arm step launch: 16 k_step_quad, 64 k_step / k_step_pos (tg_get_step_mode)
+    tg::StepPlan plan;             // which kernels step and reset the envs (choose_step_plan, at the end of tg_create)
     bool kstep_quad = true;        // TG_KSTEP_QUAD=0 (tests, measurements): the UR5's f64 step runs k_step (a lane per env) instead of k_step_quad (a quad per env)
     // profiling by the kernels' own clock (tg_kt.hpp): per-wavefront {start, end} slots, reduced after every timed scope into {ticks, scopes}
     unsigned long long* d_kt = nullptr;          // [kt_slots][2]
@@ -301,14 +321,35 @@ static void drain_events(tg_ctx* c) {
     }
     c->events.clear();
 }
-#define TG_DISPATCH(ctx_dtype, ctx_topo, CALL)                                               \
-    do {                                                                                     \
-        if ((ctx_dtype) == TG_PHYSICS_F64) {                                                 \
-            if ((ctx_topo) == 0) { CALL(double, 0); } else { CALL(double, 1); }              \
-        } else {                                                                             \
-            if ((ctx_topo) == 0) { CALL(float, 0); } else { CALL(float, 1); }                \
-        }                                                                                    \
-    } while (0)
+// The physics variant of a context as a type: dispatch(c, f) calls the generic callable f with Phys<double | float, 0 | 1> by
+// tg_config.physics_dtype and the robot's topology (0 the UR5's serial chain, 1 the MG400's tree).
+template <typename T_, int TOPO_> struct Phys { using T = T_; static constexpr int TOPO = TOPO_; };
+template <typename F> static inline void dispatch(const tg_ctx* c, F&& f) {
+    if (c->cfg.physics_dtype == TG_PHYSICS_F64) {
+        if (c->robot.topology == 0) f(Phys<double, 0>{}); else f(Phys<double, 1>{});
+    } else {
+        if (c->robot.topology == 0) f(Phys<float, 0>{}); else f(Phys<float, 1>{});
+    }
+}
+// One launch of an env kernel K(const DevRobot<T>*, const EnvConst<T>*, State, args...) over the context's envs: workgroups of one wavefront,
+// `lanes_per_env` lanes per env (1: grid (n + 63) / 64; 4: k_step_quad's quads).  T comes from the kernel's signature.  A kernel with dynamic
+// LDS has its limit raised the first time it is launched (one context per process and GPU: once per kernel).
+template <typename T, typename... P, typename... A>
+static void launch_env_on(tg_ctx* c, hipStream_t stream, int lanes_per_env, void (*kernel)(const DevRobot<T>*, const EnvConst<T>*, State, P...), size_t lds_bytes,
+                          A... args) {
+    if (lds_bytes != 0) {
+        static std::vector<const void*> raised;
+        if (std::find(raised.begin(), raised.end(), (const void*)kernel) == raised.end()) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            raised.push_back((const void*)kernel);
+        }
+    }
+    const dim3 grid((unsigned)(((size_t)lanes_per_env * c->cfg.num_envs + 63) / 64));
+    hipLaunchKernelGGL(kernel, grid, dim3(64), lds_bytes, stream, (const DevRobot<T>*)c->d_robot, (const EnvConst<T>*)c->d_const, c->st, static_cast<P>(args)...);
+}
+template <typename K, typename... A> static void launch_env(tg_ctx* c, K kernel, size_t lds_bytes, A... args) {   // a lane per env, on the context's stream
+    launch_env_on(c, c->stream, 1, kernel, lds_bytes, args...);
+}
 
 static inline uint8_t* obs_buf(const tg_ctx* c) { return c->obs_sel == 0 ? c->d_obs : c->obs_ext[c->obs_sel - 1]; }   // where this step's images go
 static inline RasterParams raster_params(const tg_ctx* c) {   // ... and the changed-block record that belongs to that buffer

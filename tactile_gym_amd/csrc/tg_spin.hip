@@ -494,9 +494,13 @@ __global__ __launch_bounds__(64) void k_step_spin(const DevRobot<double>* __rest
 
 }  // namespace
 
+bool can_run_spin(int physics_dtype, int topology, int n_dish) {
+    return physics_dtype == TG_PHYSICS_F64 && topology == 0 && n_dish > 0 && n_dish <= 64 * narrow::kSlots;
+}
+
 int launch_step_spin(int physics_dtype, int topology, int control_mode, int num_envs, int n_dish, hipStream_t stream, const void* d_robot,
                      const void* d_const, const State& st, const float* d_actions) {
-    if (physics_dtype != TG_PHYSICS_F64 || topology != 0 || n_dish <= 0 || n_dish > 64 * narrow::kSlots) return -1;
+    if (!can_run_spin(physics_dtype, topology, n_dish)) return -3;
     const size_t lds_bytes = (size_t)(SL<6>::HULL + 3 * n_dish) * sizeof(double);
     if (control_mode == TG_CONTROL_TCP_POSITION)
         hipLaunchKernelGGL((k_step_spin<0, true>), dim3(num_envs), dim3(64), lds_bytes, stream, (const DevRobot<double>*)d_robot,

@@ -134,6 +134,31 @@ def test_spinning_plate_oracle_observation_and_auto_reset():
     venv.close()
 
 
+def test_spinning_plate_random_step_draws_its_actions():
+    """step_random_async: k_step_spin does not draw actions itself, so the sampler launch must run - the step's actions are draw k of
+    sample_actions(seed, k), new in every step, and the arm moves as in a step() with those actions."""
+    import torch
+    import tactile_gym_amd as tg
+    n = 4
+    kw = dict(num_envs=n, max_steps=20, image_size=[64, 64], env_modes=SPIN_MODES, seed=77, auto_reset=False)
+    a_env, b_env = tg.make_vec("object_balance-v0", **kw), tg.make_vec("object_balance-v0", **kw)
+    a_env.reset(); b_env.reset()
+    want = torch.empty(n, a_env.act_dim, device="cuda", dtype=torch.float32)
+    prev = None
+    for k in range(3):
+        a_env.step_random_async(9, k, restart=(k == 0))
+        a_env.step_wait()
+        used = a_env.actions_torch().cpu().numpy().copy()
+        b_env.sample_actions(want, 9, k + 1)
+        torch.cuda.synchronize()
+        assert np.array_equal(used, want.cpu().numpy()), k
+        assert prev is None or not np.array_equal(used, prev), k
+        prev = used
+        b_env.step(used)
+        assert np.array_equal(a_env.get_state()["q"], b_env.get_state()["q"]), k
+    a_env.close(); b_env.close()
+
+
 def test_spinning_plate_refuses_what_is_not_built():
     import tactile_gym_amd as tg
     with pytest.raises(Exception):
