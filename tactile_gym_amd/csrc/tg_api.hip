@@ -640,26 +640,14 @@ static int stack_update(tg_ctx* c, int mode, const uint8_t* flag) {
     return 0;
 }
 
-extern "C" {
+// ------------------------------------------------------------------------------------------------ tg_create, step by step
+// create_impl runs the functions below in order.  Everything the host can hold against a configuration is said by check_config, before the
+// device is touched; every later step allocates through dev_alloc / dev_upload (tg_ctx.hpp) and, on an error, simply returns: tg_create's guard
+// destroys the context, and the context's list frees whatever had been made.  None of them names a kernel (the note above oracle_dim).
+struct HostConsts { std::vector<uint8_t> robot, env; int act_dim = 0; };   // DevRobot<T> / EnvConst<T> in the configuration's physics_dtype, as bytes
 
-const char* tg_last_error(void) { return g_err.c_str(); }
-int tg_abi_version(void) { return TG_ABI_VERSION; }
-
-static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sensor* sensor, const tg_mesh* stim, tg_ctx** out);
-int tg_create(const tg_config* cfg, const tg_robot* robot, const tg_sensor* sensor, const tg_mesh* stim, tg_ctx** out) {
-    if (!out) return fail(-1, "tg_create: NULL argument");
-    *out = nullptr;
-    const int rc = create_impl(cfg, robot, sensor, stim, out);
-    if (rc != 0 && *out) {               // a failure half way: release the context and every device allocation made so far
-        const std::string keep = g_err;
-        tg_destroy(*out);
-        *out = nullptr;
-        g_err = keep;
-    }
-    return rc;
-}
-static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sensor* sensor, const tg_mesh* stim, tg_ctx** out) {
-    if (!cfg || !robot || !sensor || !out) return fail(-1, "tg_create: NULL argument");
+static int check_config(const tg_config* cfg, const tg_robot* robot, const tg_sensor* sensor, const tg_mesh* stim, HostConsts& hc) {
+    if (!cfg || !robot || !sensor) return fail(-1, "tg_create: NULL argument");
     if (cfg->abi_version != TG_ABI_VERSION) return fail(-1, "tg_create: ABI version mismatch");
     if (cfg->env_kind != TG_ENV_EDGE_FOLLOW && cfg->env_kind != TG_ENV_SURFACE_FOLLOW_AUTO && cfg->env_kind != TG_ENV_OBJECT_BALANCE &&
         cfg->env_kind != TG_ENV_OBJECT_PUSH && cfg->env_kind != TG_ENV_OBJECT_ROLL)
@@ -689,334 +677,297 @@ static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sen
             return fail(-1, "tg_create: narrowphase GJK / EPA runs on the wave mapping (f64, cone friction, contact_mapping auto or wave)");
         if (cfg->n_tip_verts > 1152) return fail(-1, "tg_create: narrowphase GJK / EPA holds at most 1152 hull vertices");
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return fail(-3, "tg_create: no HIP device visible — the tactile-env step has no CPU fallback");
-    TG_HIP(hipSetDevice(cfg->device));
-    tg_ctx* c = new tg_ctx();
-    *out = c;                            // owned by tg_create's guard from here on
-    c->cfg = *cfg; c->robot = *robot; c->H = H; c->W = W;
+    // the robot and the env constants in the physics dtype (build_env_const holds the per-env checks: movement mode, masses, tip_link ...)
+    auto build = [&](auto zero) -> int {
+        using T = decltype(zero);
+        DevRobot<T> dr; EnvConst<T> ec;
+        build_dev_robot(*robot, dr);
+        dr.res_thr = (T)(cfg->solver_residual_threshold > 0.0 ? cfg->solver_residual_threshold : 0.0);
+        if (int rc = build_env_const(*cfg, *sensor, *robot, ec)) return rc;
+        hc.act_dim = ec.act_dim;
+        hc.robot.assign((const uint8_t*)&dr, (const uint8_t*)&dr + sizeof dr);
+        hc.env.assign((const uint8_t*)&ec, (const uint8_t*)&ec + sizeof ec);
+        return 0;
+    };
+    return cfg->physics_dtype == TG_PHYSICS_F64 ? build(0.0) : build(0.0f);
+}
+
+static int create_streams(tg_ctx* c) {
     TG_HIP(hipStreamCreate(&c->own_stream));
-    if (cfg->env_kind == TG_ENV_OBJECT_BALANCE) {
+    if (c->cfg.env_kind == TG_ENV_OBJECT_BALANCE) {
         TG_HIP(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
         TG_HIP(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)); TG_HIP(hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
     }
     c->stream = c->own_stream;
-    const int n = cfg->num_envs;
-    const size_t npix = (size_t)H * W;
-    if (cfg->physics_dtype == TG_PHYSICS_F64) {
-        DevRobot<double> dr; EnvConst<double> ec;
-        build_dev_robot(*robot, dr);
-        dr.res_thr = cfg->solver_residual_threshold > 0.0 ? cfg->solver_residual_threshold : 0.0;
-        if (int rc = build_env_const(*cfg, *sensor, *robot, ec)) { delete c; return rc; }
-        c->act_dim = ec.act_dim;
-        TG_HIP(hipMalloc(&c->d_robot, sizeof dr)); TG_HIP(hipMemcpy(c->d_robot, &dr, sizeof dr, hipMemcpyHostToDevice));
-        TG_HIP(hipMalloc(&c->d_const, sizeof ec)); TG_HIP(hipMemcpy(c->d_const, &ec, sizeof ec, hipMemcpyHostToDevice));
-    } else {
-        DevRobot<float> dr; EnvConst<float> ec;
-        build_dev_robot(*robot, dr);
-        dr.res_thr = cfg->solver_residual_threshold > 0.0 ? (float)cfg->solver_residual_threshold : 0.0f;
-        if (int rc = build_env_const(*cfg, *sensor, *robot, ec)) { delete c; return rc; }
-        c->act_dim = ec.act_dim;
-        TG_HIP(hipMalloc(&c->d_robot, sizeof dr)); TG_HIP(hipMemcpy(c->d_robot, &dr, sizeof dr, hipMemcpyHostToDevice));
-        TG_HIP(hipMalloc(&c->d_const, sizeof ec)); TG_HIP(hipMemcpy(c->d_const, &ec, sizeof ec, hipMemcpyHostToDevice));
-    }
+    return 0;
+}
+
+static int upload_consts(tg_ctx* c, const HostConsts& hc) {
+    c->act_dim = hc.act_dim;
+    if (dev_upload(c, c->d_robot, hc.robot.data(), hc.robot.size()) || dev_upload(c, c->d_const, hc.env.data(), hc.env.size())) return -2;
+    return 0;
+}
+
+// what every env kind has
+static int alloc_env_state(tg_ctx* c) {
     State& s = c->st;
-    const size_t nd = (size_t)TG_MAX_DOF * n;
-    TG_HIP(hipMalloc(&s.q, nd * 8)); TG_HIP(hipMalloc(&s.qd, nd * 8)); TG_HIP(hipMalloc(&s.qd_target, nd * 8));
-    TG_HIP(hipMalloc(&s.tcp_pos, 3 * n * 8)); TG_HIP(hipMalloc(&s.tcp_rpy, 3 * n * 8));
-    TG_HIP(hipMalloc(&s.edge_ang, n * 8)); TG_HIP(hipMalloc(&s.embed, n * 8));
-    TG_HIP(hipMalloc(&s.stim_xform, 12 * n * 4)); TG_HIP(hipMalloc(&s.term_xform, 12 * n * 4));
-    TG_HIP(hipMalloc(&s.step_count, n * 4)); TG_HIP(hipMalloc(&s.reset_ticks, n * 4)); TG_HIP(hipMalloc(&s.licence, n * 4));
-    TG_HIP(hipMalloc(&s.trig_sc, (size_t)16 * n * 8)); TG_HIP(hipMalloc(&s.edge_sc, (size_t)2 * n * 8));
-    TG_HIP(hipMemset(s.trig_sc, 0, (size_t)16 * n * 8)); TG_HIP(hipMemset(s.edge_sc, 0, (size_t)2 * n * 8));
-    TG_HIP(hipMalloc(&s.rng, n * 8));
-    TG_HIP(hipMemset(s.q, 0, nd * 8)); TG_HIP(hipMemset(s.qd, 0, nd * 8)); TG_HIP(hipMemset(s.qd_target, 0, nd * 8));
-    TG_HIP(hipMemset(s.tcp_pos, 0, 3 * n * 8)); TG_HIP(hipMemset(s.tcp_rpy, 0, 3 * n * 8));
-    TG_HIP(hipMemset(s.edge_ang, 0, n * 8)); TG_HIP(hipMemset(s.embed, 0, n * 8));
-    TG_HIP(hipMemset(s.stim_xform, 0, 12 * n * 4)); TG_HIP(hipMemset(s.term_xform, 0, 12 * n * 4));
-    TG_HIP(hipMemset(s.step_count, 0, n * 4)); TG_HIP(hipMemset(s.reset_ticks, 0, n * 4)); TG_HIP(hipMemset(s.licence, 0, n * 4));
-    TG_HIP(hipMalloc(&s.sweeps, n * 4)); TG_HIP(hipMemset(s.sweeps, 0, n * 4));
+    const size_t n = (size_t)c->cfg.num_envs, nd = (size_t)TG_MAX_DOF * n;
+    if (dev_alloc(c, s.q, nd * 8) || dev_alloc(c, s.qd, nd * 8) || dev_alloc(c, s.qd_target, nd * 8) || dev_alloc(c, s.tcp_pos, 3 * n * 8) ||
+        dev_alloc(c, s.tcp_rpy, 3 * n * 8) || dev_alloc(c, s.edge_ang, n * 8) || dev_alloc(c, s.embed, n * 8) || dev_alloc(c, s.stim_xform, 12 * n * 4) ||
+        dev_alloc(c, s.term_xform, 12 * n * 4) || dev_alloc(c, s.step_count, n * 4) || dev_alloc(c, s.reset_ticks, n * 4) || dev_alloc(c, s.licence, n * 4) ||
+        dev_alloc(c, s.trig_sc, 16 * n * 8) || dev_alloc(c, s.edge_sc, 2 * n * 8) || dev_alloc(c, s.sweeps, n * 4) || dev_alloc(c, s.contact_code, n * 4))
+        return -2;
     std::vector<uint64_t> seeds(n);
-    for (int i = 0; i < n; ++i) seeds[i] = mix64((uint64_t)i + kGolden);
-    TG_HIP(hipMemcpy(s.rng, seeds.data(), n * 8, hipMemcpyHostToDevice));
-    TG_HIP(hipMalloc(&c->d_nodef_dep, npix * 4)); TG_HIP(hipMemcpy(c->d_nodef_dep, sensor->nodef_dep, npix * 4, hipMemcpyHostToDevice));
-    {
-        std::vector<uint8_t> g8(npix);
-        make_gray_u8(sensor->nodef_gray, (int)npix, g8.data());
-        TG_HIP(hipMalloc(&c->d_nodef_gray, npix)); TG_HIP(hipMemcpy(c->d_nodef_gray, g8.data(), npix, hipMemcpyHostToDevice));
-    }
-    TG_HIP(hipMalloc(&c->d_border, npix)); TG_HIP(hipMemcpy(c->d_border, sensor->border_mask, npix, hipMemcpyHostToDevice));
+    for (size_t i = 0; i < n; ++i) seeds[i] = mix64((uint64_t)i + kGolden);
+    return dev_upload(c, s.rng, seeds.data(), n * 8);
+}
+
+// the sensor's reference images, the tile template and the interior word tables
+static int upload_sensor_tables(tg_ctx* c, const tg_sensor* sensor) {
+    const size_t npix = (size_t)c->H * c->W, nw = npix / 4;
     c->cfg_turn_off_border = sensor->turn_off_border != 0;
-    {   // what a tile is compared with (tg_pack_tiles): t_s_camera's output for an untouched sensor (tactile_sensor.py:261-294)
-        std::vector<uint8_t> g8(npix), tmpl(npix, 0);
-        make_gray_u8(sensor->nodef_gray, (int)npix, g8.data());
-        if (!c->cfg_turn_off_border)
-            for (size_t p = 0; p < npix; ++p) tmpl[p] = sensor->border_mask[p] == 1 ? g8[p] : 0;
-        TG_HIP(hipMalloc(&c->d_tile_tmpl, npix)); TG_HIP(hipMemcpy(c->d_tile_tmpl, tmpl.data(), npix, hipMemcpyHostToDevice));
+    // what a tile is compared with (tg_pack_tiles): t_s_camera's output for an untouched sensor (tactile_sensor.py:261-294)
+    std::vector<uint8_t> g8(npix), tmpl(npix, 0);
+    make_gray_u8(sensor->nodef_gray, (int)npix, g8.data());
+    if (!c->cfg_turn_off_border)
+        for (size_t p = 0; p < npix; ++p) tmpl[p] = sensor->border_mask[p] == 1 ? g8[p] : 0;
+    // interior word tables (tg_pack_interior / tg_unpack_interior): the 4-pixel words that hold at least one interior pixel
+    std::vector<int32_t> idx, rank_of(nw, -1);
+    for (size_t q = 0; q < nw; ++q) {
+        bool any = false;
+        for (int e = 0; e < 4; ++e) any = any || sensor->border_mask[4 * q + e] != 1;
+        if (any) { rank_of[q] = (int32_t)idx.size(); idx.push_back((int32_t)q); }
     }
-    {   // interior word tables (tg_pack_interior / tg_unpack_interior): the 4-pixel words that hold at least one interior pixel
-        const size_t nw = (size_t)npix / 4;
-        std::vector<int32_t> idx, rank_of(nw, -1);
-        for (size_t q = 0; q < nw; ++q) {
-            bool any = false;
-            for (int e = 0; e < 4; ++e) any = any || sensor->border_mask[4 * q + e] != 1;
-            if (any) { rank_of[q] = (int32_t)idx.size(); idx.push_back((int32_t)q); }
-        }
-        while (idx.size() % 4 != 0 && !idx.empty()) idx.push_back(idx.back());   // payload rows are padded to a multiple of 4 words
-        c->n_interior = (int)idx.size();                                         // in words
-        TG_HIP(hipMalloc(&c->d_int_idx, std::max<size_t>(idx.size(), 1) * 4)); TG_HIP(hipMalloc(&c->d_int_rank, (size_t)npix));
-        TG_HIP(hipMemcpy(c->d_int_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-        TG_HIP(hipMemcpy(c->d_int_rank, rank_of.data(), (size_t)npix, hipMemcpyHostToDevice));
+    while (idx.size() % 4 != 0 && !idx.empty()) idx.push_back(idx.back());   // payload rows are padded to a multiple of 4 words
+    c->n_interior = (int)idx.size();                                         // in words
+    if (dev_upload(c, c->d_nodef_dep, sensor->nodef_dep, npix * 4) || dev_upload(c, c->d_nodef_gray, g8.data(), npix) ||
+        dev_upload(c, c->d_border, sensor->border_mask, npix) || dev_upload(c, c->d_tile_tmpl, tmpl.data(), npix) ||
+        dev_upload(c, c->d_int_idx, idx.data(), idx.size() * 4, idx.empty() ? 4 : 0) || dev_upload(c, c->d_int_rank, rank_of.data(), nw * 4))
+        return -2;
+    return 0;
+}
+
+// [fields][n] doubles (SoA), row f = v[f] in every env: a new allocation of the context, or written over the one the field already has
+static int broadcast_soa(tg_ctx* c, double*& field, const double* v, int fields) {
+    const size_t n = (size_t)c->cfg.num_envs;
+    std::vector<double> h((size_t)fields * n);
+    for (int f = 0; f < fields; ++f) std::fill_n(h.begin() + (size_t)f * n, n, v[f]);
+    if (!field) return dev_upload(c, field, h.data(), h.size() * 8);
+    TG_HIP(hipMemcpy(field, h.data(), h.size() * 8, hipMemcpyHostToDevice));
+    return 0;
+}
+// the free body of object_balance / object_roll / object_push: load_object (base_object_env.py:66-70) puts it at one pose in every env, at rest
+static int alloc_free_body(tg_ctx* c, const double* pos, const double* rot) {
+    State& s = c->st;
+    const size_t n = (size_t)c->cfg.num_envs;
+    if (broadcast_soa(c, s.body_pos, pos, 3) || broadcast_soa(c, s.body_rot, rot, 9) || dev_alloc(c, s.body_v, 3 * n * 8) || dev_alloc(c, s.body_w, 3 * n * 8)) return -2;
+    return 0;
+}
+static bool reset_bank_env_off() { const char* e = getenv("TG_RESET_BANK"); return e && e[0] == '0'; }
+static const double kIdentity3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+
+static int alloc_balance(tg_ctx* c) {
+    const tg_config& cfg = c->cfg;
+    State& s = c->st;
+    const size_t n = (size_t)cfg.num_envs;
+    const bool spin = cfg.balance_object == TG_BALANCE_SPINNING_PLATE;
+    if (dev_alloc(c, s.ext_pos, 3 * n * 8) || dev_alloc(c, s.ext_pending, n)) return -2;
+    {   // the arm's post-reset state, computed once (k_reset_body); off with reset_bank = TG_BANK_OFF / TG_RESET_BANK=0
+        bool tmpl = cfg.reset_bank != TG_BANK_OFF;
+        if (getenv("TG_RESET_BANK")) tmpl = !reset_bank_env_off();
+        if (cfg.solver_residual_threshold > 0.0) tmpl = false;   // threshold mode: the reset tick's truncated solve sees the fallen object (1e-6 rad): every reset is recomputed
+        if (spin) tmpl = true;                                    // (its literal reset moves the arm with the spool only: the template is that state)
+        if (tmpl && dev_alloc(c, s.reset_tmpl, (2 * TG_MAX_DOF + 2) * 8)) return -2;
     }
-    if (cfg->env_kind == TG_ENV_OBJECT_PUSH) {
-        // the arm's post-reset state + the tip's path (k_reset_contact_wave's reset template); off with reset_bank = TG_BANK_OFF / TG_RESET_BANK=0 and in
-        // threshold mode (the truncated solve couples the arm to the object's rows)
-        bool tmpl = cfg->reset_bank != TG_BANK_OFF && !(cfg->solver_residual_threshold > 0.0);
-        if (const char* e = getenv("TG_RESET_BANK")) tmpl = tmpl && e[0] != '0';
-        const size_t tb = (size_t)(2 * TG_MAX_DOF + 4 + 3 * 64) * 8;
-        if (tmpl) { TG_HIP(hipMalloc(&s.reset_tmpl, tb)); TG_HIP(hipMemset(s.reset_tmpl, 0, tb)); }
-        TG_HIP(hipMalloc(&s.tmpl_stats, 16)); TG_HIP(hipMemset(s.tmpl_stats, 0, 16));
+    // load_object (base_object_env.py:66-70): loadURDF puts the object's *link* frame at init_obj_pos; the inertial frame used by
+    // get/resetBasePositionAndOrientation is obj_root_inertial_pos away.  setup_object (:185-190): default embed distance.
+    double oq[4], oR[9];
+    h_quat_from_euler(cfg.obj_init_rpy, oq);
+    h_mat_from_quat(oq, oR);
+    double p0[3] = {cfg.workframe_pos[0], cfg.workframe_pos[1], cfg.workframe_pos[2] + cfg.obj_base_height / 2 - cfg.embed_dist};
+    for (int a = 0; a < 3; ++a)
+        p0[a] += oR[3 * a] * cfg.obj_root_inertial_pos[0] + oR[3 * a + 1] * cfg.obj_root_inertial_pos[1] + oR[3 * a + 2] * cfg.obj_root_inertial_pos[2];
+    if (spin) {   // the dish where the pole would be, on top of the spool (:215-219); the spool at init_buffer_pos (:228-233) is the free body
+        std::vector<double> hulls(cfg.spin_dish_hull, cfg.spin_dish_hull + (size_t)3 * cfg.spin_n_dish);
+        hulls.insert(hulls.end(), cfg.spin_spool_hull, cfg.spin_spool_hull + (size_t)3 * cfg.spin_n_spool);
+        c->cfg.spin_dish_hull = nullptr; c->cfg.spin_spool_hull = nullptr;   // the host pointers are not kept
+        double dish[20] = {p0[0], p0[1], p0[2] + cfg.spin_buffer_height};
+        std::copy(oR, oR + 9, dish + 3);
+        const double spool[3] = {cfg.workframe_pos[0], cfg.workframe_pos[1], cfg.workframe_pos[2] + cfg.spin_buffer_height / 2};
+        if (dev_upload(c, s.spin_hulls, hulls.data(), hulls.size() * 8) || broadcast_soa(c, s.dish, dish, 20) || dev_alloc(c, s.mani, 37 * n * 8) ||
+            alloc_free_body(c, spool, kIdentity3))
+            return -2;
+    } else if (alloc_free_body(c, p0, oR)) return -2;
+    if (cfg.balance_object == TG_BALANCE_BALL_ON_PLATE) {   // load_ball (:241-260): at workframe + (0, 0, radius), at rest
+        const double ball[13] = {cfg.workframe_pos[0], cfg.workframe_pos[1], cfg.workframe_pos[2] + cfg.ball_radius};
+        if (broadcast_soa(c, s.ball, ball, 13)) return -2;
     }
-    if (cfg->env_kind == TG_ENV_OBJECT_BALANCE) {
-        TG_HIP(hipMalloc(&s.body_pos, 3 * n * 8)); TG_HIP(hipMalloc(&s.body_rot, 9 * n * 8)); TG_HIP(hipMalloc(&s.body_v, 3 * n * 8));
-        TG_HIP(hipMalloc(&s.body_w, 3 * n * 8)); TG_HIP(hipMalloc(&s.ext_pos, 3 * n * 8)); TG_HIP(hipMalloc(&s.gravity, n * 8));
-        TG_HIP(hipMalloc(&s.ext_pending, n));
-        TG_HIP(hipMemset(s.body_v, 0, 3 * n * 8)); TG_HIP(hipMemset(s.body_w, 0, 3 * n * 8)); TG_HIP(hipMemset(s.ext_pos, 0, 3 * n * 8));
-        TG_HIP(hipMemset(s.ext_pending, 0, n));
-        {   // the arm's post-reset state, computed once (k_reset_body); off with reset_bank = TG_BANK_OFF / TG_RESET_BANK=0
-            bool tmpl = cfg->reset_bank != TG_BANK_OFF;
-            if (const char* e = getenv("TG_RESET_BANK")) tmpl = e[0] != '0';
-            if (cfg->solver_residual_threshold > 0.0) tmpl = false;   // threshold mode: the reset tick's truncated solve sees the fallen object (1e-6 rad): every reset is recomputed
-            if (cfg->balance_object == TG_BALANCE_SPINNING_PLATE) tmpl = true;   // (its literal reset moves the arm with the spool only: the template is that state)
-            if (tmpl) { TG_HIP(hipMalloc(&s.reset_tmpl, (2 * TG_MAX_DOF + 2) * 8)); TG_HIP(hipMemset(s.reset_tmpl, 0, (2 * TG_MAX_DOF + 2) * 8)); }
-        }
-        if (cfg->balance_object == TG_BALANCE_SPINNING_PLATE) {
-            const size_t hw = (size_t)3 * (cfg->spin_n_dish + cfg->spin_n_spool);
-            double* dh = nullptr;
-            TG_HIP(hipMalloc(&dh, hw * 8));
-            TG_HIP(hipMemcpy(dh, cfg->spin_dish_hull, (size_t)3 * cfg->spin_n_dish * 8, hipMemcpyHostToDevice));
-            TG_HIP(hipMemcpy(dh + (size_t)3 * cfg->spin_n_dish, cfg->spin_spool_hull, (size_t)3 * cfg->spin_n_spool * 8, hipMemcpyHostToDevice));
-            s.spin_hulls = dh;
-            c->cfg.spin_dish_hull = nullptr; c->cfg.spin_spool_hull = nullptr;   // the host pointers are not kept
-            TG_HIP(hipMalloc(&s.dish, (size_t)20 * n * 8)); TG_HIP(hipMemset(s.dish, 0, (size_t)20 * n * 8));
-            TG_HIP(hipMalloc(&s.mani, (size_t)37 * n * 8)); TG_HIP(hipMemset(s.mani, 0, (size_t)37 * n * 8));
-        }
-        if (cfg->balance_object == TG_BALANCE_BALL_ON_PLATE) {   // load_ball (:241-260): at workframe + (0, 0, radius), at rest
-            TG_HIP(hipMalloc(&s.ball, (size_t)13 * n * 8));
-            std::vector<double> bl((size_t)13 * n, 0.0);
-            for (int i = 0; i < n; ++i) {
-                bl[(size_t)0 * n + i] = cfg->workframe_pos[0]; bl[(size_t)1 * n + i] = cfg->workframe_pos[1];
-                bl[(size_t)2 * n + i] = cfg->workframe_pos[2] + cfg->ball_radius;
-            }
-            TG_HIP(hipMemcpy(s.ball, bl.data(), bl.size() * 8, hipMemcpyHostToDevice));
-        }
-        // load_object (base_object_env.py:66-70): loadURDF puts the object's *link* frame at init_obj_pos; the inertial frame used by
-        // get/resetBasePositionAndOrientation is obj_root_inertial_pos away.  setup_object (:185-190): default embed distance.
-        double oq[4], oR[9];
-        h_quat_from_euler(cfg->obj_init_rpy, oq);
-        h_mat_from_quat(oq, oR);
-        double p0[3] = {cfg->workframe_pos[0], cfg->workframe_pos[1], cfg->workframe_pos[2] + cfg->obj_base_height / 2 - cfg->embed_dist};
-        for (int a = 0; a < 3; ++a)
-            p0[a] += oR[3 * a] * cfg->obj_root_inertial_pos[0] + oR[3 * a + 1] * cfg->obj_root_inertial_pos[1] + oR[3 * a + 2] * cfg->obj_root_inertial_pos[2];
-        std::vector<double> bp(3 * (size_t)n), br(9 * (size_t)n), gz(n, cfg->gravity_default), em(n, cfg->embed_dist);
-        for (int i = 0; i < n; ++i) {
-            for (int a = 0; a < 3; ++a) bp[(size_t)a * n + i] = p0[a];
-            for (int a = 0; a < 9; ++a) br[(size_t)a * n + i] = oR[a];
-        }
-        if (cfg->balance_object == TG_BALANCE_SPINNING_PLATE) {   // the dish where the pole would be, on top of the spool (:215-219); the spool at init_buffer_pos (:228-233)
-            std::vector<double> ds((size_t)20 * n, 0.0);
-            for (int i = 0; i < n; ++i) {
-                for (int a = 0; a < 3; ++a) ds[(size_t)a * n + i] = p0[a] + (a == 2 ? cfg->spin_buffer_height : 0.0);
-                for (int a = 0; a < 9; ++a) ds[(size_t)(3 + a) * n + i] = oR[a];
-                bp[(size_t)0 * n + i] = cfg->workframe_pos[0]; bp[(size_t)1 * n + i] = cfg->workframe_pos[1];
-                bp[(size_t)2 * n + i] = cfg->workframe_pos[2] + cfg->spin_buffer_height / 2;
-                for (int a = 0; a < 9; ++a) br[(size_t)a * n + i] = (a % 4 == 0) ? 1.0 : 0.0;
-            }
-            TG_HIP(hipMemcpy(s.dish, ds.data(), ds.size() * 8, hipMemcpyHostToDevice));
-        }
-        TG_HIP(hipMemcpy(s.body_pos, bp.data(), bp.size() * 8, hipMemcpyHostToDevice));
-        TG_HIP(hipMemcpy(s.body_rot, br.data(), br.size() * 8, hipMemcpyHostToDevice));
-        TG_HIP(hipMemcpy(s.gravity, gz.data(), gz.size() * 8, hipMemcpyHostToDevice));
-        TG_HIP(hipMemcpy(s.embed, em.data(), em.size() * 8, hipMemcpyHostToDevice));
-    }
-    TG_HIP(hipMalloc(&s.contact_code, (size_t)n * 4)); TG_HIP(hipMemset(s.contact_code, 0, (size_t)n * 4));
-    if (cfg->env_kind == TG_ENV_OBJECT_ROLL) {
-        TG_HIP(hipMalloc(&s.body_pos, 3 * n * 8)); TG_HIP(hipMalloc(&s.body_rot, 9 * n * 8)); TG_HIP(hipMalloc(&s.body_v, 3 * n * 8));
-        TG_HIP(hipMalloc(&s.body_w, 3 * n * 8)); TG_HIP(hipMalloc(&s.obj_mass, n * 8)); TG_HIP(hipMalloc(&s.goal, 3 * n * 8));
-        TG_HIP(hipMalloc(&s.term_feature, (size_t)12 * n * 4));
-        TG_HIP(hipMemset(s.body_v, 0, 3 * n * 8)); TG_HIP(hipMemset(s.body_w, 0, 3 * n * 8)); TG_HIP(hipMemset(s.goal, 0, 3 * n * 8));
-        TG_HIP(hipMemset(s.term_feature, 0, (size_t)12 * n * 4));
-        // load_object (base_object_env.py:66-70) at init_obj_pos, identity orientation, default radius (object_roll_env.py:156-166)
-        std::vector<double> bp(3 * (size_t)n), br(9 * (size_t)n, 0.0), rad(n, cfg->roll_radius), em(n, cfg->embed_dist);
-        for (int i = 0; i < n; ++i) {
-            for (int a = 0; a < 3; ++a) bp[(size_t)a * n + i] = cfg->obj_init_pos[a];
-            br[(size_t)0 * n + i] = 1.0; br[(size_t)4 * n + i] = 1.0; br[(size_t)8 * n + i] = 1.0;
-        }
-        TG_HIP(hipMemcpy(s.body_pos, bp.data(), bp.size() * 8, hipMemcpyHostToDevice));
-        TG_HIP(hipMemcpy(s.body_rot, br.data(), br.size() * 8, hipMemcpyHostToDevice));
-        TG_HIP(hipMemcpy(s.obj_mass, rad.data(), rad.size() * 8, hipMemcpyHostToDevice));
-        TG_HIP(hipMemcpy(s.embed, em.data(), em.size() * 8, hipMemcpyHostToDevice));
-    }
-    if (cfg->env_kind == TG_ENV_OBJECT_PUSH) {
-        TG_HIP(hipMalloc(&s.body_pos, 3 * n * 8)); TG_HIP(hipMalloc(&s.body_rot, 9 * n * 8)); TG_HIP(hipMalloc(&s.body_v, 3 * n * 8));
-        TG_HIP(hipMalloc(&s.body_w, 3 * n * 8)); TG_HIP(hipMalloc(&s.noise_seed, n * 8)); TG_HIP(hipMalloc(&s.obj_mass, n * 8));
-        TG_HIP(hipMalloc(&s.traj, (size_t)3 * TG_MAX_TRAJ_POINTS * n * 8)); TG_HIP(hipMalloc(&s.goal_id, n * 4));
-        TG_HIP(hipMalloc(&s.term_feature, (size_t)12 * n * 4));
-        if (cfg->narrowphase != TG_NARROW_CLOSED_FORM) { TG_HIP(hipMalloc(&s.mani, (size_t)37 * n * 8)); TG_HIP(hipMemset(s.mani, 0, (size_t)37 * n * 8)); }
-        TG_HIP(hipMemset(s.body_v, 0, 3 * n * 8)); TG_HIP(hipMemset(s.body_w, 0, 3 * n * 8)); TG_HIP(hipMemset(s.noise_seed, 0, n * 8));
-        TG_HIP(hipMemset(s.traj, 0, (size_t)3 * TG_MAX_TRAJ_POINTS * n * 8)); TG_HIP(hipMemset(s.goal_id, 0, n * 4));
-        TG_HIP(hipMemset(s.term_feature, 0, (size_t)12 * n * 4));
-        // load_object (base_object_env.py:66-70) at init_obj_pos / init_obj_orn (object_push_env.py:154-160)
-        double oq[4], oR[9];
-        h_quat_from_euler(cfg->obj_init_rpy, oq);
-        h_mat_from_quat(oq, oR);
-        std::vector<double> bp(3 * (size_t)n), br(9 * (size_t)n), ms(n, cfg->obj_mass);
-        for (int i = 0; i < n; ++i) {
-            for (int a = 0; a < 3; ++a) bp[(size_t)a * n + i] = cfg->obj_init_pos[a];
-            for (int a = 0; a < 9; ++a) br[(size_t)a * n + i] = oR[a];
-        }
-        TG_HIP(hipMemcpy(s.body_pos, bp.data(), bp.size() * 8, hipMemcpyHostToDevice));
-        TG_HIP(hipMemcpy(s.body_rot, br.data(), br.size() * 8, hipMemcpyHostToDevice));
-        TG_HIP(hipMemcpy(s.obj_mass, ms.data(), ms.size() * 8, hipMemcpyHostToDevice));
-        const size_t nv = (size_t)cfg->n_tip_verts * 3;
-        void* dv = nullptr;
-        if (cfg->physics_dtype == TG_PHYSICS_F64) {
-            TG_HIP(hipMalloc(&dv, nv * 8)); TG_HIP(hipMemcpy(dv, cfg->tip_verts, nv * 8, hipMemcpyHostToDevice));
-        } else {
-            std::vector<float> vf(nv);
-            for (size_t k = 0; k < nv; ++k) vf[k] = (float)cfg->tip_verts[k];
-            TG_HIP(hipMalloc(&dv, nv * 4)); TG_HIP(hipMemcpy(dv, vf.data(), nv * 4, hipMemcpyHostToDevice));
-        }
-        s.tip_verts = dv;
-        c->cfg.tip_verts = nullptr;   // the host pointer is not kept
-    }
-    if (cfg->env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) {
-        const size_t cells = (size_t)cfg->surf_rows * cfg->surf_cols;
-        // (three surfaces per env - State::hsel: live 0, last 2, spare 1 to begin with)
-        TG_HIP(hipMalloc(&s.dir, 2 * n * 8)); TG_HIP(hipMalloc(&s.goal, 3 * n * 8)); TG_HIP(hipMalloc(&s.heights, 3 * cells * n * 8));
-        TG_HIP(hipMalloc(&s.hsel, n)); TG_HIP(hipMemset(s.hsel, 2 << 2, n));
-        TG_HIP(hipMalloc(&s.surf_zoff, 3 * n * 4)); TG_HIP(hipMalloc(&s.noise_seed, n * 8)); TG_HIP(hipMalloc(&s.accum, n * 8));
-        TG_HIP(hipMemset(s.dir, 0, 2 * n * 8)); TG_HIP(hipMemset(s.goal, 0, 3 * n * 8)); TG_HIP(hipMemset(s.heights, 0, 3 * cells * n * 8));
-        TG_HIP(hipMemset(s.surf_zoff, 0, 3 * n * 4)); TG_HIP(hipMemset(s.noise_seed, 0, n * 8)); TG_HIP(hipMemset(s.accum, 0, n * 8));
-        TG_HIP(hipMalloc(&s.term_feature, (size_t)12 * n * 4)); TG_HIP(hipMemset(s.term_feature, 0, (size_t)12 * n * 4));
-        c->stim.kind = 1; c->stim.heights = s.heights; c->stim.zoff = s.surf_zoff; c->stim.hsel = s.hsel;
-        c->stim.rows = cfg->surf_rows; c->stim.cols = cfg->surf_cols; c->stim.scale = (float)cfg->surf_grid_scale;
-        c->stim.n_tris = (cfg->surf_rows - 1) * (cfg->surf_cols - 1) * 2;
-    } else {
-        TG_HIP(hipMalloc(&c->d_verts, (size_t)stim->n_verts * 12)); TG_HIP(hipMemcpy(c->d_verts, stim->verts, (size_t)stim->n_verts * 12, hipMemcpyHostToDevice));
-        TG_HIP(hipMalloc(&c->d_tris, (size_t)stim->n_tris * 12)); TG_HIP(hipMemcpy(c->d_tris, stim->tris, (size_t)stim->n_tris * 12, hipMemcpyHostToDevice));
-        c->n_tris = stim->n_tris;
-        {
-            std::vector<float> soup((size_t)stim->n_tris * 9);
-            for (int t = 0; t < stim->n_tris; ++t)
-                for (int k = 0; k < 3; ++k)
-                    for (int a = 0; a < 3; ++a) soup[(size_t)t * 9 + 3 * k + a] = stim->verts[3 * (size_t)stim->tris[3 * t + k] + a];
-            TG_HIP(hipMalloc(&c->d_soup, soup.size() * 4 + 4)); TG_HIP(hipMemcpy(c->d_soup, soup.data(), soup.size() * 4, hipMemcpyHostToDevice));
-        }
-        // The per-quad reject of k_render_small is off for every shared mesh: with the back faces culled at set-up the records are few, and
-        // without it the kernel needs 98 instead of 126 VGPRs - five workgroups per CU instead of four (edge_follow render 34.5 -> 31.7 us,
-        // 16 384 envs 0.340 -> 0.289 ms; object_push's cube unchanged; object_balance's plate never used it).
-        c->stim.skip_quad_reject = 1;
-        c->stim.fills_view = cfg->env_kind == TG_ENV_OBJECT_BALANCE ? 1 : 0;
-        c->stim.closed_outward = (mesh_closed_outward(stim) && getenv("TG_NO_BACKFACE_CULL") == nullptr) ? 1 : 0;   // env var: A/B measurements only
-        c->stim.kind = 0; c->stim.verts = c->d_verts; c->stim.tris = c->d_tris; c->stim.soup = c->d_soup; c->stim.n_tris = stim->n_tris;
-    }
+    if (broadcast_soa(c, s.gravity, &cfg.gravity_default, 1) || broadcast_soa(c, s.embed, &cfg.embed_dist, 1)) return -2;
+    return 0;
+}
+
+static int alloc_roll(tg_ctx* c) {
+    const tg_config& cfg = c->cfg;
+    State& s = c->st;
+    const size_t n = (size_t)cfg.num_envs;
+    // at init_obj_pos, identity orientation, default radius (object_roll_env.py:156-166)
+    if (alloc_free_body(c, cfg.obj_init_pos, kIdentity3) || broadcast_soa(c, s.obj_mass, &cfg.roll_radius, 1) || broadcast_soa(c, s.embed, &cfg.embed_dist, 1) ||
+        dev_alloc(c, s.goal, 3 * n * 8) || dev_alloc(c, s.term_feature, 12 * n * 4))
+        return -2;
+    return 0;
+}
+
+static int alloc_push(tg_ctx* c) {
+    const tg_config& cfg = c->cfg;
+    State& s = c->st;
+    const size_t n = (size_t)cfg.num_envs;
+    // the arm's post-reset state + the tip's path (k_reset_contact_wave's reset template); off with reset_bank = TG_BANK_OFF / TG_RESET_BANK=0 and in
+    // threshold mode (the truncated solve couples the arm to the object's rows)
+    const bool tmpl = cfg.reset_bank != TG_BANK_OFF && !(cfg.solver_residual_threshold > 0.0) && !reset_bank_env_off();
+    if (tmpl && dev_alloc(c, s.reset_tmpl, (size_t)(2 * TG_MAX_DOF + 4 + 3 * 64) * 8)) return -2;
+    // at init_obj_pos / init_obj_orn (object_push_env.py:154-160)
+    double oq[4], oR[9];
+    h_quat_from_euler(cfg.obj_init_rpy, oq);
+    h_mat_from_quat(oq, oR);
+    if (dev_alloc(c, s.tmpl_stats, 16) || alloc_free_body(c, cfg.obj_init_pos, oR) || broadcast_soa(c, s.obj_mass, &cfg.obj_mass, 1) || dev_alloc(c, s.noise_seed, n * 8) ||
+        dev_alloc(c, s.traj, (size_t)3 * TG_MAX_TRAJ_POINTS * n * 8) || dev_alloc(c, s.goal_id, n * 4) || dev_alloc(c, s.term_feature, 12 * n * 4) ||
+        (cfg.narrowphase != TG_NARROW_CLOSED_FORM && dev_alloc(c, s.mani, 37 * n * 8)))
+        return -2;
+    const size_t nv = (size_t)cfg.n_tip_verts * 3;   // the tip's hull in the physics dtype
+    const bool f64 = cfg.physics_dtype == TG_PHYSICS_F64;
+    std::vector<float> vf;
+    if (!f64) for (size_t k = 0; k < nv; ++k) vf.push_back((float)cfg.tip_verts[k]);
+    const int rc = f64 ? dev_upload(c, s.tip_verts, cfg.tip_verts, nv * 8) : dev_upload(c, s.tip_verts, vf.data(), nv * 4);
+    c->cfg.tip_verts = nullptr;   // the host pointer is not kept
+    return rc;
+}
+
+static int alloc_surface(tg_ctx* c) {
+    const tg_config& cfg = c->cfg;
+    State& s = c->st;
+    const size_t n = (size_t)cfg.num_envs, cells = (size_t)cfg.surf_rows * cfg.surf_cols;
+    // (three surfaces per env - State::hsel: live 0, last 2, spare 1 to begin with)
+    if (dev_alloc(c, s.dir, 2 * n * 8) || dev_alloc(c, s.goal, 3 * n * 8) || dev_alloc(c, s.heights, 3 * cells * n * 8) || dev_alloc(c, s.hsel, n, 2 << 2) ||
+        dev_alloc(c, s.surf_zoff, 3 * n * 4) || dev_alloc(c, s.noise_seed, n * 8) || dev_alloc(c, s.accum, n * 8) || dev_alloc(c, s.term_feature, 12 * n * 4))
+        return -2;
+    c->stim.kind = 1; c->stim.heights = s.heights; c->stim.zoff = s.surf_zoff; c->stim.hsel = s.hsel;
+    c->stim.rows = cfg.surf_rows; c->stim.cols = cfg.surf_cols; c->stim.scale = (float)cfg.surf_grid_scale;
+    c->stim.n_tris = (cfg.surf_rows - 1) * (cfg.surf_cols - 1) * 2;
+    return 0;
+}
+
+// the stimulus mesh every env shares (all but surface_follow)
+static int upload_stimulus(tg_ctx* c, const tg_mesh* stim) {
+    std::vector<float> soup((size_t)stim->n_tris * 9);
+    for (int t = 0; t < stim->n_tris; ++t)
+        for (int k = 0; k < 3; ++k)
+            for (int a = 0; a < 3; ++a) soup[(size_t)t * 9 + 3 * k + a] = stim->verts[3 * (size_t)stim->tris[3 * t + k] + a];
+    if (dev_upload(c, c->d_verts, stim->verts, (size_t)stim->n_verts * 12) || dev_upload(c, c->d_tris, stim->tris, (size_t)stim->n_tris * 12) ||
+        dev_upload(c, c->d_soup, soup.data(), soup.size() * 4, 4))
+        return -2;
+    c->n_tris = stim->n_tris;
+    // The per-quad reject of k_render_small is off for every shared mesh: with the back faces culled at set-up the records are few, and
+    // without it the kernel needs 98 instead of 126 VGPRs - five workgroups per CU instead of four (edge_follow render 34.5 -> 31.7 us,
+    // 16 384 envs 0.340 -> 0.289 ms; object_push's cube unchanged; object_balance's plate never used it).
+    c->stim.skip_quad_reject = 1;
+    c->stim.fills_view = c->cfg.env_kind == TG_ENV_OBJECT_BALANCE ? 1 : 0;
+    c->stim.closed_outward = (mesh_closed_outward(stim) && getenv("TG_NO_BACKFACE_CULL") == nullptr) ? 1 : 0;   // env var: A/B measurements only
+    c->stim.kind = 0; c->stim.verts = c->d_verts; c->stim.tris = c->d_tris; c->stim.soup = c->d_soup; c->stim.n_tris = stim->n_tris;
+    return 0;
+}
+
+// the output block, the terminal images, the episode block, the mask and action buffers
+static int alloc_outputs(tg_ctx* c) {
+    State& s = c->st;
+    const size_t n = (size_t)c->cfg.num_envs, npix = (size_t)c->H * c->W;
     // one allocation [tactile obs u8 | reward f32 | done u8]: what a rank ships to rank 0 per step is one contiguous byte range
     // (tg_get_packed_outputs).  The obs block is padded to 16 bytes so the reward block stays aligned.
-    c->packed_obs_bytes = ((size_t)npix * n + 15) & ~(size_t)15;
-    c->packed_bytes = c->packed_obs_bytes + (size_t)n * 4 + (size_t)n;
-    const bool has_feature = env_has_feature(cfg->env_kind);
+    c->packed_obs_bytes = (npix * n + 15) & ~(size_t)15;
+    c->packed_bytes = c->packed_obs_bytes + n * 4 + n;
+    const bool has_feature = env_has_feature(c->cfg.env_kind);
     if (has_feature) {   // extended_feature rides in the same message (config 4's tactile_and_feature observation)
         c->packed_feature_off = (c->packed_bytes + 3) & ~(size_t)3;
-        c->packed_bytes = c->packed_feature_off + (size_t)n * 12 * 4;
+        c->packed_bytes = c->packed_feature_off + n * 12 * 4;
     }
-    TG_HIP(hipMalloc(&c->d_obs, c->packed_bytes)); TG_HIP(hipMemset(c->d_obs, 0, c->packed_bytes));
+    if (dev_alloc(c, c->d_obs, c->packed_bytes) || dev_alloc(c, c->d_term, npix * n) || dev_alloc(c, c->d_episode, n * 16) || dev_alloc(c, c->d_mask, n) ||
+        dev_alloc(c, c->d_actions, n * 6 * sizeof(float)))
+        return -2;
     s.reward = (float*)(c->d_obs + c->packed_obs_bytes);
-    s.done = c->d_obs + c->packed_obs_bytes + (size_t)n * 4;
+    s.done = c->d_obs + c->packed_obs_bytes + n * 4;
     if (has_feature) s.feature = (float*)(c->d_obs + c->packed_feature_off);
-    TG_HIP(hipMalloc(&c->d_term, npix * n)); TG_HIP(hipMemset(c->d_term, 0, npix * n));
-    TG_HIP(hipMalloc(&c->d_episode, (size_t)n * 16)); TG_HIP(hipMemset(c->d_episode, 0, (size_t)n * 16));
     s.ep_return = (double*)c->d_episode;
-    s.ep_final_return = (float*)(c->d_episode + (size_t)n * 8);
-    s.ep_final_len = (int32_t*)(c->d_episode + (size_t)n * 12);
-    TG_HIP(hipMalloc(&c->d_mask, n));
+    s.ep_final_return = (float*)(c->d_episode + n * 8);
+    s.ep_final_len = (int32_t*)(c->d_episode + n * 12);
 #ifdef TG_TL_STAMPS
-    TG_HIP(hipMalloc(&s.tl, (4 * 8192 + 4) * 8)); TG_HIP(hipMemset(s.tl, 0, (4 * 8192 + 4) * 8));
+    if (dev_alloc(c, s.tl, (4 * 8192 + 4) * 8)) return -2;
 #endif
-    TG_HIP(hipMalloc(&c->d_actions, (size_t)n * 6 * sizeof(float)));
-    c->rp = make_raster_params(W, H, sensor->fov_deg, sensor->near_plane, sensor->far_plane, sensor->turn_off_border, sensor->nodef_dep);
-    if (make_block_tables(c->rp, sensor->nodef_dep, sensor->nodef_gray, sensor->border_mask, n, &c->d_block_tables)) return fail(-2, "hipMalloc failed (raster block tables)");
-    c->fused_pref = cfg->fused_step == TG_FUSED_OFF ? -1 : cfg->fused_step == TG_FUSED_ON ? 1 : 0;
+    return 0;
+}
+
+static int make_raster_tables(tg_ctx* c, const tg_sensor* sensor) {
+    c->rp = make_raster_params(c->W, c->H, sensor->fov_deg, sensor->near_plane, sensor->far_plane, sensor->turn_off_border, sensor->nodef_dep);
+#ifdef TG_TL_STAMPS
+    c->rp.tl = c->st.tl;
+#endif
+    if (make_block_tables(c->rp, sensor->nodef_dep, sensor->nodef_gray, sensor->border_mask, c->cfg.num_envs, &c->d_block_tables)) return fail(-2, "hipMalloc failed (raster block tables)");
+    if (c->d_block_tables) c->dev_allocs.push_back(c->d_block_tables);   // allocated by tg_raster.hip, owned by the context from here
+    return 0;
+}
+
+static int plan_step(tg_ctx* c) {
+    const tg_config& cfg = c->cfg;
+    c->fused_pref = cfg.fused_step == TG_FUSED_OFF ? -1 : cfg.fused_step == TG_FUSED_ON ? 1 : 0;
     if (const char* e = getenv("TG_FUSED_STEP")) c->fused_pref = e[0] == '0' ? -1 : 1;   // A/B switch (tests, measurements)
     c->no_inline_reset = getenv("TG_NO_INLINE_RESET") != nullptr;
     { const char* e = getenv("TG_KSTEP_QUAD"); c->kstep_quad = !(e != nullptr && e[0] == '0'); }
     c->plan = choose_step_plan(c);
-    if (c->plan.family == StepFamily::Spin && !can_run_spin(cfg->physics_dtype, robot->topology, cfg->spin_n_dish))
+    if (c->plan.family == StepFamily::Spin && !can_run_spin(cfg.physics_dtype, c->robot.topology, cfg.spin_n_dish))
         return fail(-3, "tg_create: object_balance spinning_plate has no step kernel for this combination (k_step_spin: f64, the UR5 chain, dish hull <= 1152 vertices)");
-#ifdef TG_TL_STAMPS
-    c->rp.tl = s.tl;
-#endif
-    c->bk = s;
-    {   // reset bank: edge_follow / surface_follow with auto_reset on the lane mapping (tg_config.reset_bank, TG_RESET_BANK)
-        // TG_BANK_AUTO: on (round 5; until then only for the MG400, whose reset is 0.9 ms).  With every env finishing in the same step - a random
-        // rollout from a common start - a UR5 reset on the spot costs 0.1 ms once per episode and the bank buys nothing; with episodes that end
-        // in different steps - any RL run - some env finishes in nearly every step and the step waits for that reset every time: 6.7 against
-        // 18.3 M env-steps/s at 1024 envs (tools/desync_rate.py), while the aligned rollout is unchanged since bank_refill stopped waiting across
-        // streams.
-        int want = cfg->reset_bank == TG_BANK_OFF ? 0 : cfg->reset_bank == TG_BANK_SYNC ? 2 : 1;
-        if (const char* e = getenv("TG_RESET_BANK")) want = (e[0] == '0') ? 0 : (e[0] == 's') ? 2 : 1;
-        if (const char* e = getenv("TG_RESET_BANK_EVERY")) { const int k = atoi(e); if (k >= 1) c->bank_every = k; }
-        if (want && cfg->auto_reset && c->plan.family == StepFamily::LaneArm) {
-            State& b = c->bk;
-            auto grab = [&](auto*& ptr, size_t bytes) -> int {
-                void* p_ = nullptr;
-                if (hipMalloc(&p_, bytes) != hipSuccess) return -1;
-                (void)hipMemset(p_, 0, bytes);
-                c->bank_allocs.push_back(p_);
-                ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(p_);
-                return 0;
-            };
-            int bad = 0;
-            bad |= grab(b.q, nd * 8); bad |= grab(b.qd, nd * 8); bad |= grab(b.qd_target, nd * 8);
-            bad |= grab(b.tcp_pos, (size_t)3 * n * 8); bad |= grab(b.tcp_rpy, (size_t)3 * n * 8);
-            bad |= grab(b.edge_ang, (size_t)n * 8); bad |= grab(b.embed, (size_t)n * 8); bad |= grab(b.edge_sc, (size_t)2 * n * 8);
-            bad |= grab(b.stim_xform, (size_t)12 * n * 4);
-            bad |= grab(b.step_count, (size_t)n * 4); bad |= grab(b.reset_ticks, (size_t)n * 4); bad |= grab(b.licence, (size_t)n * 4);
-            bad |= grab(b.trig_sc, (size_t)16 * n * 8);
-            bad |= grab(b.rng, (size_t)n * 8);
-            if (cfg->env_kind == TG_ENV_SURFACE_FOLLOW_AUTO) {
-                bad |= grab(b.dir, (size_t)2 * n * 8); bad |= grab(b.goal, (size_t)3 * n * 8); bad |= grab(b.hsel, (size_t)n);   // (heights / surf_zoff: the env state's own, the entry's surface goes to the spare third)
-                bad |= grab(b.accum, (size_t)n * 8); bad |= grab(b.noise_seed, (size_t)n * 8);
-                if (s.feature) bad |= grab(b.feature, (size_t)12 * n * 4);
-            }
-            bad |= grab(c->aux.tag, (size_t)n * 8); bad |= grab(c->aux.rng_in, (size_t)n * 8);
-            bad |= grab(c->aux.stats, 16);
-            bad |= grab(c->aux.need, (size_t)n); bad |= grab(c->aux.late, (size_t)n); bad |= grab(c->aux.swapped, (size_t)n);
-            if (bad) return fail(-2, "hipMalloc failed (reset bank)");
-            int lo = 0, hi = 0;
-            (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // lo = the least priority
-            TG_HIP(hipStreamCreateWithPriority(&c->bank_stream, hipStreamNonBlocking, lo));
-            TG_HIP(hipEventCreateWithFlags(&c->ev_bank, hipEventDisableTiming)); TG_HIP(hipEventCreateWithFlags(&c->ev_bank_done, hipEventDisableTiming));
-            for (int k = 0; k < tg_ctx::kBankRing; ++k) TG_HIP(hipEventCreateWithFlags(&c->ev_bank_ring[k], hipEventDisableTiming));   // the refill's pacing markers (bank_refill)
-            c->aux.enabled = 1;
-            c->bank_mode = want;
-            BankDev hb{c->bk, c->aux};
-            bad |= grab(c->d_bank, sizeof hb);
-            if (bad) return fail(-2, "hipMalloc failed (reset bank)");
-            TG_HIP(hipMemcpy(c->d_bank, &hb, sizeof hb, hipMemcpyHostToDevice));
-        }
-    }
     return 0;
 }
 
-int tg_destroy(tg_ctx* c) {
-    if (!c) return 0;
-    (void)hipSetDevice(c->cfg.device);
-    (void)hipStreamSynchronize(c->stream);
-    drain_events(c);
-    if (c->scene_on) scene_debug_stats();
-    raster_debug_stats();
+// reset bank: edge_follow / surface_follow with auto_reset on the lane mapping (tg_config.reset_bank, TG_RESET_BANK)
+// TG_BANK_AUTO: on (round 5; until then only for the MG400, whose reset is 0.9 ms).  With every env finishing in the same step - a random
+// rollout from a common start - a UR5 reset on the spot costs 0.1 ms once per episode and the bank buys nothing; with episodes that end
+// in different steps - any RL run - some env finishes in nearly every step and the step waits for that reset every time: 6.7 against
+// 18.3 M env-steps/s at 1024 envs (tools/desync_rate.py), while the aligned rollout is unchanged since bank_refill stopped waiting across
+// streams.
+static int alloc_reset_bank(tg_ctx* c) {
+    const tg_config& cfg = c->cfg;
+    c->bk = c->st;
+    int want = cfg.reset_bank == TG_BANK_OFF ? 0 : cfg.reset_bank == TG_BANK_SYNC ? 2 : 1;
+    if (const char* e = getenv("TG_RESET_BANK")) want = (e[0] == '0') ? 0 : (e[0] == 's') ? 2 : 1;
+    if (const char* e = getenv("TG_RESET_BANK_EVERY")) { const int k = atoi(e); if (k >= 1) c->bank_every = k; }
+    if (!want || !cfg.auto_reset || c->plan.family != StepFamily::LaneArm) return 0;
+    State& b = c->bk;
+    BankAux& x = c->aux;
+    const size_t n = (size_t)cfg.num_envs, nd = (size_t)TG_MAX_DOF * n;
+    if (dev_alloc(c, b.q, nd * 8) || dev_alloc(c, b.qd, nd * 8) || dev_alloc(c, b.qd_target, nd * 8) || dev_alloc(c, b.tcp_pos, 3 * n * 8) ||
+        dev_alloc(c, b.tcp_rpy, 3 * n * 8) || dev_alloc(c, b.edge_ang, n * 8) || dev_alloc(c, b.embed, n * 8) || dev_alloc(c, b.edge_sc, 2 * n * 8) ||
+        dev_alloc(c, b.stim_xform, 12 * n * 4) || dev_alloc(c, b.step_count, n * 4) || dev_alloc(c, b.reset_ticks, n * 4) || dev_alloc(c, b.licence, n * 4) ||
+        dev_alloc(c, b.trig_sc, 16 * n * 8) || dev_alloc(c, b.rng, n * 8))
+        return -2;
+    if (cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO &&   // (heights / surf_zoff: the env state's own, the entry's surface goes to the spare third)
+        (dev_alloc(c, b.dir, 2 * n * 8) || dev_alloc(c, b.goal, 3 * n * 8) || dev_alloc(c, b.hsel, n) || dev_alloc(c, b.accum, n * 8) ||
+         dev_alloc(c, b.noise_seed, n * 8) || (c->st.feature && dev_alloc(c, b.feature, 12 * n * 4))))
+        return -2;
+    if (dev_alloc(c, x.tag, n * 8) || dev_alloc(c, x.rng_in, n * 8) || dev_alloc(c, x.stats, 16) || dev_alloc(c, x.need, n) || dev_alloc(c, x.late, n) ||
+        dev_alloc(c, x.swapped, n))
+        return -2;
+    int lo = 0, hi = 0;
+    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);   // lo = the least priority
+    TG_HIP(hipStreamCreateWithPriority(&c->bank_stream, hipStreamNonBlocking, lo));
+    TG_HIP(hipEventCreateWithFlags(&c->ev_bank, hipEventDisableTiming)); TG_HIP(hipEventCreateWithFlags(&c->ev_bank_done, hipEventDisableTiming));
+    for (int k = 0; k < tg_ctx::kBankRing; ++k) TG_HIP(hipEventCreateWithFlags(&c->ev_bank_ring[k], hipEventDisableTiming));   // the refill's pacing markers (bank_refill)
+    x.enabled = 1;
+    c->bank_mode = want;
+    const BankDev hb{c->bk, c->aux};
+    return dev_upload(c, c->d_bank, &hb, sizeof hb);
+}
+
+// development builds: the launch-start stamps of the last 500 steps (TG_TL_STAMPS), k_step's phase stamps (TG_KSTEP_STAMPS)
+static void print_debug_stamps(tg_ctx* c) {
+    (void)c;
 #ifdef TG_TL_STAMPS
     if (c->st.tl) {
         std::vector<unsigned long long> h(4 * 8192 + 4);
@@ -1041,35 +992,68 @@ int tg_destroy(tg_ctx* c) {
 #ifdef TG_KSTEP_STAMPS
     { unsigned long long h[16]; if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_kstep_stamps), sizeof h) == hipSuccess) { fprintf(stderr, "k_step stamps (cycles from start, full=%llu):", h[15]); for (int i = 1; i < 13; ++i) fprintf(stderr, " [%d] %lld", i, (long long)(h[i] - h[0])); fprintf(stderr, "\n"); } }
 #endif
+}
+
+extern "C" {
+
+const char* tg_last_error(void) { return g_err.c_str(); }
+int tg_abi_version(void) { return TG_ABI_VERSION; }
+
+static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sensor* sensor, const tg_mesh* stim, tg_ctx** out);
+int tg_create(const tg_config* cfg, const tg_robot* robot, const tg_sensor* sensor, const tg_mesh* stim, tg_ctx** out) {
+    if (!out) return fail(-1, "tg_create: NULL argument");
+    *out = nullptr;
+    const int rc = create_impl(cfg, robot, sensor, stim, out);
+    if (rc != 0 && *out) {               // a failure half way: the one place that releases the context and every device allocation made so far
+        const std::string keep = g_err;
+        tg_destroy(*out);
+        *out = nullptr;
+        g_err = keep;
+    }
+    return rc;
+}
+static int create_impl(const tg_config* cfg, const tg_robot* robot, const tg_sensor* sensor, const tg_mesh* stim, tg_ctx** out) {
+    HostConsts hc;
+    if (int rc = check_config(cfg, robot, sensor, stim, hc)) return rc;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
+        return fail(-3, "tg_create: no HIP device visible — the tactile-env step has no CPU fallback");
+    TG_HIP(hipSetDevice(cfg->device));
+    tg_ctx* c = new tg_ctx();
+    *out = c;                            // owned by tg_create's guard from here on: every step below only returns its error
+    c->cfg = *cfg; c->robot = *robot; c->H = sensor->image_h; c->W = sensor->image_w;
+    if (int rc = create_streams(c)) return rc;
+    if (int rc = upload_consts(c, hc)) return rc;
+    if (int rc = alloc_env_state(c)) return rc;
+    if (int rc = upload_sensor_tables(c, sensor)) return rc;
+    switch (cfg->env_kind) {
+        case TG_ENV_OBJECT_BALANCE: if (int rc = alloc_balance(c)) return rc; break;
+        case TG_ENV_OBJECT_ROLL: if (int rc = alloc_roll(c)) return rc; break;
+        case TG_ENV_OBJECT_PUSH: if (int rc = alloc_push(c)) return rc; break;
+        default: break;
+    }
+    if (int rc = cfg->env_kind == TG_ENV_SURFACE_FOLLOW_AUTO ? alloc_surface(c) : upload_stimulus(c, stim)) return rc;
+    if (int rc = alloc_outputs(c)) return rc;
+    if (int rc = make_raster_tables(c, sensor)) return rc;
+    if (int rc = plan_step(c)) return rc;
+    return alloc_reset_bank(c);
+}
+
+int tg_destroy(tg_ctx* c) {
+    if (!c) return 0;
+    (void)hipSetDevice(c->cfg.device);
+    (void)hipStreamSynchronize(c->stream);
+    drain_events(c);
+    if (c->scene_on) scene_debug_stats();
+    raster_debug_stats();
+    print_debug_stamps(c);
     // nothing of this context may still be running when its arrays go (the refill stream reads st.rng and writes the bank)
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
-    if (c->bank_stream) (void)hipStreamSynchronize(c->bank_stream);
-    for (int k = 0; k < 2; ++k) if (c->drawn_ext[k]) (void)hipFree(c->drawn_ext[k]);
-    if (c->d_draw) (void)hipFree(c->d_draw);
-    if (c->d_bp) (void)hipFree(c->d_bp);
-    if (c->d_bp_hull) (void)hipFree(c->d_bp_hull);
-    if (c->d_bp_out) (void)hipFree(c->d_bp_out);
-    if (c->d_bp_tot) (void)hipFree(c->d_bp_tot);
-    if (c->d_kt) (void)hipFree(c->d_kt);
-    if (c->d_kt_acc) (void)hipFree(c->d_kt_acc);
-    State& s = c->st;
-    void* ptrs[] = {c->d_robot, c->d_const, s.q, s.qd, s.qd_target, s.tcp_pos, s.tcp_rpy, s.edge_ang, s.embed, s.stim_xform, s.term_xform,
-                    s.step_count, s.reset_ticks, s.licence, s.sweeps, s.tmpl_stats, s.trig_sc, s.edge_sc, s.rng, s.dir, s.goal, s.heights, s.hsel, s.accum, s.surf_zoff, s.noise_seed, s.body_pos, s.body_rot, s.body_v, s.body_w, s.ext_pos, s.gravity, s.ext_pending, s.ball, s.dish, const_cast<double*>(s.spin_hulls), s.reset_tmpl, s.traj, s.obj_mass, s.goal_id, s.contact_code, s.term_feature, s.mani, const_cast<void*>(s.tip_verts), c->d_nodef_dep, c->d_nodef_gray, c->d_border, c->d_verts, c->d_soup, c->d_tris,
-                    c->d_obs, c->d_term, c->d_mask, c->d_actions, c->d_scene_verts, c->d_scene_xf, c->d_scene_spheres, c->d_scene_tris, c->d_scene_attr, c->d_scene_local, c->d_scene_static, c->d_scene_chunks, c->d_vis, c->d_vis_term, c->d_oracle, c->d_oracle_term, c->d_int_idx, c->d_int_rank, c->d_tile_tmpl, c->d_episode, c->d_block_tables};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (void* p : {(void*)c->d_stack, (void*)c->d_stack_term, (void*)c->d_stack_rec, (void*)c->d_stack_vec[0], (void*)c->d_stack_vec[1],
-                    (void*)c->d_stack_vec_term[0], (void*)c->d_stack_vec_term[1], (void*)c->d_vstack, (void*)c->d_vstack_term}) if (p) (void)hipFree(p);
-    if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); }
-    if (c->bank_stream) { (void)hipStreamSynchronize(c->bank_stream); (void)hipStreamDestroy(c->bank_stream); }
-    if (c->ev_bank) (void)hipEventDestroy(c->ev_bank);
-    if (c->ev_bank_done) (void)hipEventDestroy(c->ev_bank_done);
-    for (hipEvent_t& e : c->ev_bank_ring) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (c->h_rows) { (void)hipHostFree(c->h_rows); c->h_rows = nullptr; }
-    for (void* p_ : c->bank_allocs) (void)hipFree(p_);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+    for (hipStream_t s : {c->stream, c->aux_stream, c->bank_stream}) if (s) (void)hipStreamSynchronize(s);
+    for (void* p : c->dev_allocs) (void)hipFree(p);
+    if (c->h_rows) (void)hipHostFree(c->h_rows);     // (pinned host memory: not in the list)
+    for (hipStream_t s : {c->aux_stream, c->bank_stream, c->own_stream}) if (s) (void)hipStreamDestroy(s);
+    for (hipEvent_t e : {c->ev_bank, c->ev_bank_done, c->ev_fork, c->ev_join}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_bank_ring) if (e) (void)hipEventDestroy(e);
     delete c;
     return 0;
 }
@@ -1243,7 +1227,7 @@ int tg_step(tg_ctx* c, const float* actions, int32_t on_device) {
 int tg_step_random(tg_ctx* c, uint64_t seed, uint64_t first_draw, int32_t restart) {
     if (!c) return fail(-1, "tg_step_random: NULL argument");
     TG_ENTER(c);
-    if (!c->d_draw) { TG_HIP(hipMalloc(&c->d_draw, tg::kDrawWords * 8)); TG_HIP(hipMemset(c->d_draw, 0, tg::kDrawWords * 8)); restart = 1; }
+    if (!c->d_draw) { if (int rc = dev_alloc(c, c->d_draw, tg::kDrawWords * 8)) return rc; restart = 1; }
     if (restart || seed != c->random_seed) {
         const unsigned long long h[4] = {first_draw, seed, 0ull, 0ull};    // the next step uses draw first_draw + 1
         TG_HIP(hipMemcpyAsync(c->d_draw, h, 32, hipMemcpyHostToDevice, c->stream));
@@ -1291,8 +1275,9 @@ int tg_set_obs_targets(tg_ctx* c, int32_t count, void* const* dev_ptrs) {
         c->obs_ext[k] = k < count ? (uint8_t*)dev_ptrs[k] : nullptr;
         if (k < count && c->rp.drawn != nullptr && regions == 0) return fail(-3, "tg_set_obs_targets: a changed-block record without 128-pixel regions (internal)");
         if (k < count && c->rp.drawn != nullptr) {   // a changed-block record of its own: nothing in that buffer is known to hold the untouched-sensor image
-            if (!c->drawn_ext[k]) TG_HIP(hipMalloc(&c->drawn_ext[k], (size_t)c->cfg.num_envs * regions * 8));
-            TG_HIP(hipMemset(c->drawn_ext[k], 0xFF, (size_t)c->cfg.num_envs * regions * 8));
+            const size_t bytes = (size_t)c->cfg.num_envs * regions * 8;
+            if (!c->drawn_ext[k] && dev_alloc(c, c->drawn_ext[k], bytes, kNoFill)) return -2;
+            TG_HIP(hipMemset(c->drawn_ext[k], 0xFF, bytes));
         }
     }
     return 0;
@@ -1329,14 +1314,15 @@ int tg_unpack_interior(tg_ctx* c, const void* src_dev, int32_t n_images, void* d
     TG_HIP(hipGetLastError());
     return 0;
 }
+// the observation_mode "oracle" vectors [n][34], allocated on first use (zeroed)
+static int need_oracle(tg_ctx* c, float*& buf) { return buf ? 0 : dev_alloc(c, buf, (size_t)c->cfg.num_envs * 34 * sizeof(float)); }
 int tg_enable_oracle_obs(tg_ctx* c) {
     if (!c) return fail(-1, "NULL ctx");
     if (c->stack_n > 1 && !c->oracle_every_step) return fail(-1, "tg_enable_oracle_obs: call it before tg_set_frame_stack");
     TG_ENTER(c);
-    if (!c->d_oracle) TG_HIP(hipMalloc(&c->d_oracle, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
-    if (!c->d_oracle_term) TG_HIP(hipMalloc(&c->d_oracle_term, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
-    TG_HIP(hipMemset(c->d_oracle, 0, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
-    TG_HIP(hipMemset(c->d_oracle_term, 0, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
+    for (float* buf : {c->d_oracle, c->d_oracle_term})    // enabled again: the rows start from zero
+        if (buf) TG_HIP(hipMemset(buf, 0, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
+    if (need_oracle(c, c->d_oracle) || need_oracle(c, c->d_oracle_term)) return -2;
     c->oracle_every_step = true;
     return 0;
 }
@@ -1358,7 +1344,7 @@ int tg_get_obs_oracle(tg_ctx* c, void** p, int32_t* dim) {
     if (!c || !p) return fail(-1, "NULL argument");
     TG_ENTER(c);
     const int d = oracle_dim(c);
-    if (!c->d_oracle) TG_HIP(hipMalloc(&c->d_oracle, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
+    if (int rc = need_oracle(c, c->d_oracle)) return rc;
     if (!c->oracle_every_step) oracle_draw(c, c->d_oracle);     // (enabled: tg_step / tg_reset have already written it)
     TG_HIP(hipGetLastError());
     *p = c->d_oracle;
@@ -1426,27 +1412,18 @@ static int set_scene_impl(tg_ctx* c, const tg_scene* sc) {
     std::vector<uint32_t> tri_local;
     build_scene_chunks(sc->verts, tris.data(), attr.data(), sc->n_tris, chunks, cverts, tri_local);
     if (chunks.size() > 8192) return fail(-1, "tg_set_scene: too many triangle chunks");
-    TG_HIP(hipMalloc(&c->d_scene_chunks, chunks.size() * sizeof(SceneChunk)));
-    TG_HIP(hipMemcpy(c->d_scene_chunks, chunks.data(), chunks.size() * sizeof(SceneChunk), hipMemcpyHostToDevice));
+    if (dev_upload(c, c->d_scene_chunks, chunks.data(), chunks.size() * sizeof(SceneChunk)) || dev_upload(c, c->d_scene_verts, cverts.data(), cverts.size() * 4, 16) ||
+        dev_upload(c, c->d_scene_tris, tris.data(), (size_t)sc->n_tris * 12) || dev_upload(c, c->d_scene_local, tri_local.data(), (size_t)sc->n_tris * 4) ||
+        dev_upload(c, c->d_scene_attr, attr.data(), (size_t)sc->n_tris * 4) || dev_alloc(c, c->d_scene_xf, n * n_frames * 12 * 4) ||
+        dev_alloc(c, c->d_vis, n * img) || dev_alloc(c, c->d_vis_term, n * img))
+        return -2;
     P.chunks = c->d_scene_chunks; P.n_chunks = (int)chunks.size();
-    TG_HIP(hipMalloc(&c->d_scene_verts, cverts.size() * 4 + 16)); TG_HIP(hipMalloc(&c->d_scene_tris, (size_t)sc->n_tris * 12));
-    TG_HIP(hipMalloc(&c->d_scene_local, (size_t)sc->n_tris * 4));
-    TG_HIP(hipMalloc(&c->d_scene_attr, (size_t)sc->n_tris * 4)); TG_HIP(hipMalloc(&c->d_scene_xf, n * n_frames * 12 * 4));
-    TG_HIP(hipMalloc(&c->d_vis, n * img)); TG_HIP(hipMalloc(&c->d_vis_term, n * img));
-    TG_HIP(hipMemcpy(c->d_scene_verts, cverts.data(), cverts.size() * 4, hipMemcpyHostToDevice));
-    TG_HIP(hipMemcpy(c->d_scene_local, tri_local.data(), (size_t)sc->n_tris * 4, hipMemcpyHostToDevice));
-    TG_HIP(hipMemcpy(c->d_scene_tris, tris.data(), (size_t)sc->n_tris * 12, hipMemcpyHostToDevice));
-    TG_HIP(hipMemcpy(c->d_scene_attr, attr.data(), (size_t)sc->n_tris * 4, hipMemcpyHostToDevice));
-    TG_HIP(hipMemset(c->d_vis, 0, n * img)); TG_HIP(hipMemset(c->d_vis_term, 0, n * img));
     P.verts = c->d_scene_verts; P.tris = c->d_scene_tris; P.tri_attr = c->d_scene_attr; P.tri_local = c->d_scene_local;
     {   // the env's translucent visuals (goal indicator / trajectory markers), one slot list per env, filled by k_scene_xf
         const int kind = c->cfg.env_kind;
         P.n_spheres = 1 + (kind == TG_ENV_OBJECT_PUSH ? c->cfg.traj_n_points : (kind == TG_ENV_OBJECT_BALANCE ? 0 : 1));   // slot 0: the arm's TCP marker
         if (P.n_spheres > 16) return fail(-1, "tg_set_scene: more than 16 trajectory markers");
-        if (P.n_spheres > 0) {
-            TG_HIP(hipMalloc(&c->d_scene_spheres, n * (size_t)P.n_spheres * 8 * 4));
-            TG_HIP(hipMemset(c->d_scene_spheres, 0, n * (size_t)P.n_spheres * 8 * 4));
-        }
+        if (P.n_spheres > 0 && dev_alloc(c, c->d_scene_spheres, n * (size_t)P.n_spheres * 8 * 4)) return -2;
         P.spheres = c->d_scene_spheres;
     }
     if (scene_prepare(P) != 0) return fail(-1, "tg_set_scene: the scene's chunk list does not fit the workgroup's LDS (or hipFuncSetAttribute failed)");
@@ -1457,7 +1434,7 @@ static int set_scene_impl(tg_ctx* c, const tg_scene* sc) {
             for (int cc = 0; cc < 3; ++cc) xf0[3 * r + cc] = (float)(V.R[3 * r + 0] * I[cc] + V.R[3 * r + 1] * I[3 + cc] + V.R[3 * r + 2] * I[6 + cc]);
             xf0[9 + r] = (float)(V.R[3 * r + 0] * z[0] + V.R[3 * r + 1] * z[1] + V.R[3 * r + 2] * z[2] + V.t[r]);
         }
-        TG_HIP(hipMalloc(&c->d_scene_static, (size_t)W * H * 8));
+        if (int rc = dev_alloc(c, c->d_scene_static, (size_t)W * H * 8, kNoFill)) return rc;   // (launch_scene_static writes every key)
         TG_HIP(hipMemcpy(c->d_scene_xf, xf0.data(), xf0.size() * 4, hipMemcpyHostToDevice));
         launch_scene_static(P, c->d_scene_xf, c->d_scene_static, c->stream);
         TG_HIP(hipStreamSynchronize(c->stream));
@@ -1477,12 +1454,9 @@ int tg_set_scene(tg_ctx* c, const tg_scene* sc) {
     if (rc != 0 && c && !c->scene_on) {     // a failed set-up leaves nothing behind: a retry starts from null pointers, nothing leaks
         const std::string keep = tg_last_error();
         (void)hipSetDevice(c->cfg.device);
-        void** ptrs[] = {(void**)&c->d_scene_chunks, (void**)&c->d_scene_verts, (void**)&c->d_scene_tris, (void**)&c->d_scene_local, (void**)&c->d_scene_attr,
-                         (void**)&c->d_scene_xf, (void**)&c->d_vis, (void**)&c->d_vis_term, (void**)&c->d_scene_static, (void**)&c->d_scene_spheres};
-        for (void** p : ptrs) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
+        dev_release(c, c->d_scene_chunks); dev_release(c, c->d_scene_verts); dev_release(c, c->d_scene_tris); dev_release(c, c->d_scene_local);
+        dev_release(c, c->d_scene_attr); dev_release(c, c->d_scene_xf); dev_release(c, c->d_vis); dev_release(c, c->d_vis_term);
+        dev_release(c, c->d_scene_static); dev_release(c, c->d_scene_spheres);
         (void)hipGetLastError();
         tg::report_error(rc, keep.c_str());
     }
@@ -1627,9 +1601,8 @@ int tg_copy_obs_rows(tg_ctx* c, int32_t visual, int32_t terminal, const int32_t*
 
 // ---- frame stack (VecFrameStack on the device; tg_stack.hip) ----
 static void free_stack(tg_ctx* c) {
-    for (void** p : {(void**)&c->d_stack, (void**)&c->d_stack_term, (void**)&c->d_stack_rec, (void**)&c->d_stack_vec[0], (void**)&c->d_stack_vec[1],
-                     (void**)&c->d_stack_vec_term[0], (void**)&c->d_stack_vec_term[1], (void**)&c->d_vstack, (void**)&c->d_vstack_term})
-        if (*p) { (void)hipFree(*p); *p = nullptr; }
+    dev_release(c, c->d_stack); dev_release(c, c->d_stack_term); dev_release(c, c->d_stack_rec); dev_release(c, c->d_vstack); dev_release(c, c->d_vstack_term);
+    for (int k = 0; k < 2; ++k) { dev_release(c, c->d_stack_vec[k]); dev_release(c, c->d_stack_vec_term[k]); }
     c->stack_vec_dim[0] = c->stack_vec_dim[1] = 0;
     c->stack_n = 1;
 }
@@ -1642,23 +1615,19 @@ static int alloc_stacks(tg_ctx* c, int n, int cf) {
     const size_t envs = (size_t)c->cfg.num_envs;
     if (n > 1) {
         const size_t img = envs * c->H * c->W * n, rec = envs * (c->H / 16) * (c->W / 16);   // (the same bytes in either layout)
-        TG_HIP(hipMalloc(&c->d_stack, img)); TG_HIP(hipMalloc(&c->d_stack_term, img)); TG_HIP(hipMalloc(&c->d_stack_rec, rec));
-        TG_HIP(hipMemset(c->d_stack, 0, img)); TG_HIP(hipMemset(c->d_stack_term, 0, img));
-        TG_HIP(hipMemset(c->d_stack_rec, 0, rec));   // no slot holds the template: the first update writes every block
+        if (dev_alloc(c, c->d_stack, img) || dev_alloc(c, c->d_stack_term, img) || dev_alloc(c, c->d_stack_rec, rec)) return -2;   // rec 0: no slot holds the template, the first update writes every block
         c->stack_vec_dim[0] = c->oracle_every_step ? oracle_dim(c) : 0;
         c->stack_vec_dim[1] = env_has_feature(c->cfg.env_kind) ? feature_dim(c) : 0;
         for (int k = 0; k < 2; ++k) {
             if (!c->stack_vec_dim[k]) continue;
             const size_t b = envs * c->stack_vec_dim[k] * n * sizeof(float);
-            TG_HIP(hipMalloc(&c->d_stack_vec[k], b)); TG_HIP(hipMalloc(&c->d_stack_vec_term[k], b));
-            TG_HIP(hipMemset(c->d_stack_vec[k], 0, b)); TG_HIP(hipMemset(c->d_stack_vec_term[k], 0, b));
+            if (dev_alloc(c, c->d_stack_vec[k], b) || dev_alloc(c, c->d_stack_vec_term[k], b)) return -2;
         }
         c->stack_n = n;
     }
     if (c->scene_every_step && (n > 1 || cf)) {      // the visual observation modes
         const size_t b = envs * c->scene.H * c->scene.W * 3 * n;
-        TG_HIP(hipMalloc(&c->d_vstack, b)); TG_HIP(hipMalloc(&c->d_vstack_term, b));
-        TG_HIP(hipMemset(c->d_vstack, 0, b)); TG_HIP(hipMemset(c->d_vstack_term, 0, b));
+        if (dev_alloc(c, c->d_vstack, b) || dev_alloc(c, c->d_vstack_term, b)) return -2;
     }
     TG_HIP(hipDeviceSynchronize());
     return 0;

@@ -66,8 +66,7 @@ int tg_set_broadphase(tg_ctx* c, const tg_broadphase* g) {
     if (!c) return fail(-1, "NULL argument");
     TG_ENTER(c);
     TG_HIP(hipStreamSynchronize(c->stream));
-    if (c->d_bp) { (void)hipFree(c->d_bp); c->d_bp = nullptr; }
-    if (c->d_bp_hull) { (void)hipFree(c->d_bp_hull); c->d_bp_hull = nullptr; }
+    dev_release(c, c->d_bp); dev_release(c, c->d_bp_hull);
     c->bp_every_step = false;
     if (!g) return 0;
     if (g->n_hull_verts < 0 || (g->n_hull_verts > 0 && !g->hull_verts) || !(g->margin >= 0.0) || !(g->sphere_half > 0.0))
@@ -88,15 +87,12 @@ int tg_set_broadphase(tg_ctx* c, const tg_broadphase* g) {
     h.margin = g->margin; h.hull_margin = g->hull_margin; h.sphere_half = g->sphere_half; h.ball_radius = g->ball_radius;
     for (int k = 0; k < 3; ++k) h.stim_pos[k] = c->cfg.stim_pos[k];
     h.table_slot = 16; h.has_ball = c->st.ball != nullptr;
-    const size_t hb = (size_t)std::max(g->n_hull_verts, 1) * 3 * 8;
-    TG_HIP(hipMalloc(&c->d_bp_hull, hb));
-    if (g->n_hull_verts > 0) TG_HIP(hipMemcpy(c->d_bp_hull, g->hull_verts, (size_t)g->n_hull_verts * 3 * 8, hipMemcpyHostToDevice));
+    if (int rc = dev_upload(c, c->d_bp_hull, g->hull_verts, (size_t)g->n_hull_verts * 3 * 8, g->n_hull_verts > 0 ? 0 : 24)) return rc;
     h.hull = c->d_bp_hull;
-    TG_HIP(hipMalloc(&c->d_bp, sizeof h)); TG_HIP(hipMemcpy(c->d_bp, &h, sizeof h, hipMemcpyHostToDevice));
+    if (int rc = dev_upload(c, c->d_bp, &h, sizeof h)) return rc;
     const size_t ob = (size_t)3 * c->cfg.num_envs * 4;
-    if (!c->d_bp_out) TG_HIP(hipMalloc(&c->d_bp_out, ob));
-    if (!c->d_bp_tot) TG_HIP(hipMalloc(&c->d_bp_tot, 3 * 8));
-    TG_HIP(hipMemset(c->d_bp_out, 0, ob)); TG_HIP(hipMemset(c->d_bp_tot, 0, 3 * 8));
+    if ((!c->d_bp_out && dev_alloc(c, c->d_bp_out, ob, kNoFill)) || (!c->d_bp_tot && dev_alloc(c, c->d_bp_tot, 3 * 8, kNoFill))) return -2;
+    TG_HIP(hipMemset(c->d_bp_out, 0, ob)); TG_HIP(hipMemset(c->d_bp_tot, 0, 3 * 8));     // (kept across guards: results and totals start from zero with each)
     c->bp_every_step = g->every_step != 0;
     return 0;
 }
@@ -295,11 +291,9 @@ int tg_profile_enable(tg_ctx* c, int32_t enable) {
         // slots for the largest launch of this context: a render of every env's image in 64-row tiles, two passes, four wavefronts each
         const size_t n = (size_t)c->cfg.num_envs;
         c->kt_slots = std::max<size_t>(n + 64, (size_t)((c->rp.W + 63) / 64) * (size_t)((c->rp.H + 63) / 64) * n * 8);
-        TG_HIP(hipMalloc(&c->d_kt, c->kt_slots * 16));
-        TG_HIP(hipMalloc(&c->d_kt_acc, 8 * 16));
         std::vector<unsigned long long> init(c->kt_slots * 2);
         for (size_t i = 0; i < c->kt_slots; ++i) { init[2 * i] = ~0ull; init[2 * i + 1] = 0ull; }
-        TG_HIP(hipMemcpy(c->d_kt, init.data(), c->kt_slots * 16, hipMemcpyHostToDevice));
+        if (dev_upload(c, c->d_kt, init.data(), c->kt_slots * 16) || dev_alloc(c, c->d_kt_acc, 8 * 16)) return -2;
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->cfg.device) == hipSuccess && khz > 0) c->wall_clock_khz = (double)khz;
     }

@@ -2,6 +2,8 @@
 // dispatch on the physics variant and the env-kernel launch helper, the host -> device translation of a robot description.  tg_api.hip (configuration, creation, the step / reset launch sequences, the reset
 // bank), tg_api_state.hip (state read-back, inspection, profiling, the broadphase guard's entry points) and tg_api_ops.hip (the
 // context-free function-level entry points) include it; round 6 split them out of one 2 400-line file.
+// Device memory of a context has one owner, tg_ctx::dev_allocs: dev_alloc (allocate into a field, zero-filled unless told otherwise),
+// dev_upload (allocate and copy a host block) and dev_release (free one field early) below, beside DevBuf; tg_destroy frees the list.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -209,6 +211,7 @@ struct StepPlan {
 }  // namespace tg
 
 struct tg_ctx {
+    std::vector<void*> dev_allocs;         // every device allocation this context owns (dev_alloc / dev_upload / dev_release below); tg_destroy frees them
     tg_config cfg;
     tg_robot robot;
     int H, W, act_dim;
@@ -273,7 +276,6 @@ struct tg_ctx {
     long long bank_steps = 0;
     hipStream_t bank_stream = nullptr;
     hipEvent_t ev_bank = nullptr, ev_bank_done = nullptr;
-    std::vector<void*> bank_allocs;
     void* d_bank = nullptr;            // BankDev {bk, aux} in device memory (k_reset's argument)
     // profiling
     bool profile = false;          // tg_profile_enable(1): HIP event pairs around every launch class
@@ -370,11 +372,33 @@ template <typename T> static int fetch_soa(tg_ctx* c, const T* dev, int fields, 
     return 0;
 }
 
-struct DevBuf {
+struct DevBuf {                       // a temporary of one call (tg_get_state, the function-level entry points): not context memory
     void* p = nullptr;
     ~DevBuf() { if (p) (void)hipFree(p); }
     int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8) == hipSuccess ? 0 : -1; }
 };
+// Device memory that lives with a context: allocated into one of its pointer fields and entered in tg_ctx::dev_allocs, which tg_destroy frees - a
+// new buffer needs no line anywhere else.  One hipMalloc per field, as ever: the kernels see the addresses and sizes they always saw.  Not in the
+// list: the pinned host block tg_ctx::h_rows, DevBuf temporaries, and what tg_exchange.hip, tg_api_ops.hip and the test units allocate.
+constexpr int kNoFill = -1;
+template <typename P> static int dev_alloc(tg_ctx* c, P*& field, size_t bytes, int fill = 0) {   // filled with the byte `fill`; kNoFill: left as it comes
+    void* p = nullptr;
+    TG_HIP(hipMalloc(&p, bytes));
+    if (p) c->dev_allocs.push_back(p);
+    field = (P*)p;
+    if (p && fill != kNoFill) TG_HIP(hipMemset(p, fill, bytes));
+    return 0;
+}
+template <typename P> static int dev_upload(tg_ctx* c, P*& field, const void* host, size_t bytes, size_t pad = 0) {   // `pad` bytes behind the block for vector reads past its end
+    if (int rc = dev_alloc(c, field, bytes + pad, kNoFill)) return rc;
+    TG_HIP(hipMemcpy((void*)field, host, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+template <typename P> static void dev_release(tg_ctx* c, P*& field) {   // what is replaced while the context lives: free, take off the list, null the field
+    const auto it = std::find(c->dev_allocs.begin(), c->dev_allocs.end(), (void*)field);
+    if (field && it != c->dev_allocs.end()) { (void)hipFree(*it); c->dev_allocs.erase(it); }
+    field = nullptr;
+}
 
 template <typename T> static int upload_robot(const tg_robot* robot, DevBuf& buf) {
     DevRobot<T> dr;

@@ -52,6 +52,32 @@ def test_no_gpu_fails_loudly(edge_modes):
         tg.make_vec("edge_follow-v0", num_envs=2, max_steps=10, image_size=[128, 128], env_modes=edge_modes)
 
 
+def _raw_create(cfg, robot, sensor, mesh):
+    """tg_create as a C caller of the ABI makes it (no build_config check in front): (return code, tg_last_error(), the out pointer)."""
+    import ctypes as C
+    from tactile_gym_amd import _capi
+    L = _capi.lib()
+    ctx = C.c_void_p(0xdead)                  # must come back null
+    rc = L.tg_create(C.byref(cfg), C.byref(robot), C.byref(sensor.struct), C.byref(mesh.struct), C.byref(ctx))
+    return rc, L.tg_last_error().decode(), ctx.value
+
+
+def test_rejected_configuration_reports_itself_and_leaves_no_context(edge_modes):
+    """A configuration that build_env_const rejects is refused before the device is touched and before a context exists: -1 with its own message
+    (with or without a GPU), the out pointer null - nothing is left for anybody to free, or to free twice."""
+    from tactile_gym_amd.rl_envs import edge_follow, object_push
+    cfg, robot, sensor, mesh, _ = edge_follow.build_config(2, 10, [128, 128], edge_modes)
+    cfg.movement_mode = 99
+    rc, msg, ctx = _raw_create(cfg, robot, sensor, mesh)
+    assert rc == -1 and "Incorrect movement mode" in msg and not ctx, (rc, msg, ctx)
+    push_modes = dict(movement_mode="TyRz", control_mode="TCP_velocity_control", rand_init_orn=False, rand_obj_mass=False, traj_type="simplex",
+                      observation_mode="tactile", reward_mode="dense", arm_type="ur5", tactile_sensor_name="tactip")
+    cfg, robot, sensor, mesh, _, _tip = object_push.build_config(2, 10, [128, 128], push_modes)
+    cfg.traj_n_points = 1
+    rc, msg, ctx = _raw_create(cfg, robot, sensor, mesh)
+    assert rc == -1 and "traj_n_points" in msg and not ctx, (rc, msg, ctx)
+
+
 def test_constructor_kwarg_errors(edge_modes):
     from tactile_gym_amd.rl_envs.edge_follow import build_config
     bad = dict(edge_modes)
