@@ -68,6 +68,12 @@ int tg_selftest_render(const tg_sensor* sensor, const tg_mesh* mesh, int32_t row
                        const float* zoff, int32_t n, const float* xf, int32_t kernel, int32_t skip_quad_reject, int32_t fills_view,
                        int32_t backface_cull, const uint8_t* mask, const float* term_xf, const uint8_t* term_mask, uint8_t* term_out,
                        uint8_t* out, int32_t* launched);
+/* How tg_random_translate / tg_random_translate_rows would launch a call (csrc/tg_augment.h: translate_plan, the function the launcher itself
+ * calls): in_dtype TG_AUGMENT_*, the layout, C, H, W, B and the addresses of the input and the output.  *path = 0 per element / 1 staged
+ * through LDS, *chunks = 4096-element chunks per plane, *lds_bytes = dynamic LDS of a workgroup, *launches = kernel launches (B samples at
+ * 2^23 workgroups per launch).  -1 for a shape the call itself refuses.  Host only: needs no device. */
+int tg_selftest_translate_plan(int32_t in_dtype, int32_t channels_first, int32_t C, int32_t H, int32_t W, int64_t B, uint64_t in_addr,
+                               uint64_t out_addr, int32_t* path, int32_t* chunks, int32_t* lds_bytes, int64_t* launches);
 /* The message of the last failing call of this library on the calling thread. */
 const char* tg_selftest_last_error(void);
 

@@ -25,8 +25,6 @@
 namespace tg {
 
 constexpr int kTrThreads = 256;
-constexpr int kTrChunk = 4096;    // output elements per workgroup: 4 float4 per lane
-constexpr int kTrMaxRow = 8192;   // R + S of the staged path: LDS <= (4096 + 8192 + 44) * 4 B = 48.2 KiB
 
 struct TrSample {
     bool apply;
@@ -203,20 +201,12 @@ __global__ __launch_bounds__(kTrThreads) void k_random_translate(TranslateArgs a
 
 template <typename TIN, bool CF>
 static int launch_typed(const TranslateArgs& a, hipStream_t stream) {
-    const int P = CF ? a.C : 1, R = CF ? a.W : a.W * a.C, S = CF ? 1 : a.C;
-    const int64_t HR = (int64_t)a.H * R;
-    const int nchunk = (int)((HR + kTrChunk - 1) / kTrChunk);
-    constexpr int V = 16 / (int)sizeof(TIN);
-    const int vec = HR % V == 0 && !(((uintptr_t)a.in | (uintptr_t)a.out) & 15) && R + S <= kTrMaxRow;
-    const int lds_floats = vec ? (kTrChunk + R + S + 2 * V + 12 + 3) / 4 * 4 : 0;
-    const int64_t per_sample = (int64_t)P * nchunk;
-    const int64_t max_blocks = 1 << 23;                       // grid x * 256 lanes stays below 2^32
-    const int64_t spl = max_blocks / per_sample;
-    if (spl < 1) return -1;
-    for (int64_t b0 = 0; b0 < a.B; b0 += spl) {
-        const int64_t nb = a.B - b0 < spl ? a.B - b0 : spl;
-        hipLaunchKernelGGL((k_random_translate<TIN, CF>), dim3((unsigned)(nb * per_sample)), dim3(kTrThreads), (size_t)lds_floats * 4, stream,
-                           a, b0, nchunk, vec, lds_floats);
+    const TranslatePlan pl = translate_plan((int)sizeof(TIN), CF, a.C, a.H, a.W, (uintptr_t)a.in, (uintptr_t)a.out);
+    if (pl.spl < 1) return -1;
+    for (int64_t b0 = 0; b0 < a.B; b0 += pl.spl) {
+        const int64_t nb = a.B - b0 < pl.spl ? a.B - b0 : pl.spl;
+        hipLaunchKernelGGL((k_random_translate<TIN, CF>), dim3((unsigned)(nb * pl.per_sample)), dim3(kTrThreads), (size_t)pl.lds_floats * 4, stream,
+                           a, b0, pl.nchunk, pl.vec, pl.lds_floats);
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

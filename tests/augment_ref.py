@@ -92,6 +92,46 @@ def warp_f32(x, params, channels_first=True):
     return np.ascontiguousarray(out, dtype=np.float32)
 
 
+def warp_f32_batched(x, params, channels_first=True):
+    """warp_f32 with the loop over samples turned into array operations - per element the same float32 operations in the same order - for
+    batches of millions of tiny images, where a Python loop over samples does not end.  tests/test_augment_paths_cpu.py holds it to warp_f32
+    bit for bit."""
+    xf = np.asarray(x).astype(np.float32)
+    if not channels_first:
+        xf = xf.transpose(0, 3, 1, 2)
+    B, C, H, W = xf.shape
+    prm = np.asarray(params, dtype=np.float32)
+
+    def split(t, n):
+        with np.errstate(invalid="ignore", over="ignore"):
+            m = -(t.astype(np.float64) * n / (n - 1))
+            m = np.where(np.isnan(m), -(n + 2.0), np.minimum(np.maximum(m, -(n + 2.0)), n + 2.0))
+        o = np.floor(m)
+        return o.astype(np.int64), (m - o).astype(np.float32)
+
+    ox, fx = split(prm[:, 1], W)
+    oy, fy = split(prm[:, 2], H)
+    bi = np.arange(B)[:, None, None]
+
+    def tap(dy, dx):
+        yy = np.arange(H)[None, :, None] + (oy + dy)[:, None, None]
+        xx = np.arange(W)[None, None, :] + (ox + dx)[:, None, None]
+        ok = (yy >= 0) & (yy < H) & (xx >= 0) & (xx < W)
+        v = xf[bi, :, np.clip(yy, 0, H - 1), np.clip(xx, 0, W - 1)]                # [B, H, W, C]
+        return np.where(ok[..., None], v, np.float32(0)).transpose(0, 3, 1, 2)
+
+    one = np.float32(1)
+    fx, fy = fx[:, None, None, None], fy[:, None, None, None]
+    h0 = (one - fx) * tap(0, 0) + fx * tap(0, 1)
+    h1 = (one - fx) * tap(1, 0) + fx * tap(1, 1)
+    out = (one - fy) * h0 + fy * h1
+    out = np.where((prm[:, 0] == 0)[:, None, None, None], xf, out)
+    assert out.dtype == np.float32
+    if not channels_first:
+        out = out.transpose(0, 2, 3, 1)
+    return np.ascontiguousarray(out, dtype=np.float32)
+
+
 def warp_kornia(x, params, channels_first=True):
     """kornia's path in float64 on the CPU: theta = [[1, 0, -2 tx / (W - 1)], [0, 1, -2 ty / (H - 1)]] through affine_grid / grid_sample
     (bilinear, zeros, align_corners=False); samples whose apply flag is 0 are the input.  float64 numpy, same layout."""

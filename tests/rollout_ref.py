@@ -74,6 +74,41 @@ def gae_bound(rewards, values, last_values, adv_f64, gamma, gae_lambda):
     return 8 * 2.0 ** -24 * A * (T if gl >= 1 else 1 / (1 - gl))
 
 
+def gae_error(adv32, ret32, adv64, ret64):
+    """The figure gae_bound bounds: max |adv32 - adv64|, and max |ret32 - ret64| less the one rounding of the final last + v."""
+    return max(np.abs(adv32 - adv64).max(), np.abs(ret32 - ret64).max() - 2.0 ** -24 * np.abs(ret64).max())
+
+
+# The shapes and inputs of the GAE kernel's edge tests (tests/test_gpu_rollout_abi.py; tests/test_rollout_cpu.py holds gae_f32 to gae_bound on
+# them): T on both sides of the kernel's blocks of 8 prefetched steps, N on both sides of its workgroups of 64 envs.
+GAE_T = (1, 2, 7, 8, 9, 15, 16, 17, 64, 65)
+GAE_N = (1, 2, 63, 64, 65, 127, 128, 129, 1000)
+GAE_PARAMS = ((0.95, 0.9), (0.99, 0.95), (0.999, 1.0), (0.99, 0.0), (1.0, 0.95))       # (gamma, lambda)
+GAE_STARTS = ("none", "all", "alternating", "first", "last")
+
+
+def gae_edge_inputs(T, N, starts):
+    """(rewards, values, episode_starts, last_values, dones) float32 for one edge case; dones 0 / 1."""
+    rng = np.random.default_rng(1000 * T + N)
+    r = rng.standard_normal((T, N)).astype(np.float32)
+    v = (rng.standard_normal((T, N)) * 5).astype(np.float32)
+    lv = (rng.standard_normal(N) * 5).astype(np.float32)
+    es = np.zeros((T, N), np.float32)
+    d = (rng.random(N) < 0.3).astype(np.float32)
+    if starts == "all":
+        es[:], d[:] = 1.0, 1.0
+    elif starts == "alternating":
+        es[:] = (np.arange(T)[:, None] + np.arange(N)[None, :]) % 2
+    elif starts == "first":
+        es[0] = 1.0
+    elif starts == "last":
+        es[T - 1] = 1.0
+    else:
+        assert starts == "none"
+        d[:] = 0.0
+    return r, v, es, lv, d
+
+
 def flat_rows(indices, T, N):
     """Storage rows t N + n of SB3's flat sample indices i = n T + t."""
     i = np.asarray(indices, dtype=np.int64)

@@ -12,7 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
-from rollout_ref import flat_rows, gae_bound, gae_f32, gae_f64, minibatches, swap_and_flatten  # noqa: E402
+from rollout_ref import (GAE_N, GAE_PARAMS, GAE_STARTS, GAE_T, flat_rows, gae_bound, gae_edge_inputs, gae_error, gae_f32, gae_f64,  # noqa: E402
+                         minibatches, swap_and_flatten)
 
 from tactile_gym_amd import _capi, spaces  # noqa: E402
 
@@ -44,6 +45,23 @@ def test_f32_restatement_within_the_bound_of_sb3_f64(gamma, lam, T, p_start, sca
         print(f"gamma={gamma} lambda={lam} T={T} seed={seed}: max err {err:.3e}, bound {bound:.3e}, ratio {err / bound:.4f}")
         assert a32.dtype == np.float32 and r32.dtype == np.float32
         assert err <= bound, (err, bound)
+
+
+@pytest.mark.parametrize("T", GAE_T)
+def test_f32_restatement_within_the_bound_on_the_edge_shapes(T):
+    """The inputs of tests/test_gpu_rollout_abi.py's GAE matrix: the margin that test grants the device against float64 holds for the
+    restatement itself."""
+    worst = 0.0
+    for N in GAE_N:
+        for starts in GAE_STARTS:
+            r, v, es, lv, d = gae_edge_inputs(T, N, starts)
+            for gamma, lam in GAE_PARAMS:
+                a32, r32 = gae_f32(r, v, es, lv, d, gamma, lam)
+                a64, r64 = gae_f64(r, v, es, lv, d, gamma, lam)
+                err, bound = gae_error(a32, r32, a64, r64), gae_bound(r, v, lv, a64, gamma, lam)
+                worst = max(worst, err / bound)
+                assert err <= bound, (T, N, starts, gamma, lam, err, bound)
+    print(f"T={T}: worst error / bound {worst:.4f}")
 
 
 @pytest.mark.parametrize("gamma,lam,T,p_start,scale", CASES[:4])
