@@ -74,6 +74,47 @@ int tg_selftest_render(const tg_sensor* sensor, const tg_mesh* mesh, int32_t row
  * 2^23 workgroups per launch).  -1 for a shape the call itself refuses.  Host only: needs no device. */
 int tg_selftest_translate_plan(int32_t in_dtype, int32_t channels_first, int32_t C, int32_t H, int32_t W, int64_t B, uint64_t in_addr,
                                uint64_t out_addr, int32_t* path, int32_t* chunks, int32_t* lds_bytes, int64_t* launches);
+/* The scene camera (csrc/tg_scene.hip: k_scene; the product reaches it through tg_set_scene / tg_render_scene) on any triangle set.
+ * tg_selftest_scene_plan - host only, needs no device - runs the product's build_scene_chunks and scene_layout on verts [n_verts][3], tris
+ * [n_tris][3], tri_frame [n_tris] (< 16), tri_rgb [n_tris][3] for a W x H image and reports *plan; the arrays (each may be NULL) receive
+ * chunk_sphere [n_chunks][4] = centre, radius; chunk_table [n_chunks][5] = start, count, frame, vstart, vcount; cverts [n_cverts][3] the
+ * chunk-ordered vertex copies; tris_out [n_tris][3] re-indexed into cverts; tri_local [n_tris] = i0 | i1 << 8 | i2 << 16 relative to vstart;
+ * attr [n_tris] = frame << 24 | r << 16 | g << 8 | b, all in the chunk order.  Size them for n_chunks <= n_tris, n_cverts <= 3 n_tris. */
+typedef struct tg_scene_plan {
+    int32_t n_chunks, n_cverts;
+    int32_t tile_w, tile_h, big_cap, lds_bytes;   /* the launch: tile, capacity of the LDS queue of large triangles, dynamic LDS bytes */
+    int32_t accepted;                              /* 1: scene_prepare takes the scene, 0: it refuses it (too many chunks for the LDS) */
+    int32_t small_area, big_area, huge_area, huge_cap, big_cap_max, chunk, max_chunks, max_spheres, max_frames;   /* kSmallArea ... kMaxFrames */
+} tg_scene_plan;
+int tg_selftest_scene_plan(int32_t n_verts, const float* verts, int32_t n_tris, const int32_t* tris, const uint8_t* tri_frame, const uint8_t* tri_rgb,
+                           int32_t W, int32_t H, tg_scene_plan* plan, float* chunk_sphere, int32_t* chunk_table, float* cverts, int32_t* tris_out,
+                           uint32_t* tri_local, uint32_t* attr);
+/* Draws n images (1..65535) along the product's path: build_scene_chunks, scene_prepare, launch_scene_static when use_static, launch_scene.
+ * The caller gives eye space: xf [n][n_frames][12] are the eye <- frame transforms themselves (R row-major, t) and light_eye the unit vector
+ * towards the light.  THE FRAMES ARE RIGID OR UNIFORMLY SCALED - the kernel's own contract: its chunk cull takes the scale from the norm of one
+ * matrix column.  With use_static the triangles of frame 0 are drawn once from env 0's xf [0] (the product's world frame: the same in every env).
+ * Heightfield (hf_heights NULL: none): drawn in frame n_frames - 1 with hf_rgb; hf_sel NULL: hf_heights [n][rows * cols], hf_zoff [n]; else
+ * hf_heights [3][n][rows * cols], hf_zoff [3][n], hf_sel [n] names each env's third (0..2).  spheres [n][n_spheres][8] (n_spheres <= 16) =
+ * centre in eye space, radius, r, g, b (0..255), alpha (0: slot unused).  out [n][H][W][3] is in / out: an env whose mask byte is 0 (mask NULL:
+ * all drawn) keeps what it held; prev (NULL or [n][H][W][3], in / out) is passed as save_prev: a drawn env's previous image goes there first.
+ * Refused with -1, nothing launched, as tg_set_scene refuses: a side above 128 that is no multiple of 128, a bad projection, more than 16
+ * frames or spheres, an index out of range, a scene that scene_prepare rejects; and n outside 1..65535.  The checks restate tg_set_scene's
+ * (which reads them off a context) with one difference: an empty triangle set (n_tris == 0), which tg_set_scene refuses as an empty scene,
+ * is drawn here - a heightfield or spheres alone. */
+typedef struct tg_scene_test {
+    int32_t image_h, image_w, n_verts, n_tris;
+    const float* verts; const int32_t* tris; const uint8_t* tri_frame; const uint8_t* tri_rgb;
+    int32_t n_frames, use_static;
+    double fov_deg, near_plane, far_plane;
+    float light_eye[3];
+    uint8_t background[3], hf_rgb[3];
+    const double* hf_heights; const float* hf_zoff; const uint8_t* hf_sel;
+    int32_t hf_rows, hf_cols;
+    double hf_scale;
+    const float* spheres;
+    int32_t n_spheres;
+} tg_scene_test;
+int tg_selftest_scene(const tg_scene_test* scene, int32_t n, const float* xf, const uint8_t* mask, uint8_t* out, uint8_t* prev);
 /* The message of the last failing call of this library on the calling thread. */
 const char* tg_selftest_last_error(void);
 

@@ -279,6 +279,20 @@ def _share_torch_hip_runtime():
             pass
 
 
+class TgScenePlan(C.Structure):      # tg_scene_plan (include/tactile_gym_hip_test.h)
+    _fields_ = [(k, C.c_int32) for k in ("n_chunks", "n_cverts", "tile_w", "tile_h", "big_cap", "lds_bytes", "accepted", "small_area", "big_area",
+                                         "huge_area", "huge_cap", "big_cap_max", "chunk", "max_chunks", "max_spheres", "max_frames")]
+
+
+class TgSceneTest(C.Structure):      # tg_scene_test
+    _fields_ = [("image_h", C.c_int32), ("image_w", C.c_int32), ("n_verts", C.c_int32), ("n_tris", C.c_int32),
+                ("verts", _fp), ("tris", C.POINTER(C.c_int32)), ("tri_frame", _u8p), ("tri_rgb", _u8p),
+                ("n_frames", C.c_int32), ("use_static", C.c_int32), ("fov_deg", C.c_double), ("near_plane", C.c_double), ("far_plane", C.c_double),
+                ("light_eye", C.c_float * 3), ("background", C.c_uint8 * 3), ("hf_rgb", C.c_uint8 * 3),
+                ("hf_heights", _dp), ("hf_zoff", _fp), ("hf_sel", _u8p), ("hf_rows", C.c_int32), ("hf_cols", C.c_int32), ("hf_scale", C.c_double),
+                ("spheres", _fp), ("n_spheres", C.c_int32)]
+
+
 # libtactile_gym_hip_test.so (include/tactile_gym_hip_test.h): device self-tests, test infrastructure - tests/ are the only callers
 TEST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtactile_gym_hip_test.so")
 TEST_SYMBOLS = {
@@ -295,6 +309,9 @@ TEST_SYMBOLS = {
                                      C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "tg_selftest_scene_plan": (C.c_int, [C.c_int32, _fp, C.c_int32, C.POINTER(C.c_int32), _u8p, _u8p, C.c_int32, C.c_int32, C.POINTER(TgScenePlan), _fp,
+                                         C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "tg_selftest_scene": (C.c_int, [C.POINTER(TgSceneTest), C.c_int32, _fp, _u8p, _u8p, _u8p]),
     "tg_selftest_last_error": (C.c_char_p, []),
 }
 # raster kernel ids of tg_selftest_render (TG_RK_*)

@@ -37,9 +37,10 @@ cc tg_render_test & p14=$!
 cc tg_stack & p15=$!
 cc tg_augment -ffp-contract=off & p16=$!
 cc tg_rollout -ffp-contract=off & p17=$!
-wait $p1; wait $p2; wait $p3; wait $p4; wait $p5; wait $p6; wait $p7; wait $p8; wait $p9; wait $p10; wait $p11; wait $p12; wait $p13; wait $p14; wait $p15; wait $p16; wait $p17    # each wait returns its job's status: a failed translation unit fails the build (set -e)
+cc tg_scene_test & p18=$!
+wait $p1; wait $p2; wait $p3; wait $p4; wait $p5; wait $p6; wait $p7; wait $p8; wait $p9; wait $p10; wait $p11; wait $p12; wait $p13; wait $p14; wait $p15; wait $p16; wait $p17; wait $p18    # each wait returns its job's status: a failed translation unit fails the build (set -e)
 $HIPCC --offload-arch=gfx950 -shared -fPIC "$OUT/tg_raster.o" "$OUT/tg_noise.o" "$OUT/tg_api.o" "$OUT/tg_contact_wave.o" "$OUT/tg_scene.o" "$OUT/tg_exchange.o" "$OUT/tg_fused.o" "$OUT/tg_broadphase.o" "$OUT/tg_api_state.o" "$OUT/tg_api_ops.o" "$OUT/tg_spin.o" "$OUT/tg_stack.o" "$OUT/tg_augment.o" "$OUT/tg_rollout.o" -o "$OUT/libtactile_gym_hip.so"
 # test infrastructure (include/tactile_gym_hip_test.h): device self-tests of the raster's division / block test and of the wave-mapped GJK / EPA,
-# the render with a chosen kernel (with the product's own raster object)
-$HIPCC --offload-arch=gfx950 -shared -fPIC "$OUT/tg_narrow_test.o" "$OUT/tg_selftest.o" "$OUT/tg_render_test.o" "$OUT/tg_raster.o" -o "$OUT/libtactile_gym_hip_test.so"
+# the render with a chosen kernel (with the product's own raster object), the scene camera on any triangle set (with the product's own tg_scene.o)
+$HIPCC --offload-arch=gfx950 -shared -fPIC "$OUT/tg_narrow_test.o" "$OUT/tg_selftest.o" "$OUT/tg_render_test.o" "$OUT/tg_scene_test.o" "$OUT/tg_raster.o" "$OUT/tg_scene.o" -o "$OUT/libtactile_gym_hip_test.so"
 echo "built $OUT/libtactile_gym_hip.so $OUT/libtactile_gym_hip_test.so"

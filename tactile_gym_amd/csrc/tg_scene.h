@@ -59,6 +59,16 @@ void launch_scene(const SceneParams& P, const float* xf, int n_envs, const uint8
 // One-off: draws the triangles of frame 0 (world: the same for every env, the camera is fixed) and stores their z keys, W * H of them, tile by
 // tile; xf_env0 = any env's [n_frames][12] transforms (only frame 0 is read).
 void launch_scene_static(const SceneParams& P, const float* xf_env0, unsigned long long* static_keys, hipStream_t stream);
+// The launch geometry of a W x H image whose scene has n_chunks chunks - tile, capacity of the LDS queue of large triangles, dynamic LDS -
+// whether the scene fits (scene_prepare refuses it otherwise), and the kernel's constants.  Host only; scene_prepare and both launches call it,
+// and so does the test library (tg_selftest_scene_plan).
+struct SceneLayout {
+    int tw, th, big_cap;
+    size_t lds_bytes;
+    int fits;
+    int small_area, big_area, huge_area, huge_cap, big_cap_max, chunk, max_chunks, max_spheres, max_frames;
+};
+SceneLayout scene_layout(int W, int H, int n_chunks);
 int scene_prepare(const SceneParams& P);   // one-time kernel attributes (large dynamic LDS); call outside stream capture; non-zero: the scene does not fit
 
 void scene_debug_stats();          // -DTG_SCENE_STATS builds: per-workgroup work counters to stderr (development)

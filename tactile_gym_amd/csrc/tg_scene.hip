@@ -403,6 +403,17 @@ LdsLayout lds_layout(int tw, int th, int n_chunks) {
 
 }  // namespace
 
+SceneLayout scene_layout(int W, int H, int n_chunks) {
+    SceneLayout S{};
+    S.tw = W < 128 ? W : 128; S.th = H < 128 ? H : 128;
+    const LdsLayout L = lds_layout(S.tw, S.th, n_chunks);
+    S.big_cap = L.big_cap; S.lds_bytes = L.bytes;
+    S.fits = n_chunks <= kMaxChunks && L.big_cap >= 64;
+    S.small_area = kSmallArea; S.big_area = kBigArea; S.huge_area = kHugeArea; S.huge_cap = kHugeCap; S.big_cap_max = kBigCap;
+    S.chunk = kChunk; S.max_chunks = kMaxChunks; S.max_spheres = kMaxSpheres; S.max_frames = kMaxFrames;
+    return S;
+}
+
 SceneParams make_scene_params(int W, int H, double fov_deg, double near_, double far_) {
     SceneParams P{};
     P.W = W; P.H = H;
@@ -509,9 +520,8 @@ void build_scene_chunks(const float* verts, int32_t* tris, uint32_t* attr, int n
 }
 
 int scene_prepare(const SceneParams& P) {
-    const int tw = P.W < 128 ? P.W : 128, th = P.H < 128 ? P.H : 128;
-    const LdsLayout L = lds_layout(tw, th, P.n_chunks);
-    if (P.n_chunks > kMaxChunks || L.big_cap < 64) return -1;
+    const SceneLayout L = scene_layout(P.W, P.H, P.n_chunks);
+    if (!L.fits) return -1;
     // the attribute belongs to the function (per device), not to a context: another context of this process may launch k_scene with a larger
     // tile, so the limit is only ever raised
     static std::mutex mu;
@@ -519,9 +529,9 @@ int scene_prepare(const SceneParams& P) {
     int dev = 0;
     (void)hipGetDevice(&dev);
     std::lock_guard<std::mutex> lock(mu);
-    if (dev >= 0 && dev < 64 && (int)L.bytes <= raised[dev]) return 0;
-    const int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scene), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes);
-    if (rc == 0 && dev >= 0 && dev < 64) raised[dev] = (int)L.bytes;
+    if (dev >= 0 && dev < 64 && (int)L.lds_bytes <= raised[dev]) return 0;
+    const int rc = (int)hipFuncSetAttribute(reinterpret_cast<const void*>(k_scene), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes);
+    if (rc == 0 && dev >= 0 && dev < 64) raised[dev] = (int)L.lds_bytes;
     return rc;
 }
 
@@ -536,19 +546,19 @@ void scene_debug_stats() {
 void scene_debug_stats() {}
 #endif
 void launch_scene(const SceneParams& P, const float* xf, int n_envs, const uint8_t* mask, uint8_t* out, uint8_t* save_prev, hipStream_t stream) {
-    const int tw = P.W < 128 ? P.W : 128, th = P.H < 128 ? P.H : 128;
+    const SceneLayout L = scene_layout(P.W, P.H, P.n_chunks);
+    const int tw = L.tw, th = L.th;
     dim3 grid((P.W / tw) * (P.H / th), n_envs);
-    const LdsLayout L = lds_layout(tw, th, P.n_chunks);
-    hipLaunchKernelGGL(k_scene, grid, dim3(kThreads), L.bytes, stream, P, xf, mask, out, save_prev, tw, th, L.big_cap, (unsigned long long*)nullptr);
+    hipLaunchKernelGGL(k_scene, grid, dim3(kThreads), L.lds_bytes, stream, P, xf, mask, out, save_prev, tw, th, L.big_cap, (unsigned long long*)nullptr);
 }
 
 void launch_scene_static(const SceneParams& P, const float* xf_env0, unsigned long long* static_keys, hipStream_t stream) {
-    const int tw = P.W < 128 ? P.W : 128, th = P.H < 128 ? P.H : 128;
+    const SceneLayout L = scene_layout(P.W, P.H, P.n_chunks);
+    const int tw = L.tw, th = L.th;
     dim3 grid((P.W / tw) * (P.H / th), 1);
-    const LdsLayout L = lds_layout(tw, th, P.n_chunks);
     SceneParams Q = P;
     Q.static_keys = nullptr;
-    hipLaunchKernelGGL(k_scene, grid, dim3(kThreads), L.bytes, stream, Q, xf_env0, (const uint8_t*)nullptr, (uint8_t*)nullptr, (uint8_t*)nullptr, tw, th, L.big_cap, static_keys);
+    hipLaunchKernelGGL(k_scene, grid, dim3(kThreads), L.lds_bytes, stream, Q, xf_env0, (const uint8_t*)nullptr, (uint8_t*)nullptr, (uint8_t*)nullptr, tw, th, L.big_cap, static_keys);
 }
 
 }  // namespace tg
