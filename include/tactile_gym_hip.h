@@ -650,6 +650,32 @@ int tg_rollout_gae(const float* rewards_dev, const float* values_dev, const floa
                    double gae_lambda, void* hip_stream);
 int tg_rollout_gather(int32_t n_arrays, const void* const* src_dev, void* const* dst_dev, const int64_t* row_bytes, const int64_t* rows_dev,
                       int64_t B, void* hip_stream);
+
+/* ---- device replay buffer: stable_baselines3's ReplayBuffer / DictReplayBuffer over step-major [T][N][...] device rings ----
+ * Context free; every call is ONE launch enqueued on hip_stream, nothing is allocated or synchronised.  The tables are host arrays of
+ * n_arrays <= TG_ROLLOUT_MAX_ARRAYS entries, read before the call returns; the pointers in them are device memory.
+ *
+ * tg_replay_add: array i has n_rows rows of row_bytes[i] bytes, back to back in src_dev[i], alt_dev[i] and dst_dev[i].  Destination row n is row n
+ * of alt_dev[i] when alt_dev[i] != NULL && select_dev[n] (uint8 [n_rows], non-zero = take alt), else row n of src_dev[i]; only the chosen source
+ * of a row is read.  TG_ROLLOUT_COPY copies the bytes; TG_ROLLOUT_FLAG_U8 (row_bytes[i] = 1) reads one uint8 per row and writes one float32
+ * 0.0 / 1.0 (dst 4-byte aligned).  select_dev may be NULL when every alt_dev[i] is.  16-byte accesses where the row byte count and the three
+ * addresses allow, 4-byte or single bytes otherwise.  No destination may overlap a source of its array.  One transition batch of a replay
+ * buffer: next_observations[pos] (alt = the terminal observations, select = the done flags), actions, rewards, dones, timeouts, and - an
+ * array like the others with a NULL alt - observations[pos + 1].
+ *
+ * tg_replay_draw: the counter-based draw of a minibatch, on tg_sample_actions' generator.  For b < B:
+ *     h = mix64(mix64(seed + G (counter + 1)) + G (b + 1));     G = 0x9E3779B97F4A7C15
+ *     t = (first_slot + (((h >> 32) * n_slots) >> 32)) % T;       n = ((h & 0xffffffff) * N) >> 32;      row = t N + n
+ *     rows_dev[b] = row;   rows_dev[B + b] = row + next_offset                        (int64 [2 B]; all of it 64-bit integer arithmetic)
+ *     actions_out[b][0 .. A) = actions_dev[row][0 .. A);   rewards_out[b] = rewards_dev[row];
+ *     dones_out[b] = dones_dev[row] * (1 - timeouts_dev[row])                        (float32, one rounding per operation)
+ * 1 <= n_slots <= T, n_slots and N below 2^31, T N <= 2^40, 0 <= first_slot < T.  actions_dev, rewards_dev, dones_dev and timeouts_dev may be
+ * NULL together: then only the rows are written (and the three outputs are not touched). */
+int tg_replay_add(int32_t n_arrays, const void* const* src_dev, const void* const* alt_dev, void* const* dst_dev, const int64_t* row_bytes,
+                  const int32_t* kinds, int64_t n_rows, const void* select_dev, void* hip_stream);
+int tg_replay_draw(int64_t B, int64_t n_slots, int64_t first_slot, int64_t T, int64_t N, uint64_t seed, uint64_t counter,
+                   const float* actions_dev, int32_t A, const float* rewards_dev, const float* dones_dev, const float* timeouts_dev,
+                   int64_t next_offset, int64_t* rows_dev, float* actions_out, float* rewards_out, float* dones_out, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ loudly when the HIP library or a GPU is missing.
     aug = torch.nn.Sequential(K.RandomAffine(degrees=0, translate=[0.05, 0.05], scale=[1.0, 1.0], p=0.5))
     buf = tg.DeviceRolloutBuffer.for_env(venv, n_steps, gamma=0.95, gae_lambda=0.9)   # SB3's rollout buffer in device memory (tg.rollout; imports torch)
     for batch in buf.get(64, augment=aug): ...
+    rb = tg.DeviceReplayBuffer.for_env(venv, 100_000)   # SB3's replay buffer (SAC / RAD_SAC) in device memory (tg.replay; imports torch)
+    rb.start(venv.reset()); venv.step(actions); rb.add_from_env(actions); batch = rb.sample(64, augment=aug)
 """
 from . import rl_envs  # noqa: F401  (registers the env ids)
 from .registry import make, make_vec, register, registered_ids  # noqa: F401
@@ -21,10 +23,13 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("augment", "rollout"):   # imported on first use: they need torch, the rest of the package does not
+    if name in ("augment", "rollout", "replay"):   # imported on first use: they need torch, the rest of the package does not
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "DeviceRolloutBuffer":
         import importlib
         return importlib.import_module(".rollout", __name__).DeviceRolloutBuffer
+    if name == "DeviceReplayBuffer":
+        import importlib
+        return importlib.import_module(".replay", __name__).DeviceReplayBuffer
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -234,6 +234,10 @@ SYMBOLS = {
                                  C.c_int64, C.c_double, C.c_double, C.c_void_p]),
     "tg_rollout_gather": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.c_int64,
                                     C.c_void_p]),
+    "tg_replay_add": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64),
+                                C.POINTER(C.c_int32), C.c_int64, C.c_void_p, C.c_void_p]),
+    "tg_replay_draw": (C.c_int, [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tg_get_state": (C.c_int, [_ctx, C.POINTER(TgStateView)]),
     "tg_set_joint_state": (C.c_int, [_ctx, _dp, _dp]),
     "tg_profile_enable": (C.c_int, [_ctx, C.c_int32]),
