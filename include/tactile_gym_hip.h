@@ -622,6 +622,29 @@ int tg_random_translate_rows(const void* in_dev, void* out_dev, int32_t in_dtype
                              int32_t W, double ax, double ay, float p, uint64_t seed, uint64_t counter, const float* params_in_dev,
                              float* params_out_dev, const int64_t* rows_dev, void* hip_stream);
 
+/* ---- general affine augmentation: kornia's RandomAffine(degrees, translate, scale, shear, p) with its defaults ----------------
+ * Context free; images, layouts, dtypes (TG_AUGMENT_*), overlap rule and stream as tg_random_translate: one launch, nothing allocated or
+ * synchronised.  Sample b is warped with probability p by a rotation of angle ~ U(d0, d1) degrees and a scale of scale_x ~ U(s0, s1), scale_y
+ * ~ U(s2, s3) (s2 = s3 = 0: scale_y = scale_x) about the image centre, a shear of shear_x ~ U(h0, h1), shear_y ~ U(h2, h3) degrees about it,
+ * and a shift of tx ~ U(-ax W, ax W), ty ~ U(-ay H, ay H) pixels, resampled as kornia's warp_affine does (bilinear, zero padding,
+ * align_corners=False), all channels alike; otherwise out = in.  The draws are element 8 b + k of tg_sample_actions' generator at
+ * (seed, counter).  params_in_dev (nullable): float32 [B][8] (apply, tx, ty, angle, scale_x, scale_y, shear_x, shear_y) used instead of the
+ * draws; params_out_dev (nullable): receives them (apply as 0 / 1).  coeffs_in_dev (nullable): float32 [B][6] (a00, a01, a02, a10, a11, a12),
+ * output pixel (column j, row i) samples the input at (a00 j + a01 i + a02, a10 j + a11 i + a12), used as they are instead of the ones the
+ * parameters give - only `apply` is then taken from the parameters; coeffs_out_dev (nullable): receives the coefficients used.
+ * H, W >= 2, 0 <= ax, ay, p <= 1, every range finite and ordered, scales > 0; B = 0 does nothing.  The arithmetic, stage by stage: DESIGN.md 4.11. */
+int tg_random_affine(const void* in_dev, void* out_dev, int32_t in_dtype, int32_t channels_first, int64_t B, int32_t C, int32_t H, int32_t W,
+                     double ax, double ay, float d0, float d1, float s0, float s1, float s2, float s3, float h0, float h1, float h2, float h3,
+                     float p, uint64_t seed, uint64_t counter, const float* params_in_dev, float* params_out_dev, const float* coeffs_in_dev,
+                     float* coeffs_out_dev, void* hip_stream);
+/* tg_random_affine with a row-indexed source, as tg_random_translate_rows: sample b reads source sample rows_dev[b] (nullable: b itself);
+ * draws, parameters, coefficients and the output stay indexed by b.  The caller guarantees that every entry names a sample inside in_dev's
+ * allocation and that out_dev does not overlap it. */
+int tg_random_affine_rows(const void* in_dev, void* out_dev, int32_t in_dtype, int32_t channels_first, int64_t B, int32_t C, int32_t H, int32_t W,
+                          double ax, double ay, float d0, float d1, float s0, float s1, float s2, float s3, float h0, float h1, float h2,
+                          float h3, float p, uint64_t seed, uint64_t counter, const float* params_in_dev, float* params_out_dev,
+                          const float* coeffs_in_dev, float* coeffs_out_dev, const int64_t* rows_dev, void* hip_stream);
+
 /* ---- device rollout buffer: stable_baselines3's RolloutBuffer / DictRolloutBuffer over step-major [T][N][...] device arrays ----
  * Context free; every call is ONE launch enqueued on hip_stream, nothing is allocated or synchronised.  The pointer / size tables are host arrays
  * of n_arrays <= TG_ROLLOUT_MAX_ARRAYS entries, read before the call returns; the pointers in them are device memory.

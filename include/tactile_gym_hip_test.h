@@ -74,6 +74,12 @@ int tg_selftest_render(const tg_sensor* sensor, const tg_mesh* mesh, int32_t row
  * 2^23 workgroups per launch).  -1 for a shape the call itself refuses.  Host only: needs no device. */
 int tg_selftest_translate_plan(int32_t in_dtype, int32_t channels_first, int32_t C, int32_t H, int32_t W, int64_t B, uint64_t in_addr,
                                uint64_t out_addr, int32_t* path, int32_t* chunks, int32_t* lds_bytes, int64_t* launches);
+/* How tg_random_affine / tg_random_affine_rows would launch a call (csrc/tg_affine.h: affine_plan, the function the launcher itself calls):
+ * *path = 0 per element / 1 taps gathered from global memory, float4 stores / 2 source rows staged through LDS; *in_vec = 1 when samples that
+ * are not applied are copied with 16-byte loads; *chunks = 4096-element chunks per plane, *lds_bytes = dynamic LDS of a workgroup, *launches =
+ * kernel launches.  -1 for a shape the call itself refuses.  Host only: needs no device. */
+int tg_selftest_affine_plan(int32_t in_dtype, int32_t channels_first, int32_t C, int32_t H, int32_t W, int64_t B, uint64_t in_addr,
+                            uint64_t out_addr, int32_t* path, int32_t* in_vec, int32_t* chunks, int32_t* lds_bytes, int64_t* launches);
 /* The scene camera (csrc/tg_scene.hip: k_scene; the product reaches it through tg_set_scene / tg_render_scene) on any triangle set.
  * tg_selftest_scene_plan - host only, needs no device - runs the product's build_scene_chunks and scene_layout on verts [n_verts][3], tris
  * [n_tris][3], tri_frame [n_tris] (< 16), tri_rgb [n_tris][3] for a W x H image and reports *plan; the arrays (each may be NULL) receive

@@ -29,7 +29,7 @@ CONTACT_MAP = {"auto": 0, "lane": 1, "wave": 2}
 RESET_BANK = {"auto": 0, "off": 1, "sync": 2, "on": 3}
 FUSED_STEP = {"auto": 0, "off": 1, "on": 2}
 OBS_KEY = {"tactile": 0, "oracle": 1, "extended_feature": 2}   # TG_OBS_KEY_* (tg_get_obs_stack)
-AUGMENT_DTYPE = {"uint8": 0, "float32": 1}   # TG_AUGMENT_* (tg_random_translate)
+AUGMENT_DTYPE = {"uint8": 0, "float32": 1}   # TG_AUGMENT_* (tg_random_translate, tg_random_affine)
 ROLLOUT_MAX_ARRAYS = 16                      # TG_ROLLOUT_MAX_ARRAYS
 ROLLOUT_COPY, ROLLOUT_FLAG_U8 = 0, 1         # TG_ROLLOUT_* array kinds (tg_rollout_add)
 ROLLOUT_DONES = {"uint8": 0, "float32": 1}   # TG_ROLLOUT_DONES_* (tg_rollout_gae)
@@ -229,6 +229,11 @@ SYMBOLS = {
                                       C.c_double, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tg_random_translate_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                            C.c_double, C.c_float, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tg_random_affine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double]
+                         + [C.c_float] * 11 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tg_random_affine_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double,
+                                        C.c_double] + [C.c_float] * 11 + [C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                          C.c_void_p, C.c_void_p]),
     "tg_rollout_add": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_void_p]),
     "tg_rollout_gae": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                  C.c_int64, C.c_double, C.c_double, C.c_void_p]),
@@ -309,6 +314,9 @@ TEST_SYMBOLS = {
                                             C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "tg_selftest_translate_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64,
                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "tg_selftest_affine_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64,
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int64)]),
     "tg_selftest_render": (C.c_int, [C.POINTER(TgSensor), C.POINTER(TgMesh), C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double),
                                      C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),

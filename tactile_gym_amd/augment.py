@@ -14,6 +14,10 @@ every channel alike - and otherwise passed through unchanged (its values convert
 the same distribution as kornia's, not the same numbers.  Inputs: contiguous 4-D uint8 or float32 tensors on the device, [B, C, H, W]
 (channels_first) or [B, H, W, C]; the output is a new float32 tensor of the same shape.  The input is never written, so obs_mode="torch"
 observations can be augmented directly.  There is no CPU path: anything else raises.
+
+The general affine warp - rotation, scale and shear as well as the shift - is `random_affine` / `RandomWarp` / `RandomRotation`
+(csrc/tg_affine.hip: k_random_affine): kornia's RandomAffine argument list, the same tensors, layouts and draw scheme (eight
+uniforms per sample).  The `RandomAffine` factory below still builds only the translate module and refuses the rest.
 """
 import ctypes as C
 
@@ -21,7 +25,7 @@ import torch
 
 from . import _capi as capi
 
-__all__ = ["random_translate", "RandomTranslate", "RandomAffine", "augment_images"]
+__all__ = ["random_translate", "RandomTranslate", "RandomAffine", "augment_images", "random_affine", "RandomWarp", "RandomRotation"]
 
 _DTYPES = {torch.uint8: capi.AUGMENT_DTYPE["uint8"], torch.float32: capi.AUGMENT_DTYPE["float32"]}
 
@@ -119,6 +123,186 @@ class RandomTranslate(torch.nn.Module):
 
     def extra_repr(self):
         return f"translate={self.translate}, p={self.p}, seed={self.seed}, channels_first={self.channels_first}"
+
+
+def _degrees_range(degrees):
+    """kornia's normalisation: a number d means (-d, d) and must be >= 0; a pair is (d0, d1)."""
+    if isinstance(degrees, (int, float)):
+        if degrees < 0:
+            raise ValueError(f"degrees as a single number must be >= 0, got {degrees}")
+        return -float(degrees), float(degrees)
+    d = tuple(float(x) for x in degrees)
+    if len(d) != 2 or not d[0] <= d[1]:
+        raise ValueError(f"degrees must be a number or an ordered pair, got {degrees!r}")
+    return d
+
+
+def _scale_range(scale):
+    """None: (1, 1); (a, b): scale_y = scale_x ~ U(a, b); (a, b, c, d): scale_y ~ U(c, d).  Every bound > 0.  Returns (4 bounds, has_y)."""
+    if scale is None:
+        return (1.0, 1.0, 1.0, 1.0), False
+    sc = tuple(float(x) for x in scale)
+    if len(sc) not in (2, 4) or not all(x > 0.0 for x in sc) or not sc[0] <= sc[1] or (len(sc) == 4 and not sc[2] <= sc[3]):
+        raise ValueError(f"scale must be None, (a, b) or (a, b, c, d) with ordered bounds > 0, got {scale!r}")
+    return (sc if len(sc) == 4 else sc + sc), len(sc) == 4
+
+
+def _shear_range(shear):
+    """kornia's normalisation: None: no shear; a number s: (-s, s, 0, 0); a pair (a, b): (a, b, 0, 0); four numbers as they are (degrees)."""
+    if shear is None:
+        return 0.0, 0.0, 0.0, 0.0
+    if isinstance(shear, (int, float)):
+        if shear < 0:
+            raise ValueError(f"shear as a single number must be >= 0, got {shear}")
+        return -float(shear), float(shear), 0.0, 0.0
+    sh = tuple(float(x) for x in shear)
+    if len(sh) == 2:
+        sh = sh + (0.0, 0.0)
+    if len(sh) != 4 or not (sh[0] <= sh[1] and sh[2] <= sh[3]):
+        raise ValueError(f"shear must be None, a number, a pair or four numbers with ordered bounds, got {shear!r}")
+    return sh
+
+
+def _translate_pair(translate):
+    if translate is None:
+        return 0.0, 0.0
+    t = _pair(translate, "translate")
+    if not all(0.0 <= v <= 1.0 for v in t):
+        raise ValueError(f"translate must lie in [0, 1], got {t}")
+    return t
+
+
+def _f32_tensor(t, name, shape, x):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError(f"{name} must be a float32 torch tensor")
+    if tuple(t.shape) != shape or t.device != x.device or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {list(shape)} tensor on the input's device")
+
+
+def _affine_call(x, out, rows, B, Cn, H, W, channels_first, ranges, p, seed, counter, params, pout, coeffs, cout, stream):
+    """The one place that lays out tg_random_affine_rows' arguments (random_affine and the device buffers' fused gathers)."""
+    (ax, ay), (d0, d1), (sc, has_y), sh = ranges
+    s2, s3 = (sc[2], sc[3]) if has_y else (0.0, 0.0)
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)   # noqa: E731
+    capi.check(capi.lib().tg_random_affine_rows(
+        ptr(x), ptr(out), _DTYPES[x.dtype], int(bool(channels_first)), B, Cn, H, W, ax, ay, d0, d1, sc[0], sc[1], s2, s3, sh[0], sh[1], sh[2], sh[3],
+        p, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(counter) & 0xFFFFFFFFFFFFFFFF), ptr(params), ptr(pout), ptr(coeffs),
+        ptr(cout), ptr(rows), C.c_void_p(stream)))
+
+
+_centers = {}   # (H, W, device) -> float32 [1, 2] on the device: uploaded once, not per call
+
+
+def _kornia_params(prm, H, W):
+    """kornia's RandomAffine._params names from the [B, 8] rows (apply, tx, ty, angle, scale_x, scale_y, shear_x, shear_y)."""
+    key = (H, W, prm.device)
+    if key not in _centers:
+        _centers[key] = torch.tensor([[(W - 1) / 2.0, (H - 1) / 2.0]], dtype=torch.float32, device=prm.device)
+    center = _centers[key].expand(prm.shape[0], 2)
+    return {"batch_prob": prm[:, 0] != 0, "translations": prm[:, 1:3], "center": center, "scale": prm[:, 4:6], "angle": prm[:, 3],
+            "sx": prm[:, 6], "sy": prm[:, 7]}
+
+
+def random_affine(x, degrees=0.0, translate=None, scale=None, shear=None, p=0.5, seed=0, counter=0, params=None, coeffs=None,
+                  channels_first=True, out=None, return_params=False):
+    """One draw of the general affine warp over the batch x ([B, C, H, W], or [B, H, W, C] with channels_first=False): a new float32 tensor
+    (or `out`).  degrees, translate, scale, shear: kornia's RandomAffine arguments (degrees d: (-d, d); shear s: (-s, s, 0, 0); scale (a, b)
+    or (a, b, c, d)).  (seed, counter) pick the draws: element 8 b + k of tg_sample_actions' generator.  params: an optional float32 [B, 8]
+    device tensor (apply, tx, ty, angle, scale_x, scale_y, shear_x, shear_y) used instead of the draws; coeffs: an optional float32 [B, 6]
+    device tensor (a00, a01, a02, a10, a11, a12) of source-coordinate coefficients used as they are (only `apply` then comes from the
+    parameters).  return_params=True returns (out, params, coeffs) with the [B, 8] and [B, 6] values that were used."""
+    _check_images(x)
+    ranges = (_translate_pair(translate), _degrees_range(degrees), _scale_range(scale), _shear_range(shear))
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"p must lie in [0, 1], got {p}")
+    B = x.shape[0]
+    if channels_first:
+        Cn, H, W = x.shape[1], x.shape[2], x.shape[3]
+    else:
+        H, W, Cn = x.shape[1], x.shape[2], x.shape[3]
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    else:
+        _check_images(out, "out")
+        if out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device:
+            raise ValueError("out must be a float32 tensor of the input's shape on its device")
+    if params is not None:
+        _f32_tensor(params, "params", (B, 8), x)
+    if coeffs is not None:
+        _f32_tensor(coeffs, "coeffs", (B, 6), x)
+    pout = torch.empty((B, 8), dtype=torch.float32, device=x.device) if return_params else None
+    cout = torch.empty((B, 6), dtype=torch.float32, device=x.device) if return_params else None
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _affine_call(x, out, None, B, Cn, H, W, channels_first, ranges, p, seed, counter, params, pout, coeffs, cout, stream)
+    return (out, pout, cout) if return_params else out
+
+
+def _refuse_unbuilt(who, same_on_batch, align_corners, padding_mode, resample):
+    if same_on_batch:
+        raise NotImplementedError(f"{who}: same_on_batch=True (only per-sample draws are built)")
+    if align_corners:
+        raise NotImplementedError(f"{who}: align_corners=True (only False is built)")
+    if str(getattr(padding_mode, "name", padding_mode)).lower() != "zeros":
+        raise NotImplementedError(f"{who}: padding_mode={padding_mode!r} (only 'zeros' is built)")
+    if str(getattr(resample, "name", resample)).lower() != "bilinear":
+        raise NotImplementedError(f"{who}: resample={resample!r} (only 'bilinear' is built)")
+
+
+class RandomWarp(torch.nn.Module):
+    """kornia's RandomAffine(degrees, translate, scale, shear, p) on the device: rotation, scale and shear about the image centre, then the
+    shift.  Call k (from 0) draws with (seed, k).  After a call, `_params` holds kornia's names: `batch_prob` (bool [B]),
+    `translations` ([B, 2], pixels), `center` ([B, 2]), `scale` ([B, 2]), `angle` ([B], degrees), `sx`, `sy` ([B], degrees); `_coeffs` the
+    [B, 6] source-coordinate coefficients.  same_on_batch, align_corners, padding_mode and resample other than kornia's defaults are refused."""
+
+    def __init__(self, degrees, translate=None, scale=None, shear=None, p=0.5, same_on_batch=False, align_corners=False, padding_mode="zeros",
+                 resample="bilinear", seed=None, channels_first=True):
+        super().__init__()
+        _refuse_unbuilt("RandomWarp", same_on_batch, align_corners, padding_mode, resample)
+        self.degrees = _degrees_range(degrees)
+        self.translate = _translate_pair(translate)
+        self.scale, self.scale_has_y = _scale_range(scale)
+        self.shear = _shear_range(shear)
+        self.p = float(p)
+        if not 0.0 <= self.p <= 1.0:
+            raise ValueError(f"p must lie in [0, 1], got {self.p}")
+        self.seed = _draw_seed() if seed is None else int(seed)
+        self.channels_first = bool(channels_first)
+        self.counter = 0
+        self._params = None
+        self._coeffs = None
+
+    def _ranges(self):
+        return self.translate, self.degrees, (self.scale, self.scale_has_y), self.shear
+
+    def _fused(self, src, out, rows, B, Cn, H, W, channels_first, stream):
+        """One call over a row-indexed source (the device buffers' gathers): draws (seed, counter), advances the counter, sets `_params`."""
+        prm = torch.empty((B, 8), dtype=torch.float32, device=out.device)
+        co = torch.empty((B, 6), dtype=torch.float32, device=out.device)
+        _affine_call(src, out, rows, B, Cn, H, W, channels_first, self._ranges(), self.p, self.seed, self.counter, None, prm, None, co, stream)
+        self.counter += 1
+        self._params, self._coeffs = _kornia_params(prm, H, W), co
+
+    def forward(self, x):
+        _check_images(x)
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        B = x.shape[0]
+        Cn, H, W = (x.shape[1], x.shape[2], x.shape[3]) if self.channels_first else (x.shape[3], x.shape[1], x.shape[2])
+        with torch.cuda.device(x.device):
+            self._fused(x, out, None, B, Cn, H, W, self.channels_first, torch.cuda.current_stream(x.device).cuda_stream)
+        return out
+
+    def extra_repr(self):
+        scale = self.scale if self.scale_has_y else self.scale[:2]
+        return (f"degrees={self.degrees}, translate={self.translate}, scale={scale}, shear={self.shear}, p={self.p}, seed={self.seed}, "
+                f"channels_first={self.channels_first}")
+
+
+def RandomRotation(degrees, p=0.5, same_on_batch=False, align_corners=False, resample="bilinear", seed=None, channels_first=True):
+    """kornia.augmentation.RandomRotation: a RandomWarp that only rotates (angle ~ U(-d, d) for a number d, or U(d0, d1))."""
+    _refuse_unbuilt("RandomRotation", same_on_batch, align_corners, "zeros", resample)
+    return RandomWarp(degrees, p=p, seed=seed, channels_first=channels_first)
 
 
 def _is_zero_pair(v):

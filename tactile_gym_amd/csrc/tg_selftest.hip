@@ -8,6 +8,7 @@
 
 #include "../../include/tactile_gym_hip_test.h"
 #include "tg_augment.h"      // translate_plan: the launch decision of tg_random_translate (host only)
+#include "tg_affine.h"       // affine_plan: the launch decision of tg_random_affine (host only)
 #include "tg_ctx.hpp"        // fail: the message behind tg_selftest_last_error
 #include "tg_raster_dev.hpp"
 
@@ -176,6 +177,23 @@ extern "C" int tg_selftest_translate_plan(int32_t in_dtype, int32_t channels_fir
     *path = p.vec;
     *chunks = p.nchunk;
     *lds_bytes = p.lds_floats * 4;
+    *launches = (B + p.spl - 1) / p.spl;
+    return 0;
+}
+
+// The launch decision of tg_random_affine, by the launcher's own function (tg_affine.h: affine_plan); argument checks as above.  Host only.
+extern "C" int tg_selftest_affine_plan(int32_t in_dtype, int32_t channels_first, int32_t C, int32_t H, int32_t W, int64_t B, uint64_t in_addr,
+                                       uint64_t out_addr, int32_t* path, int32_t* in_vec, int32_t* chunks, int32_t* lds_bytes, int64_t* launches) {
+    using tg::fail;
+    if (!path || !in_vec || !chunks || !lds_bytes || !launches) return fail(-1, "NULL argument");
+    if (in_dtype != TG_AUGMENT_UINT8 && in_dtype != TG_AUGMENT_FLOAT32) return fail(-1, "unknown input dtype");
+    if (B < 0 || C < 1 || H < 2 || W < 2 || (int64_t)C * H * W > (1 << 30)) return fail(-1, "need B >= 0, C >= 1, H >= 2, W >= 2, C H W <= 2^30");
+    const tg::AffinePlan p = tg::affine_plan(in_dtype == TG_AUGMENT_UINT8 ? 1 : 4, channels_first != 0, C, H, W, (uintptr_t)in_addr, (uintptr_t)out_addr);
+    if (p.spl < 1) return fail(-1, "one sample has more workgroups than a launch holds");
+    *path = p.path;
+    *in_vec = p.in_vec;
+    *chunks = p.nchunk;
+    *lds_bytes = p.lds_bytes;
     *launches = (B + p.spl - 1) / p.spl;
     return 0;
 }

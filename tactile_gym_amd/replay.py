@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from . import _capi as capi
+from .augment import RandomWarp
 from .rollout import DeviceRolloutBuffer, _space_shapes, _unwrap_augment
 
 __all__ = ["DeviceReplayBuffer", "ReplayBufferSamples"]
@@ -289,8 +290,8 @@ class DeviceReplayBuffer:
 
     def sample(self, batch_size, env=None, augment=None, out_dtype=torch.float32):
         """ReplayBufferSamples(observations, actions, next_observations, dones, rewards) of new device tensors: dones and rewards [B, 1], dones
-        = dones * (1 - timeouts).  Image keys come out float32 (0 ... 255), through `augment` - a RandomTranslate or the nn.Sequential holding
-        one - when given: observations and next_observations of a key are the two halves of ONE call of the module over 2 B samples (its counter
+        = dones * (1 - timeouts).  Image keys come out float32 (0 ... 255), through `augment` - a RandomTranslate, a RandomWarp or the nn.Sequential
+        holding one - when given: observations and next_observations of a key are the two halves of ONE call of the module over 2 B samples (its counter
         advances by one, `_params` covers 2 B samples; the two halves draw independently).  out_dtype=torch.uint8 without augment keeps them
         uint8.  `env` is SB3's VecNormalize argument: not built."""
         if env is not None:
@@ -323,6 +324,10 @@ class DeviceReplayBuffer:
                     out = torch.empty((2 * B,) + shape, dtype=torch.float32, device=dev)
                     cf = self._channels_first[k]
                     c, h, w = shape if cf else (shape[2], shape[0], shape[1])
+                    if isinstance(module, RandomWarp):                                         # the general warp: tg_random_affine_rows
+                        module._fused(src, out, rows, 2 * B, c, h, w, cf, stream.value)
+                        obs[k], nxt[k] = out[:B], out[B:]
+                        continue
                     if module is not None:
                         (ax, ay), p, seed, counter = module.translate, module.p, module.seed, module.counter
                         prm = torch.empty((2 * B, 3), dtype=torch.float32, device=dev)

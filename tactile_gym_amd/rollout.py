@@ -1,6 +1,6 @@
 """A rollout buffer in device memory: stable_baselines3's RolloutBuffer / DictRolloutBuffer (the on-policy buffer of the reference's PPO /
 RAD_PPO) over torch tensors on the ROCm device, filled from obs_mode="torch" observations and read as augmented minibatches without a trip
-through the host (csrc/tg_rollout.hip: k_rollout_add, k_rollout_gae, k_rollout_gather; csrc/tg_augment.hip: the row-indexed k_random_translate).
+through the host (csrc/tg_rollout.hip: k_rollout_add, k_rollout_gae, k_rollout_gather; csrc/tg_augment.hip: the row-indexed k_random_translate; csrc/tg_affine.hip: the row-indexed k_random_affine for a RandomWarp).
 
     buf = tg.DeviceRolloutBuffer.for_env(venv, n_steps, gamma=0.95, gae_lambda=0.9)
     obs, starts = venv.reset(), torch.ones(venv.num_envs, device=buf.device)
@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .augment import RandomTranslate
+from .augment import RandomTranslate, RandomWarp
 
 __all__ = ["DeviceRolloutBuffer", "RolloutBufferSamples", "flat_rows"]
 
@@ -65,15 +65,15 @@ def _space_shapes(space, name):
 
 
 def _unwrap_augment(augment):
-    """The RandomTranslate of `augment`: the module itself or the one member of the params files' nn.Sequential."""
+    """The RandomTranslate or RandomWarp of `augment`: the module itself or the one member of the params files' nn.Sequential."""
     m = augment
     if isinstance(m, torch.nn.Sequential):
         if len(m) != 1:
-            raise TypeError(f"augment must hold exactly one RandomTranslate, got an nn.Sequential of {len(m)} modules")
+            raise TypeError(f"augment must hold exactly one RandomTranslate or RandomWarp, got an nn.Sequential of {len(m)} modules")
         m = m[0]
-    if not isinstance(m, RandomTranslate):
-        raise TypeError(f"augment must be a tactile_gym_amd.augment.RandomTranslate (or the nn.Sequential of one), got {type(m).__name__}: the "
-                        "fused gather needs the module's translate, p, seed and counter, not a callable")
+    if not isinstance(m, (RandomTranslate, RandomWarp)):
+        raise TypeError(f"augment must be a tactile_gym_amd.augment.RandomTranslate or RandomWarp (or the nn.Sequential of one), got "
+                        f"{type(m).__name__}: the fused gather needs the module's ranges, p, seed and counter, not a callable")
     return m
 
 
@@ -244,7 +244,7 @@ class DeviceRolloutBuffer:
         """A generator over the minibatches of the full buffer (RolloutBufferSamples of new device tensors).  Without `indices` the order is one
         torch.randperm(T N) on the device (`generator`: a device torch.Generator); with `indices` (int64, SB3's flat sample indices i = n T + t,
         checked once for range) that order is used.  Slices of batch_size are yielded, the last one shorter; None is the whole buffer.  Image keys
-        come out float32 (0 ... 255), through `augment` - a RandomTranslate or the nn.Sequential holding one - when given, each image key of each
+        come out float32 (0 ... 255), through `augment` - a RandomTranslate, a RandomWarp or the nn.Sequential holding one - when given, each image key of each
         minibatch being one call of the module (its counter advances, `_params` is set); out_dtype=torch.uint8 without augment keeps them uint8."""
         if not self.full:
             raise RuntimeError(f"get() needs a full rollout buffer: {self.pos} of {self.buffer_size} steps added")
@@ -289,6 +289,10 @@ class DeviceRolloutBuffer:
                     out = torch.empty((B,) + shape, dtype=torch.float32, device=dev)
                     cf = self._channels_first[k]
                     c, h, w = shape if cf else (shape[2], shape[0], shape[1])
+                    if isinstance(module, RandomWarp):                                         # the general warp: tg_random_affine_rows
+                        module._fused(src, out, rows, B, c, h, w, cf, stream.value)
+                        obs[k] = out
+                        continue
                     if module is not None:
                         (ax, ay), p, seed, counter = module.translate, module.p, module.seed, module.counter
                         prm = torch.empty((B, 3), dtype=torch.float32, device=dev)
