@@ -699,6 +699,33 @@ int tg_replay_add(int32_t n_arrays, const void* const* src_dev, const void* cons
 int tg_replay_draw(int64_t B, int64_t n_slots, int64_t first_slot, int64_t T, int64_t N, uint64_t seed, uint64_t counter,
                    const float* actions_dev, int32_t A, const float* rewards_dev, const float* dones_dev, const float* timeouts_dev,
                    int64_t next_offset, int64_t* rows_dev, float* actions_out, float* rewards_out, float* dones_out, void* hip_stream);
+
+/* ---- device VecNormalize: stable_baselines3's VecNormalize / RunningMeanStd over float32 device arrays, statistics in float64 ----
+ * Context free; enqueued on hip_stream, nothing is allocated or synchronised.  The tables are host arrays of n_arrays <= TG_VECNORM_MAX_ARRAYS
+ * entries, read before the call returns; the pointers in them are device memory.  Array i is float32 [rows][widths[i]], widths[i] >= 1 and the
+ * widths add up to at most TG_VECNORM_MAX_WIDTH; stats_dev[i] is its block of 2 widths[i] + 1 doubles: mean [d] | var [d] | count.  ret_stats_dev
+ * is the block of the discounted return: mean, var, count.  Every operation is float64 with one rounding; the order of the sums is DESIGN.md
+ * 4.12's (tests/vecnorm_ref.py restates it bit for bit).
+ *
+ * tg_vecnorm_update (TWO launches): RunningMeanStd.update of every array with its N rows, 1 <= N <= TG_VECNORM_MAX_ROWS.  With returns_dev
+ * (float64 [N]), rewards_dev (float32 [N]) and ret_stats_dev - NULL together or not at all - also returns = returns gamma + rewards, written back,
+ * and the update of ret_stats with the new returns as an [N][1] batch.  scratch_dev: 2 ((N + 255) / 256) (sum of widths + 1) doubles of the
+ * caller's, overwritten.
+ *
+ * tg_vecnorm_apply (ONE launch): out_dev[i][r][j] = (float) clip(((double) x_dev[i][r][j] - mean[j]) / sqrt(var[j] + epsilon), -clip_obs, clip_obs)
+ * for r < R (any row count up to TG_VECNORM_MAX_APPLY_ROWS; out_dev[i] may be x_dev[i]).  With rewards_dev: rewards_out[e] = (float)
+ * clip((double) rewards_dev[e] / sqrt(ret var + epsilon), -clip_reward, clip_reward) for e < n_rewards (rewards_out may be rewards_dev).  With
+ * returns_dev: returns_dev[e] = 0 for e < n_reset where dones_dev[e] (uint8), everywhere when dones_dev is NULL. */
+#define TG_VECNORM_MAX_ARRAYS 4
+#define TG_VECNORM_MAX_WIDTH 512
+#define TG_VECNORM_MAX_ROWS 65535
+#define TG_VECNORM_MAX_APPLY_ROWS 2147483647
+int tg_vecnorm_update(int32_t n_arrays, const float* const* x_dev, const int32_t* widths, double* const* stats_dev, int64_t N, double* returns_dev,
+                      const float* rewards_dev, double gamma, double* ret_stats_dev, double* scratch_dev, void* hip_stream);
+int tg_vecnorm_apply(int32_t n_arrays, const float* const* x_dev, float* const* out_dev, const int32_t* widths, const double* const* stats_dev,
+                     int64_t R, double clip_obs, double epsilon, const float* rewards_dev, float* rewards_out, int64_t n_rewards,
+                     const double* ret_stats_dev, double clip_reward, double* returns_dev, const uint8_t* dones_dev, int64_t n_reset,
+                     void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@ loudly when the HIP library or a GPU is missing.
     for batch in buf.get(64, augment=aug): ...
     rb = tg.DeviceReplayBuffer.for_env(venv, 100_000)   # SB3's replay buffer (SAC / RAD_SAC) in device memory (tg.replay; imports torch)
     rb.start(venv.reset()); venv.step(actions); rb.add_from_env(actions); batch = rb.sample(64, augment=aug)
+    vn = tg.DeviceVecNormalize(venv, gamma=0.95)        # SB3's VecNormalize on the device (tg.vecnorm; imports torch); rb.sample(64, env=vn)
 """
 from . import rl_envs  # noqa: F401  (registers the env ids)
 from .registry import make, make_vec, register, registered_ids  # noqa: F401
@@ -23,7 +24,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("augment", "rollout", "replay"):   # imported on first use: they need torch, the rest of the package does not
+    if name in ("augment", "rollout", "replay", "vecnorm"):   # imported on first use: they need torch, the rest of the package does not
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "DeviceRolloutBuffer":
@@ -32,4 +33,7 @@ def __getattr__(name):
     if name == "DeviceReplayBuffer":
         import importlib
         return importlib.import_module(".replay", __name__).DeviceReplayBuffer
+    if name == "DeviceVecNormalize":
+        import importlib
+        return importlib.import_module(".vecnorm", __name__).DeviceVecNormalize
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

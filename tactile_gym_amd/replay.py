@@ -31,6 +31,7 @@ import torch
 from . import _capi as capi
 from .augment import RandomWarp
 from .rollout import DeviceRolloutBuffer, _space_shapes, _unwrap_augment
+from .vecnorm import DeviceVecNormalize
 
 __all__ = ["DeviceReplayBuffer", "ReplayBufferSamples"]
 
@@ -104,6 +105,8 @@ class DeviceReplayBuffer:
         device buffers."""
         if getattr(venv, "obs_mode", None) != "torch":
             raise ValueError("for_env needs an env made with obs_mode='torch' (its observations are read in device memory)")
+        if isinstance(venv, DeviceVecNormalize):               # the originals are stored, as SB3's replay buffer does: sample(env=) normalises
+            venv = venv.venv
         buf = cls(buffer_size, venv.observation_space, venv.action_space, device=torch.device("cuda", venv._cfg.device), n_envs=venv.num_envs,
                   channels_first=bool(venv.channels_first), seed=seed)
         buf._venv = venv
@@ -293,9 +296,10 @@ class DeviceReplayBuffer:
         = dones * (1 - timeouts).  Image keys come out float32 (0 ... 255), through `augment` - a RandomTranslate, a RandomWarp or the nn.Sequential
         holding one - when given: observations and next_observations of a key are the two halves of ONE call of the module over 2 B samples (its counter
         advances by one, `_params` covers 2 B samples; the two halves draw independently).  out_dtype=torch.uint8 without augment keeps them
-        uint8.  `env` is SB3's VecNormalize argument: not built."""
-        if env is not None:
-            raise NotImplementedError("sample(env=...): VecNormalize is not built")
+        uint8.  `env` is SB3's VecNormalize argument: a DeviceVecNormalize, whose current statistics normalise the vector keys of observations
+        and next_observations and the rewards in one more launch (image keys and `augment` are not touched by it)."""
+        if env is not None and not isinstance(env, DeviceVecNormalize):
+            raise NotImplementedError(f"sample(env=...): only a tactile_gym_amd DeviceVecNormalize is built, got {type(env).__name__}")
         if isinstance(batch_size, bool) or int(batch_size) != batch_size or int(batch_size) < 1:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
         module = _unwrap_augment(augment) if augment is not None else None
@@ -308,6 +312,7 @@ class DeviceReplayBuffer:
         dev = self._device_index()
         L = capi.lib()
         obs, nxt, plain = {}, {}, []              # plain: (pair [2, T, N, ...], destination [2 B, ...]) of the one k_rollout_gather launch
+        whole = {}                                # their destinations by key: what sample(env=) normalises
         with self._on_device(dev):
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             rows = torch.empty((2 * B,), dtype=torch.int64, device=dev)
@@ -343,6 +348,7 @@ class DeviceReplayBuffer:
                 else:
                     out = torch.empty((2 * B,) + shape, dtype=dt, device=dev)
                     plain.append((src, out))
+                    whole[k] = out
                 obs[k], nxt[k] = out[:B], out[B:]
             if plain:
                 n = len(plain)
@@ -350,6 +356,8 @@ class DeviceReplayBuffer:
                 for i, (s, d) in enumerate(plain):
                     src_tab[i], dst_tab[i], bytes_tab[i] = s.data_ptr(), d.data_ptr(), s[0, 0, 0].numel() * s.element_size()
                 capi.check(L.tg_rollout_gather(n, src_tab, dst_tab, bytes_tab, C.c_void_p(rows.data_ptr()), 2 * B, stream))
+            if env is not None:                                # after the gather: both halves of every vector key and the rewards, in place
+                env._normalize_sample(whole, rewards)
         if not self._dict_obs:
             obs, nxt = obs[None], nxt[None]
         return ReplayBufferSamples(obs, actions, nxt, dones, rewards)

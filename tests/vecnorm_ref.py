@@ -1,0 +1,131 @@
+"""numpy restatements of the device VecNormalize (tactile_gym_amd.vecnorm; csrc/tg_vecnorm.hip).
+
+`plain`: stable_baselines3's VecNormalize / RunningMeanStd as formulas, the batch moments by np.mean / np.var.
+`device_order`: the same formulas with the batch moments in the kernels' order of operations, bit for bit: chunks of 256 rows, each reduced to
+(mean_c, M2_c) by two passes of a fixed binary tree over the 256 slots (absent rows add an exact zero), the chunks merged in ascending order.
+
+Both are a VecNormRef; only the batch-moment function differs.  Everything is float64 with one rounding per operation (numpy's elementwise
+operations do not fuse), the outputs are rounded to float32 once."""
+import numpy as np
+
+CHUNK = 256
+COUNT0 = 1e-4
+
+
+def plain_moments(x):
+    """(mean, population variance about that mean) over axis 0 of x [n, d].  The sums are taken in extended precision (np.longdouble), so what is
+    left of np.mean / np.var's own summation error is the final rounding to float64; DESIGN.md 4.12's bound counts it as one rounding each."""
+    x = np.asarray(x, dtype=np.float64)
+    return (np.mean(x, axis=0, dtype=np.longdouble).astype(np.float64), np.var(x, axis=0, dtype=np.longdouble).astype(np.float64))
+
+
+def tree_sum(v):
+    """The kernels' sum over axis 1 of v [C, 256, d]: within each block of 64 slots, slot l adds slot l + s for s = 32, 16 ... 1, then
+    (w0 + w1) + (w2 + w3)."""
+    w = v.reshape(v.shape[0], 4, 64, -1)
+    for s in (32, 16, 8, 4, 2, 1):
+        w = w[:, :, :s] + w[:, :, s:2 * s]
+    w = w[:, :, 0]
+    return (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
+
+
+def device_moments(x):
+    """(mean, variance) over axis 0 of x [n, d] in the order of k_vecnorm_partial and k_vecnorm_merge."""
+    x = np.asarray(x, dtype=np.float64)
+    n, d = x.shape
+    C = (n + CHUNK - 1) // CHUNK
+    pad = np.zeros((C * CHUNK, d))
+    pad[:n] = x
+    pad = pad.reshape(C, CHUNK, d)
+    rows = np.minimum(CHUNK, n - CHUNK * np.arange(C)).astype(np.float64)
+    present = (np.arange(C * CHUNK) < n).reshape(C, CHUNK, 1)
+    mean_c = tree_sum(pad) / rows[:, None]
+    dev = np.where(present, pad - mean_c[:, None, :], 0.0)
+    m2_c = tree_sum(dev * dev)
+    cnt, mean, m2 = rows[0], mean_c[0], m2_c[0]
+    for c in range(1, C):
+        nc = rows[c]
+        delta = mean_c[c] - mean
+        tot = cnt + nc
+        mean = mean + delta * nc / tot
+        m2 = m2 + m2_c[c] + delta * delta * cnt * nc / tot
+        cnt = tot
+    return mean, m2 / cnt
+
+
+class RunningMeanStd:
+    """SB3's RunningMeanStd: mean zeros, var ones, count 1e-4 (all float64)."""
+
+    def __init__(self, shape=(), moments=plain_moments, count=COUNT0):
+        self.mean, self.var, self.count = np.zeros(shape, np.float64), np.ones(shape, np.float64), np.float64(count)
+        self._moments = moments
+
+    def update(self, x):
+        x = np.asarray(x, dtype=np.float64)
+        x = x.reshape(x.shape[0], -1)
+        bm, bv = self._moments(x)
+        self.update_from_moments(bm.reshape(self.mean.shape), bv.reshape(self.mean.shape), np.float64(x.shape[0]))
+
+    def update_from_moments(self, bm, bv, n):
+        delta = bm - self.mean
+        tot = self.count + n
+        new_mean = self.mean + delta * n / tot
+        m2 = self.var * self.count + bv * n + delta * delta * self.count * n / tot
+        self.mean, self.var, self.count = new_mean, m2 / tot, tot
+
+
+class VecNormRef:
+    """VecNormalize over a dict of float32 [N, d] vector keys (DESIGN.md 4.12's specification).  widths: {key: d} of the normalised keys."""
+
+    def __init__(self, widths, num_envs, moments=plain_moments, training=True, norm_obs=True, norm_reward=True, clip_obs=10.0, clip_reward=10.0,
+                 gamma=0.99, epsilon=1e-8, count=COUNT0):
+        self.obs_rms = {k: RunningMeanStd((d,), moments, count) for k, d in widths.items()}
+        self.ret_rms = RunningMeanStd((), moments, count)
+        self.returns = np.zeros(num_envs, np.float64)
+        self.training, self.norm_obs, self.norm_reward = training, norm_obs, norm_reward
+        self.clip_obs, self.clip_reward, self.gamma, self.epsilon = float(clip_obs), float(clip_reward), float(gamma), float(epsilon)
+
+    def normalize_obs(self, obs):
+        out = dict(obs)
+        if self.norm_obs:
+            for k, rms in self.obs_rms.items():
+                y = (np.asarray(obs[k], np.float32).astype(np.float64) - rms.mean) / np.sqrt(rms.var + self.epsilon)
+                out[k] = np.clip(y, -self.clip_obs, self.clip_obs).astype(np.float32)
+        return out
+
+    def normalize_reward(self, reward):
+        if not self.norm_reward:
+            return np.asarray(reward, np.float32)
+        y = np.asarray(reward, np.float32).astype(np.float64) / np.sqrt(self.ret_rms.var + self.epsilon)
+        return np.clip(y, -self.clip_reward, self.clip_reward).astype(np.float32)
+
+    def _update_obs(self, obs):
+        if self.training and self.norm_obs:
+            for k, rms in self.obs_rms.items():
+                rms.update(obs[k])
+
+    def reset(self, obs):
+        self.returns[:] = 0.0
+        self._update_obs(obs)
+        return self.normalize_obs(obs)
+
+    def step(self, obs, reward, done, terminal=None):
+        """What step_wait hands out for the inner env's (obs, reward, done) and terminal observation batch: (obs, reward, terminal or None).
+        `returns` is zeroed where done AFTER the reward is normalised."""
+        self._update_obs(obs)
+        out = self.normalize_obs(obs)
+        if self.training:
+            self.returns = self.returns * self.gamma + np.asarray(reward, np.float32).astype(np.float64)
+            self.ret_rms.update(self.returns[:, None])
+        rew = self.normalize_reward(reward)
+        term = self.normalize_obs(terminal) if terminal is not None else None
+        self.returns[np.asarray(done).astype(bool)] = 0.0
+        return out, rew, term
+
+
+def plain(widths, num_envs, **kw):
+    return VecNormRef(widths, num_envs, moments=plain_moments, **kw)
+
+
+def device_order(widths, num_envs, **kw):
+    return VecNormRef(widths, num_envs, moments=device_moments, **kw)
