@@ -3,7 +3,10 @@
  *
  * TEST INFRASTRUCTURE, not part of the boundary a maintainer binds (that is tactile_gym_hip.h / libtactile_gym_hip.so): built by
  * csrc/build.sh next to the product library from the same device headers, loaded only by tests/ (tactile_gym_amd._capi.test_lib()).
- * Every function returns 0 on success, -1 bad argument, -2 no HIP device / allocation failed, -3 launch failed.
+ * Translation units: tg_narrow_test.hip, tg_selftest.hip, tg_render_test.hip, tg_scene_test.hip and tg_stack_test.hip, the last three linked
+ * with the product's own tg_raster.o, tg_scene.o and tg_stack.o.
+ * Every function returns 0 on success, -1 bad argument, -2 no HIP device / allocation failed, -3 launch failed (tg_selftest_stack: the
+ * launcher's own value).
  */
 #ifndef TACTILE_GYM_HIP_TEST_H
 #define TACTILE_GYM_HIP_TEST_H
@@ -121,6 +124,26 @@ typedef struct tg_scene_test {
     int32_t n_spheres;
 } tg_scene_test;
 int tg_selftest_scene(const tg_scene_test* scene, int32_t n, const float* xf, const uint8_t* mask, uint8_t* out, uint8_t* prev);
+/* The device frame stack (csrc/tg_stack.hip: launch_frame_stack / k_frame_stack, launch_obs_stack / k_obs_stack; the product reaches them
+ * through tg_set_frame_stack / tg_set_obs_layout) on raw DEVICE buffers of the caller's (csrc/tg_stack_test.hip).  The fields are those of
+ * StackArgs / StackVec / VisStack (csrc/tg_stack.h: layouts, modes and rules there); `which` names the launcher, and channels_first and the
+ * vis_ block are read by TG_STACK_TEST_OBS only.  The launch goes on `stream`, unsynchronised.  Returns the launcher's own value: 0, -1 for
+ * arguments it refuses (nothing launched), -2 when the launch failed.  Nothing is checked or allocated here. */
+enum { TG_STACK_TEST_FRAME = 0, TG_STACK_TEST_OBS = 1 };
+typedef struct tg_stack_test_vec {
+    const float* src; const float* term; float* stack; float* term_stack;
+    int32_t dim, pitch;
+} tg_stack_test_vec;
+typedef struct tg_stack_test {
+    int32_t which, num_envs, n, mode, rewrite_all, channels_first;   /* mode: 0 step, 1 reset */
+    int32_t H, W;
+    const uint8_t* frame; const uint8_t* term_frame; const uint8_t* tmpl; uint8_t* stack; uint8_t* term_stack; uint8_t* rec;
+    tg_stack_test_vec vec[2];
+    const uint8_t* vis_frame; const uint8_t* vis_term_frame; uint8_t* vis_stack; uint8_t* vis_term_stack;
+    int32_t vis_H, vis_W;
+    const uint8_t* flag;
+} tg_stack_test;
+int tg_selftest_stack(const tg_stack_test* t, void* stream);
 /* The message of the last failing call of this library on the calling thread. */
 const char* tg_selftest_last_error(void);
 

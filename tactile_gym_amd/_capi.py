@@ -308,6 +308,17 @@ class TgSceneTest(C.Structure):      # tg_scene_test
                 ("spheres", _fp), ("n_spheres", C.c_int32)]
 
 
+class TgStackTestVec(C.Structure):   # tg_stack_test_vec: device pointers as plain addresses
+    _fields_ = [("src", C.c_void_p), ("term", C.c_void_p), ("stack", C.c_void_p), ("term_stack", C.c_void_p), ("dim", C.c_int32), ("pitch", C.c_int32)]
+
+
+class TgStackTest(C.Structure):      # tg_stack_test
+    _fields_ = ([(k, C.c_int32) for k in ("which", "num_envs", "n", "mode", "rewrite_all", "channels_first", "H", "W")]
+                + [(k, C.c_void_p) for k in ("frame", "term_frame", "tmpl", "stack", "term_stack", "rec")] + [("vec", TgStackTestVec * 2)]
+                + [(k, C.c_void_p) for k in ("vis_frame", "vis_term_frame", "vis_stack", "vis_term_stack")]
+                + [("vis_H", C.c_int32), ("vis_W", C.c_int32), ("flag", C.c_void_p)])
+
+
 # libtactile_gym_hip_test.so (include/tactile_gym_hip_test.h): device self-tests, test infrastructure - tests/ are the only callers
 TEST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtactile_gym_hip_test.so")
 TEST_SYMBOLS = {
@@ -330,10 +341,12 @@ TEST_SYMBOLS = {
     "tg_selftest_scene_plan": (C.c_int, [C.c_int32, _fp, C.c_int32, C.POINTER(C.c_int32), _u8p, _u8p, C.c_int32, C.c_int32, C.POINTER(TgScenePlan), _fp,
                                          C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "tg_selftest_scene": (C.c_int, [C.POINTER(TgSceneTest), C.c_int32, _fp, _u8p, _u8p, _u8p]),
+    "tg_selftest_stack": (C.c_int, [C.POINTER(TgStackTest), C.c_void_p]),
     "tg_selftest_last_error": (C.c_char_p, []),
 }
 # raster kernel ids of tg_selftest_render (TG_RK_*)
 RK_AUTO, RK_BLOCKS, RK_SMALL_QREJ, RK_SMALL, RK_HF_BANDS, RK_HF_CELLS, RK_TACTILE_128, RK_TACTILE_64, RK_SCATTER_128, RK_SCATTER_64 = range(10)
+STACK_TEST_FRAME, STACK_TEST_OBS = 0, 1      # tg_stack_test.which (TG_STACK_TEST_*)
 _test_lib = None
 
 

@@ -322,6 +322,8 @@ static void launch_obs_n(bool cf, dim3 grid, const StackArgs& o, const VisStack&
 
 int launch_obs_stack(const StackArgs& a, const VisStack& v, int channels_first, hipStream_t stream) {
     if (a.n < 1 || a.n > kStackMax || a.num_envs <= 0) return -1;
+    // (the visual key is checked before k_frame_stack is launched: a refused call writes nothing)
+    if (v.frame && (v.H <= 0 || v.W <= 0 || v.W % 16 || !v.stack || (!channels_first && a.n < 2))) return -1;
     StackArgs o = a;                                   // what k_obs_stack writes besides the visual image
     if (!channels_first) {
         if (a.n >= 2) {
@@ -336,10 +338,7 @@ int launch_obs_stack(const StackArgs& a, const VisStack& v, int channels_first, 
         if (o.n < 2 || o.H % 16 || o.W % 16 || nb % 16 || !o.tmpl || !o.stack || !o.rec) return -1;
         img = (long)o.num_envs * (nb / 16);
     }
-    if (v.frame) {
-        if (v.H <= 0 || v.W <= 0 || v.W % 16 || !v.stack || (!channels_first && a.n < 2)) return -1;
-        vis = ((long)o.num_envs * (v.H * v.W / 16) + 255) / 256;
-    }
+    if (v.frame) vis = ((long)o.num_envs * (v.H * v.W / 16) + 255) / 256;
     for (const StackVec& x : o.vec)
         if (x.dim < 0 || (x.dim > 0 && (o.n < 2 || !x.src || !x.stack || x.pitch < x.dim))) return -1;
     const long groups = img + vis + ((long)o.num_envs * (o.vec[0].dim + o.vec[1].dim) + 255) / 256;

@@ -1,5 +1,5 @@
 """Guarded device buffers for the tests that call the C entry points on raw pointers (tests/test_gpu_augment_paths.py,
-tests/test_gpu_rollout_abi.py): a payload at a chosen offset inside a larger allocation, with bytes of a known pattern in front of and behind it."""
+tests/test_gpu_rollout_abi.py, tests/test_gpu_vecnorm_abi.py, tests/test_gpu_stack_matrix.py): a payload at a chosen offset inside a larger allocation, with bytes of a known pattern in front of and behind it."""
 import numpy as np
 import torch
 
