@@ -71,6 +71,13 @@ int tg_selftest_render(const tg_sensor* sensor, const tg_mesh* mesh, int32_t row
                        const float* zoff, int32_t n, const float* xf, int32_t kernel, int32_t skip_quad_reject, int32_t fills_view,
                        int32_t backface_cull, const uint8_t* mask, const float* term_xf, const uint8_t* term_mask, uint8_t* term_out,
                        uint8_t* out, int32_t* launched);
+/* tg_selftest_render followed (xf2 not NULL) by a second launch on the same image buffer and the same block tables, as a step after a step:
+ * xf2 [n][12], mask2 [n] or NULL, and prev [n][H][W] (in / out) as the launch's save_prev - an env drawn by the second launch leaves the image
+ * it held in prev, the others keep what prev held.  The terminal layer belongs to the first launch only. */
+int tg_selftest_render_twice(const tg_sensor* sensor, const tg_mesh* mesh, int32_t rows, int32_t cols, double grid_scale, const double* heights,
+                             const float* zoff, int32_t n, const float* xf, int32_t kernel, int32_t skip_quad_reject, int32_t fills_view,
+                             int32_t backface_cull, const uint8_t* mask, const float* term_xf, const uint8_t* term_mask, uint8_t* term_out,
+                             uint8_t* out, int32_t* launched, const float* xf2, const uint8_t* mask2, uint8_t* prev);
 /* How tg_random_translate / tg_random_translate_rows would launch a call (csrc/tg_augment.h: translate_plan, the function the launcher itself
  * calls): in_dtype TG_AUGMENT_*, the layout, C, H, W, B and the addresses of the input and the output.  *path = 0 per element / 1 staged
  * through LDS, *chunks = 4096-element chunks per plane, *lds_bytes = dynamic LDS of a workgroup, *launches = kernel launches (B samples at

@@ -338,6 +338,11 @@ TEST_SYMBOLS = {
                                      C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
                                      C.POINTER(C.c_uint8), C.POINTER(C.c_int32)]),
+    "tg_selftest_render_twice": (C.c_int, [C.POINTER(TgSensor), C.POINTER(TgMesh), C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double),
+                                           C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8),
+                                           C.POINTER(C.c_uint8), C.POINTER(C.c_int32), C.POINTER(C.c_float), C.POINTER(C.c_uint8),
+                                           C.POINTER(C.c_uint8)]),
     "tg_selftest_scene_plan": (C.c_int, [C.c_int32, _fp, C.c_int32, C.POINTER(C.c_int32), _u8p, _u8p, C.c_int32, C.c_int32, C.POINTER(TgScenePlan), _fp,
                                          C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "tg_selftest_scene": (C.c_int, [C.POINTER(TgSceneTest), C.c_int32, _fp, _u8p, _u8p, _u8p]),

@@ -830,6 +830,12 @@ __global__ __launch_bounds__(kThreads, 6) void k_render_small(RasterParams P, St
 // clock, 100 MHz), printed by raster_debug_stats()
 __device__ unsigned long long g_blk_log[1024 * 4 * 8];
 __device__ int g_blk_nt[1024 * 2];
+// ... and, summed over every launch: launches, then per workgroup the wave-passes (one wavefront, one record, 64 quads) that got past the
+// scalar reach test (issued) and those in which at least one lane got past the per-lane rejects and ran the pixel loop (executed)
+__device__ unsigned long long g_blk_pass[1 + 1024 * 2];
+#define TG_PASS_WG (blockIdx.y < 1024 && blockIdx.x == 0 && blockIdx.z == 0)
+#define TG_PASS_ISSUED() do { if (lane == 0 && TG_PASS_WG) atomicAdd(&g_blk_pass[1 + 2 * blockIdx.y], 1ull); } while (0)
+#define TG_PASS_LIVE() do { const unsigned long long lv_ = __ballot(1); if (lane == (int)__builtin_ctzll(lv_) && TG_PASS_WG) atomicAdd(&g_blk_pass[2 + 2 * blockIdx.y], 1ull); } while (0)
 #define TG_STAMP(i) do { if (lane == 0 && blockIdx.y < 1024 && blockIdx.x == 0 && blockIdx.z == 0) g_blk_log[(blockIdx.y * 4 + wave) * 8 + (i)] = wall_clock64(); } while (0)
 void raster_debug_stats() {
     static unsigned long long h[1024 * 4 * 8];
@@ -866,9 +872,16 @@ void raster_debug_stats() {
     fprintf(stderr, "\n");
     double an = 0, aT = 0; for (int g = 0; g < 1024; ++g) { an += nt[2 * g] & 255; aT += nt[2 * g + 1]; }
     fprintf(stderr, "  mean n %.2f mean T %.2f\n", an / 1024, aT / 1024);
+    static unsigned long long ps[1 + 2048];
+    if (hipMemcpyFromSymbol(ps, HIP_SYMBOL(g_blk_pass), sizeof ps) != hipSuccess || !ps[0]) return;
+    double pi = 0, pl = 0; for (int g = 0; g < 1024; ++g) { pi += (double)ps[1 + 2 * g]; pl += (double)ps[2 + 2 * g]; }
+    fprintf(stderr, "  wave-passes per image and launch, the four wavefronts together, over %llu launches (first 1024 envs): issued %.2f executed %.2f\n",
+            ps[0], pi / 1024 / (double)ps[0], pl / 1024 / (double)ps[0]);
 }
 #else
 #define TG_STAMP(i) do { } while (0)
+#define TG_PASS_ISSUED() do { } while (0)
+#define TG_PASS_LIVE() do { } while (0)
 void raster_debug_stats() {}
 #endif
 
@@ -885,16 +898,24 @@ void raster_debug_stats() {}
 //   3. only CHANGED blocks are written: RasterParams::drawn records per image which blocks do not hold the untouched-sensor image; blocks
 //      reached now are drawn, blocks drawn by the launch before and not reached now are restored (16-byte words, whole 128-byte lines),
 //      everything else is left alone - the observation buffer is read-only for the caller (TG_RASTER_REWRITE_ALL=1: no record).
-//   4. reached blocks are drawn by ALL four wavefronts together, 4 NQ = 12 blocks per round: wavefront w owns the w-th quarter of the rows
-//      of each, a lane NQ quads (one in each of NQ block groups) - whatever the contact patch looks like, the four wavefronts finish
-//      together, and the lanes of a visited record are in compact patches that mostly hit.  Records that reach none of a group's blocks
-//      are skipped as scalar branches; a quad whose depth plane is nowhere in front of what it holds is skipped per lane.
+//   4. every reached block is drawn whole by ONE wavefront (a lane is one quad of it) against the records that reach it, and the reached
+//      blocks are dealt to the four wavefronts by load - the number of records that reach them, counted per block in step 2 - so that
+//      the four finish together whatever the contact patch looks like (TG_BLK_DEAL = 1, below).  A quad whose depth plane is nowhere in
+//      front of what it holds is skipped per lane.  Until then (TG_BLK_DEAL = 0) ALL four wavefronts drew every block together, 4 NQ = 12
+//      blocks per round: wavefront w owned the w-th quarter of the rows of each, a lane NQ quads (one in each of NQ groups of four
+//      blocks), and a record that reached one block of a group was issued on all four wavefronts for all four blocks - 14.8 wave-passes
+//      per edge image ran the pixel loop where there are 11.1 (record, block) pairs (profiles/blk_deal.txt).
 // Against k_render_small (two workgroups per image, each lane carrying 8 quads spread over its half): half the set-ups, 4096 instead of
 // 8192 wavefronts at 1024 envs, no wavefront whose share of the image is the whole contact patch, a third of the HBM traffic.  The pixel
 // arithmetic is that of the other kernels, expression by expression; the depth test keeps the smallest d, so neither the record order
 // nor the conservative skips can change the image.  DESIGN.md 4.2 has the measurements and the per-phase timeline.
 #ifndef TG_BLK_NQ
 #define TG_BLK_NQ 3
+#endif
+// TG_BLK_DEAL (A/B builds, like TG_BLK_NQ): 1 = step 4 draws every reached block whole on ONE wavefront, the reached blocks dealt to the
+// four wavefronts by load (the number of records that reach them); 0 = the rounds of 4 NQ blocks described above.
+#ifndef TG_BLK_DEAL
+#define TG_BLK_DEAL 1
 #endif
 template <int BW>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_render_blocks(RasterParams P, Stimulus S, const float* __restrict__ xform, int xform_soa, int n_envs,
@@ -910,6 +931,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     extern __shared__ TriRec recs[];
     __shared__ int count;
     __shared__ unsigned long long reach_rec[64], reach_all;    // per record: the blocks it can change; their union
+#if TG_BLK_DEAL
+    __shared__ unsigned blk_cnt[64];                           // per block: the records that reach it (the block's load in step 4)
+#endif
     const int env = blockIdx.y;
     if (mask != nullptr && mask[env] == 0) return;
     const int n_tris = S.n_tris;
@@ -939,6 +963,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     // of the mesh beyond the near plane) is a ballot, and the record counter is cleared by the wavefront that then counts (LDS operations
     // of one wavefront execute in order) - one workgroup barrier instead of four
     if (tid == 0) { count = 0; reach_all = 0ull; }
+#if TG_BLK_DEAL
+    if (tid < 64) blk_cnt[tid] = 0u;                               // (added to after the barrier below)
+#endif
     const bool has = tid < n_tris;                                 // (lanes of wavefront 0)
     float cx[3] = {0.0f, 0.0f, 0.0f}, cy[3] = {0.0f, 0.0f, 0.0f}, cw[3] = {0.0f, 0.0f, 0.0f};
     bool beyond = true;
@@ -1018,6 +1045,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         const float X0 = (float)(rx + (lane % NBX) * BW) + 0.5f, Y0 = (float)(ry + (lane / NBX) * BH) + 0.5f;   // first / last pixel centres
         const float X1 = X0 + (float)(BW - 1), Y1 = Y0 + (float)(BH - 1);
         unsigned long long part = 0ull;
+        unsigned nreach = 0u;                           // records of this wavefront's share that reach this lane's block
 #define TG_RL(v) __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(v), t))
         for (int t = wave; t < n; t += 4) {
             const float xl = TG_RL(q_xl), xh = TG_RL(q_xh), yl = TG_RL(q_yl), yh = TG_RL(q_yh), dm = TG_RL(q_dm);
@@ -1030,9 +1058,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
             if (kEdgeReach) miss = miss | edges_exclude_rect(x0, y0, TG_RL(q_x1), TG_RL(q_y1), TG_RL(q_x2), TG_RL(q_y2), X0, X1, Y0, Y1);
             const unsigned long long m = __ballot(!miss);
             part |= m;
+            nreach += miss ? 0u : 1u;
             if (lane == 0) reach_rec[t] = m;
         }
         if (lane == 0 && part) atomicOr(&reach_all, part);
+#if TG_BLK_DEAL
+        if (nreach) atomicAdd(&blk_cnt[lane], nreach);
+#endif
         __syncthreads();
         reached = reach_all;
     }
@@ -1045,6 +1077,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
         g_blk_nt[2 * blockIdx.y] = n | ((xcc & 15) << 8) | (((hw >> 8) & 15) << 12) | (((hw >> 13) & 7) << 16) | (((hw >> 12) & 1) << 20);
         g_blk_nt[2 * blockIdx.y + 1] = __builtin_popcountll(reached);
+        if (blockIdx.y == 0) atomicAdd(&g_blk_pass[0], 1ull);
     }
 #endif
     const unsigned long long restore = stale & ~reached;      // blocks to bring back to the untouched-sensor image
@@ -1078,8 +1111,103 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         for (int i = 0; i < NCP; ++i)
             if (TG_RESTORE(i)) *reinterpret_cast<uint4*>(dst + TG_COFF(i)) = tv[i];
     }
-    // 4. reached blocks, 4 NQ per round, every wavefront a quarter of each
     TG_STAMP(4);
+#if TG_BLK_DEAL
+    // 4. reached blocks, each drawn whole by one wavefront (a lane is one quad of the block: row lane / 4, columns 4 (lane % 4) ...): a record
+    //    is visited once per block it reaches and by nobody else - in rounds of block groups a record that reached one block of a group was
+    //    issued on all four wavefronts for all four blocks.  The blocks are dealt by load: ranked by the number of records that reach them
+    //    (descending, ties by block index: one ballot per distinct count), the ranks go to the wavefronts in snake order 0123 3210 ...,
+    //    rotated by the env so that wavefront 0 - the same SIMD in every workgroup, possibly - is not always served first.
+    unsigned long long mine;
+    {
+        const int c_l = (int)blk_cnt[lane];
+        int rank = 0, base = 0;
+        for (int c = n; c > 0; --c) {
+            const unsigned long long m = __ballot(c_l == c);
+            if (!m) continue;
+            rank = c_l == c ? base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) : rank;
+            base += __builtin_popcountll(m);
+        }
+        const int s8 = rank & 7, w0 = s8 < 4 ? s8 : 7 - s8;
+        mine = __ballot((((reached >> lane) & 1ull) != 0ull) & (((w0 + env) & 3) == wave));     // every reached block has exactly one owner
+    }
+    const unsigned long long rr_l = lane < n ? reach_rec[lane] : 0ull;      // lane-as-record again: the blocks record `lane` reaches
+    static_assert(BW == 16 && BH == 16, "64 quads per block: one per lane");
+    const int drow = lane >> 2, dcol = 4 * (lane & 3);
+    // the next block's inputs are fetched before the current block's record loop: the L2 round trip is off the wavefront's chain
+    size_t off_n = 0;
+    float4 nd_n = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    uchar4 ng_n = make_uchar4(0, 0, 0, 0), bm_n = ng_n, old_n = ng_n;
+#define TG_BLK_FETCH(b) do { \
+        off_n = (size_t)(ry + ((b) / NBX) * BH + drow) * P.W + (rx + ((b) % NBX) * BW + dcol); \
+        nd_n = *reinterpret_cast<const float4*>(nodef_dep + off_n); \
+        ng_n = *reinterpret_cast<const uchar4*>(gray_u8 + off_n); \
+        bm_n = *reinterpret_cast<const uchar4*>(border + off_n); \
+        if (prev) old_n = *reinterpret_cast<const uchar4*>(dst + off_n); \
+    } while (0)
+    if (mine) TG_BLK_FETCH((int)__builtin_ctzll(mine));
+    while (mine) {
+        const int b = (int)__builtin_ctzll(mine);
+        mine &= mine - 1ull;
+        const size_t off = off_n;
+        const float4 nd = nd_n;
+        const uchar4 ng = ng_n, bmk = bm_n, old = old_n;
+        if (mine) TG_BLK_FETCH((int)__builtin_ctzll(mine));
+        const int qx = rx + (b % NBX) * BW + dcol;
+        const float fy = (float)(ry + (b / NBX) * BH + drow) + 0.5f;
+        float z[4] = {nd.x, nd.y, nd.z, nd.w};
+        unsigned long long rb = __ballot(((rr_l >> b) & 1ull) != 0ull);        // the records that reach block b
+        while (rb) {
+            const int t = (int)__builtin_ctzll(rb);
+            rb &= rb - 1ull;
+            TG_PASS_ISSUED();
+            const TriRec r = recs[t];
+            const float rA = TG_RL(q_A), rB = TG_RL(q_B), rmg = TG_RL(q_mg);
+            if (fy < r.ymin || fy > r.ymax) continue;
+            if ((float)qx + 3.5f < r.xmin || (float)qx + 0.5f > r.xmax) continue;
+            const float zmax = fmaxf(fmaxf(z[0], z[1]), fmaxf(z[2], z[3]));
+            if (r.dmin >= zmax) continue;
+            // the record's depth plane over the quad's four pixel centres (see 1.): nowhere in front of what the quad holds -> no pixel can pass d < z
+            const float qlow = (r.d0 + rA * (((float)qx + (rA >= 0.0f ? 0.5f : 3.5f)) - r.x0)) + rB * (fy - r.y0);
+            if (qlow - rmg >= zmax) continue;
+            TG_PASS_LIVE();
+            const float a0 = r.y2 - fy, a1 = r.y1 - fy, a2 = r.y0 - fy;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const float fx = (float)(qx + p) + 0.5f;
+                const float e0 = (r.x1 - fx) * a0 - (r.x2 - fx) * a1;
+                const float e1 = (r.x2 - fx) * a2 - (r.x0 - fx) * a0;
+                const float e2 = (r.x0 - fx) * a1 - (r.x1 - fx) * a2;
+                const bool box = (fx >= r.xmin) & (fx <= r.xmax);
+                const bool pos = (e0 >= 0.0f) & (e1 >= 0.0f) & (e2 >= 0.0f), neg = (e0 <= 0.0f) & (e1 <= 0.0f) & (e2 <= 0.0f);
+                const float s = (e0 + e1) + e2;
+                const float d = div_mid_range((e0 * r.d0 + e1 * r.d1) + e2 * r.d2, s);
+                const bool hit = box & (pos | neg) & (s != 0.0f) & (d < z[p]);
+                z[p] = hit ? d : z[p];
+            }
+        }
+        const float ndv[4] = {nd.x, nd.y, nd.z, nd.w};
+        const uint8_t ngv[4] = {ng.x, ng.y, ng.z, ng.w}, bmv[4] = {bmk.x, bmk.y, bmk.z, bmk.w};
+        uint8_t o[4] = {0, 0, 0, 0};
+        if ((z[0] != ndv[0]) | (z[1] != ndv[1]) | (z[2] != ndv[2]) | (z[3] != ndv[3])) {   // an unchanged depth gives 0 below
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                float diff = z[p] - ndv[p];
+                if (diff >= -eps && diff <= eps) diff = 0.0f;
+                const float pen = fabsf(diff);
+                const float cl = pen < 0.0f ? 0.0f : (pen > max_pen ? max_pen : pen);
+                o[p] = (uint8_t)(div_mid_range(cl, max_pen) * 255.0f);
+            }
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+            if (!P.turn_off_border && bmv[p] == 1) o[p] = ngv[p];
+        if (prev) *reinterpret_cast<uchar4*>(prev + off) = old;
+        *reinterpret_cast<uchar4*>(dst + off) = make_uchar4(o[0], o[1], o[2], o[3]);
+    }
+#undef TG_BLK_FETCH
+#else
+    // 4. reached blocks, 4 NQ per round, every wavefront a quarter of each
     unsigned long long left = reached;
     while (left) {
         int bq[NQ];
@@ -1128,6 +1256,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
 #pragma unroll
             for (int j = 0; j < NQ; ++j) {
                 if (!(mt & grp[j])) continue;
+                TG_PASS_ISSUED();
                 if (fy[j] < r.ymin || fy[j] > r.ymax) continue;
                 if ((float)qx[j] + 3.5f < r.xmin || (float)qx[j] + 0.5f > r.xmax) continue;
                 const float zmax = fmaxf(fmaxf(z[j][0], z[j][1]), fmaxf(z[j][2], z[j][3]));
@@ -1135,6 +1264,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                 // the record's depth plane over the quad's four pixel centres (see 1.): nowhere in front of what the quad holds -> no pixel can pass d < z
                 const float qlow = (r.d0 + rA * (((float)qx[j] + (rA >= 0.0f ? 0.5f : 3.5f)) - r.x0)) + rB * (fy[j] - r.y0);
                 if (qlow - rmg >= zmax) continue;
+                TG_PASS_LIVE();
                 const float a0 = r.y2 - fy[j], a1 = r.y1 - fy[j], a2 = r.y0 - fy[j];
 #pragma unroll
                 for (int p = 0; p < 4; ++p) {
@@ -1183,6 +1313,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
             *reinterpret_cast<uchar4*>(dst + off[j]) = make_uchar4(o[0], o[1], o[2], o[3]);
         }
     }
+#endif
     TG_STAMP(5);
     TG_STAMP(6);
 #undef TG_RESTORE

@@ -47,11 +47,12 @@ int tg_selftest_render_kernel(const tg_sensor* sen, const tg_mesh* mesh, int32_t
     return 0;
 }
 
-int tg_selftest_render(const tg_sensor* sen, const tg_mesh* mesh, int32_t rows, int32_t cols, double grid_scale, const double* heights,
-                       const float* zoff, int32_t n, const float* xf, int32_t kernel, int32_t skip_quad_reject, int32_t fills_view,
-                       int32_t backface_cull, const uint8_t* mask, const float* term_xf, const uint8_t* term_mask, uint8_t* term_out,
-                       uint8_t* out, int32_t* launched) {
+int tg_selftest_render_twice(const tg_sensor* sen, const tg_mesh* mesh, int32_t rows, int32_t cols, double grid_scale, const double* heights,
+                             const float* zoff, int32_t n, const float* xf, int32_t kernel, int32_t skip_quad_reject, int32_t fills_view,
+                             int32_t backface_cull, const uint8_t* mask, const float* term_xf, const uint8_t* term_mask, uint8_t* term_out,
+                             uint8_t* out, int32_t* launched, const float* xf2, const uint8_t* mask2, uint8_t* prev) {
     if (!launched) return fail(-1, "NULL argument");
+    if (xf2 && !prev) return fail(-1, "a second launch saves the first one's images: prev is needed");
     *launched = -1;
     if (!xf || !out) return fail(-1, "NULL argument");
     if (!mesh && (!heights || !zoff)) return fail(-1, "a mesh or a heightfield");
@@ -62,7 +63,7 @@ int tg_selftest_render(const tg_sensor* sen, const tg_mesh* mesh, int32_t rows, 
     if (int rc = need_device()) return rc;
     const int H = sen->image_h, W = sen->image_w;
     const size_t npix = (size_t)H * W, cells = mesh ? 0 : (size_t)rows * cols;
-    DevBuf nd, ng, bm, xx, oo, mk, tx, tm, to, hh, zz, sp, bt;
+    DevBuf nd, ng, bm, xx, oo, mk, tx, tm, to, hh, zz, sp, bt, x2, m2, pv;
     if (nd.alloc(npix * 4) || ng.alloc(npix) || bm.alloc(npix) || xx.alloc((size_t)n * 48) || oo.alloc(npix * n)) return fail(-2, "hipMalloc failed");
     TG_HIP(hipMemcpy(nd.p, sen->nodef_dep, npix * 4, hipMemcpyHostToDevice));
     { std::vector<uint8_t> g8(npix); make_gray_u8(sen->nodef_gray, (int)npix, g8.data()); TG_HIP(hipMemcpy(ng.p, g8.data(), npix, hipMemcpyHostToDevice)); }
@@ -100,11 +101,29 @@ int tg_selftest_render(const tg_sensor* sen, const tg_mesh* mesh, int32_t rows, 
                                 (uint8_t*)oo.p, nullptr, (const float*)tx.p, (const uint8_t*)tm.p, (uint8_t*)to.p, 0);
     if (k < 0) return fail(-1, "the forced kernel cannot draw this input");
     TG_HIP(hipGetLastError());
+    if (xf2) {   // the same image buffer and the same block tables (the changed-block record of the first launch), the old images saved
+        if (x2.alloc((size_t)n * 48) || pv.alloc(npix * n) || (mask2 && m2.alloc((size_t)n))) return fail(-2, "hipMalloc failed");
+        TG_HIP(hipMemcpy(x2.p, xf2, (size_t)n * 48, hipMemcpyHostToDevice));
+        TG_HIP(hipMemcpy(pv.p, prev, npix * n, hipMemcpyHostToDevice));
+        if (mask2) TG_HIP(hipMemcpy(m2.p, mask2, (size_t)n, hipMemcpyHostToDevice));
+        if (launch_render(P, S, (const float*)x2.p, 0, n, (const uint8_t*)m2.p, (const float*)nd.p, (const uint8_t*)ng.p, (const uint8_t*)bm.p,
+                          (uint8_t*)oo.p, (uint8_t*)pv.p, nullptr, nullptr, nullptr, 0) != k) return fail(-3, "the second launch chose another kernel");
+        TG_HIP(hipGetLastError());
+    }
     TG_HIP(hipDeviceSynchronize());
+    if (xf2) TG_HIP(hipMemcpy(prev, pv.p, npix * n, hipMemcpyDeviceToHost));
     TG_HIP(hipMemcpy(out, oo.p, npix * n, hipMemcpyDeviceToHost));
     if (term_xf) TG_HIP(hipMemcpy(term_out, to.p, npix * n, hipMemcpyDeviceToHost));
     *launched = k;
     return 0;
+}
+
+int tg_selftest_render(const tg_sensor* sen, const tg_mesh* mesh, int32_t rows, int32_t cols, double grid_scale, const double* heights,
+                       const float* zoff, int32_t n, const float* xf, int32_t kernel, int32_t skip_quad_reject, int32_t fills_view,
+                       int32_t backface_cull, const uint8_t* mask, const float* term_xf, const uint8_t* term_mask, uint8_t* term_out,
+                       uint8_t* out, int32_t* launched) {
+    return tg_selftest_render_twice(sen, mesh, rows, cols, grid_scale, heights, zoff, n, xf, kernel, skip_quad_reject, fills_view, backface_cull,
+                                    mask, term_xf, term_mask, term_out, out, launched, nullptr, nullptr, nullptr);
 }
 
 const char* tg_selftest_last_error(void) { return g_err.c_str(); }
