@@ -726,6 +726,35 @@ int tg_vecnorm_apply(int32_t n_arrays, const float* const* x_dev, float* const* 
                      int64_t R, double clip_obs, double epsilon, const float* rewards_dev, float* rewards_out, int64_t n_rewards,
                      const double* ret_stats_dev, double clip_reward, double* returns_dev, const uint8_t* dones_dev, int64_t n_reset,
                      void* hip_stream);
+
+/* ---- device action heads: what stable_baselines3 does between the policy's output and venv.step(), use_sde=False --------------
+ * Context free; ONE launch on hip_stream, nothing is allocated or synchronised.  mean_dev: float32 [N][A]; log_std_dev: float32 [A] with
+ * log_std_stride 0 (PPO's state-independent parameter) or [N][A] with log_std_stride A (SAC's network output), clamped to
+ * [log_std_min, log_std_max] first (-inf / +inf: no clamp); lo, hi: the action space's bounds, float32 host arrays of A entries read before the
+ * call returns.  Float32 arithmetic with one rounding per operation; exp, tanh, log and the draw are evaluated in double on the float32 argument
+ * and rounded to float32 once.  With ls the clamped log_std, sigma = (float) exp(ls), eps the draw and x = mean + sigma eps:
+ *   TG_HEAD_GAUSSIAN  (DiagGaussianDistribution, PPO)   actions = x;  env = min(max(x, lo), hi) (np.clip; a NaN passes);
+ *                     log_prob[i] = sum_j (-(x - mean)^2 / (2 sigma^2) - ls - log sqrt(2 pi)), float32, j ascending
+ *   TG_HEAD_SQUASHED  (SquashedDiagGaussianDistribution, SAC)   a = (float) tanh(x);  actions = a;  env = lo + 0.5 (a + 1) (hi - lo)
+ *                     (unscale_action), clipped to [lo, hi] (the float32 formula can leave it by one rounding at a = +-1);
+ *                     log_prob[i] = the Gaussian sum - sum_j (float) log(1 - a a + 1e-6f)
+ *   TG_HEAD_UNIFORM   (SAC before learning_starts)   env = lo + (hi - lo) u, u = 24 bits 2^-24 of element e = i A + j of tg_sample_actions'
+ *                     generator at (seed, counter), at most hi;  actions = 2 ((env - lo) / (hi - lo)) - 1 (scale_action).  mean_dev and log_std_dev are
+ *                     not read (they may be NULL); gaussian_out and log_prob_out are not written.
+ * The draw: k1, k2 = the 24 bits of elements 2 e and 2 e + 1;  eps = (float) (sqrt(-2 log((k1 + 1) 2^-24)) cos(2 pi k2 2^-24)), in double;
+ * |eps| <= 5.77.  deterministic != 0: eps = 0.  noise_in_dev (nullable, float32 [N][A]) is used in place of the draws (of u in the uniform
+ * mode).  Every output is nullable: actions_out, env_actions_out, gaussian_out (x), noise_out [N][A], log_prob_out [N].  N = 0 does nothing.
+ * Errors, each without a launch: NULL mean_dev or log_std_dev in a Gaussian mode, A outside [1, TG_HEAD_MAX_ACT], a stride other than 0 or A,
+ * lo[j] > hi[j], lo[j] == hi[j] in the squashed or uniform mode, log_std_min > log_std_max, an unknown mode. */
+#define TG_HEAD_GAUSSIAN 0
+#define TG_HEAD_SQUASHED 1
+#define TG_HEAD_UNIFORM 2
+#define TG_HEAD_MAX_ACT 16
+#define TG_HEAD_MAX_ROWS 2147483647
+int tg_action_head(const float* mean_dev, const float* log_std_dev, int32_t log_std_stride, int64_t N, int32_t A, const float* lo, const float* hi,
+                   float log_std_min, float log_std_max, int32_t mode, int32_t deterministic, uint64_t seed, uint64_t counter,
+                   const float* noise_in_dev, float* actions_out, float* env_actions_out, float* gaussian_out, float* log_prob_out,
+                   float* noise_out, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,10 @@ loudly when the HIP library or a GPU is missing.
     rb = tg.DeviceReplayBuffer.for_env(venv, 100_000)   # SB3's replay buffer (SAC / RAD_SAC) in device memory (tg.replay; imports torch)
     rb.start(venv.reset()); venv.step(actions); rb.add_from_env(actions); batch = rb.sample(64, augment=aug)
     vn = tg.DeviceVecNormalize(venv, gamma=0.95)        # SB3's VecNormalize on the device (tg.vecnorm; imports torch); rb.sample(64, env=vn)
+    head = tg.DeviceDiagGaussian.for_env(venv)          # SB3's Gaussian sample, log-prob and clip in one launch (tg.action_head; imports torch);
+    actions, env_actions, log_prob = head.sample(mean, log_std)   # tg.DeviceSquashedDiagGaussian: SAC's tanh head and its uniform warm-up
+    obs, starts = tg.collect.collect_rollouts(venv, policy, buf, head, n_steps, obs, starts)   # SB3's two collection loops over the device pieces
+    obs, num_timesteps = tg.collect.collect_transitions(venv, actor, rb, head, n_steps, num_timesteps, learning_starts, obs)
 """
 from . import rl_envs  # noqa: F401  (registers the env ids)
 from .registry import make, make_vec, register, registered_ids  # noqa: F401
@@ -24,7 +28,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("augment", "rollout", "replay", "vecnorm"):   # imported on first use: they need torch, the rest of the package does not
+    if name in ("augment", "rollout", "replay", "vecnorm", "action_head", "collect"):   # imported on first use: they need torch, the rest of the package does not
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "DeviceRolloutBuffer":
@@ -36,4 +40,7 @@ def __getattr__(name):
     if name == "DeviceVecNormalize":
         import importlib
         return importlib.import_module(".vecnorm", __name__).DeviceVecNormalize
+    if name in ("DeviceDiagGaussian", "DeviceSquashedDiagGaussian"):
+        import importlib
+        return getattr(importlib.import_module(".action_head", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -34,6 +34,7 @@ ROLLOUT_MAX_ARRAYS = 16                      # TG_ROLLOUT_MAX_ARRAYS
 ROLLOUT_COPY, ROLLOUT_FLAG_U8 = 0, 1         # TG_ROLLOUT_* array kinds (tg_rollout_add)
 ROLLOUT_DONES = {"uint8": 0, "float32": 1}   # TG_ROLLOUT_DONES_* (tg_rollout_gae)
 VECNORM_MAX_ARRAYS, VECNORM_MAX_WIDTH, VECNORM_MAX_ROWS = 4, 512, 65535   # TG_VECNORM_* (tg_vecnorm_update, tg_vecnorm_apply)
+HEAD_GAUSSIAN, HEAD_SQUASHED, HEAD_UNIFORM, HEAD_MAX_ACT = 0, 1, 2, 16   # TG_HEAD_* (tg_action_head)
 OBS_STACK_KEY = dict(OBS_KEY, visual=3)   # + TG_OBS_KEY_VISUAL (ABI v16: the scene camera's images)
 NARROWPHASE = {"closed_form": 0, "gjk_manifold": 1, "gjk_single": 2}
 BALANCE_OBJECT = {"pole": 0, "ball_on_plate": 1, "spinning_plate": 2}
@@ -249,6 +250,8 @@ SYMBOLS = {
     "tg_vecnorm_apply": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p), C.c_int64,
                                    C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
                                    C.c_int64, C.c_void_p]),
+    "tg_action_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, _fp, _fp, C.c_float, C.c_float, C.c_int32, C.c_int32,
+                                 C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tg_get_state": (C.c_int, [_ctx, C.POINTER(TgStateView)]),
     "tg_set_joint_state": (C.c_int, [_ctx, _dp, _dp]),
     "tg_profile_enable": (C.c_int, [_ctx, C.c_int32]),

@@ -1,0 +1,232 @@
+"""numpy restatements of the device action heads (tactile_gym_amd.action_head; csrc/tg_action_head.hip).
+
+`device_order(...)` follows k_action_head operation for operation: every float32 operation is one numpy float32 operation (numpy's elementwise
+operations do not fuse), and exp, tanh, log and the Box-Muller draw are numpy float64 functions of the float32 argument, rounded to float32
+once.  The arithmetic-only paths (the clip, unscale_action, scale_action, the uniform draw, x from a given sigma) are therefore the kernel's
+bit for bit; the paths through a transcendental function agree with it to one float32 neighbour where the two double libraries round apart.
+
+`exact_*` evaluate SB3's formulas in float64 from given inputs, one stage at a time: x from (mean, log_std, eps), a from x, env from a,
+log_prob from (x, mean, log_std, a).  A test compares a float32 result with `exact_*` at the float32 inputs of that stage.
+
+The bounds.  U = 2^-24 is the float32 unit roundoff: one rounding of a value v errs by at most U |v|.  A transcendental function evaluated in
+double by a library good to a few double ulps and rounded to float32 lies within one float32 neighbour of the true value: at most 2 U |v|
+(counted as two roundings below).  First order in U; SLACK covers the second-order terms.
+
+  x = fl(mean + fl(sigma^ eps)), sigma^ = fl(exp(ls)):  sigma^ 2 U, the product U, the sum U:
+        |x^ - x| <= U (|x| + 3 |sigma eps|)                                                                        bound_x
+  a = fl(tanh(x)):  |a^ - a| <= 2 U |a|                                                                            bound_tanh
+  env = fl(lo + fl(fl(0.5 fl(a + 1)) fl(hi - lo))):  a + 1 U, the half exact, hi - lo U, the product U, the sum U:
+        |env^ - env| <= U (|env| + 3 |0.5 (a + 1) (hi - lo)|)                                                      bound_unscale
+     (the clip to [lo, hi] that follows moves env^ towards the true value, which lies inside)
+  the Gaussian sum, per column t = (x - mean)^2 / (2 sigma^2), T = t + |ls| + C, C = log sqrt(2 pi):
+        d = fl(x - mean) U;  q = fl(d d) 2 U + U;  var = fl(sigma^ sigma^) 4 U + U;  2 var exact;  t^ = fl(q / den) one more: 9 U t
+        t1 = fl(-t^ - ls) U (t + |ls|);  C^ = fl(C) U C;  term = fl(t1 - C^) U T:   per column <= U (11 t + 2 |ls| + 2 C) <= 11 U T
+        the A - 1 inexact additions of the row sum, each U |partial sum| <= U sum_j T_j
+        |G^ - G| <= U (A + 10) sum_j T_j                                                                           bound_gaussian_sum
+     with log(sigma^) for ls (torch's Normal.log_prob: log of the rounded exp) each column adds 2 U (from sigma^) + 2 U |ls| (the log):
+        + U sum_j (2 + 2 |ls_j|)                                                                                   (log_of_exp=True)
+  the tanh correction, per column w = 1 - a^2 + 1e-6:  aa = fl(a a) U a^2;  om = fl(1 - aa) U |om|;  w^ = fl(om + fl(1e-6)) U w + U 1e-6:
+        |w^ - w| <= U (a^2 + |1 - a^2| + w + 1e-6) =: e_w;   log w has the condition number 1 / w:  |log w^ - log w| <= e_w / w
+        c = fl(log w^) 2 U |log w|;  the A - 1 additions U sum_j |log w_j|;  the final subtraction U |log_prob|
+        |L^ - L| <= bound_gaussian_sum + sum_j (e_w_j / w_j + 2 U |log w_j|) + U (A - 1) sum_j |log w_j| + U |L|   bound_squashed_sum
+"""
+import numpy as np
+
+U = 2.0 ** -24
+SLACK = 1.0 + 1e-5
+MASK = (1 << 64) - 1
+GOLDEN = 0x9E3779B97F4A7C15
+LOG_SQRT_2PI = 0.9189385332046727
+GAUSSIAN, SQUASHED, UNIFORM = 0, 1, 2
+EPSILON = 1e-6
+_f32 = np.float32
+
+
+# ---------------------------------------------------------------------------------------------------------------- the generator
+def _mix64(z):
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def bits24(seed, counter, elements):
+    """The 24 random bits of `elements` (any integer array) of draw `counter`: tg_sample_actions' integers."""
+    with np.errstate(over="ignore"):
+        base = _mix64(np.uint64((seed + GOLDEN * (counter + 1)) & MASK))
+        e = np.asarray(elements, dtype=np.uint64)
+        return (_mix64(base + np.uint64(GOLDEN) * (e + np.uint64(1))) >> np.uint64(40)).astype(np.int64)
+
+
+def bits24_int(seed, counter, e):
+    """The same with Python integers."""
+    def mix(z):
+        z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & MASK
+        z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & MASK
+        return z ^ (z >> 31)
+    return mix((mix((seed + GOLDEN * (counter + 1)) & MASK) + GOLDEN * (e + 1)) & MASK) >> 40
+
+
+def uniform_draws(seed, counter, n):
+    """u of elements 0 .. n - 1, float32 in [0, 1): tg_sample_actions' floats before the scaling."""
+    return bits24(seed, counter, np.arange(n)).astype(_f32) * _f32(1.0 / 16777216.0)
+
+
+def normal_draws(seed, counter, n):
+    """eps of elements 0 .. n - 1: Box-Muller in double on the 24-bit values of elements 2 e and 2 e + 1, rounded to float32."""
+    e = np.arange(n, dtype=np.int64)
+    u1 = (bits24(seed, counter, 2 * e) + 1).astype(np.float64) * (1.0 / 16777216.0)
+    u2 = bits24(seed, counter, 2 * e + 1).astype(np.float64) * (1.0 / 16777216.0)
+    return (np.sqrt(-2.0 * np.log(u1)) * np.cos(6.283185307179586 * u2)).astype(_f32)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the kernel's order
+def clamp(ls, lo, hi):
+    ls = np.asarray(ls, dtype=_f32)
+    return np.where(ls < _f32(lo), _f32(lo), np.where(ls > _f32(hi), _f32(hi), ls)).astype(_f32)
+
+
+def clip_f32(x, lo, hi):
+    """The kernel's clip: x < lo ? lo : x, then > hi ? hi : that (a NaN passes) - np.clip for lo <= hi."""
+    up = np.where(x < lo, lo, x)
+    return np.where(up > hi, hi, up).astype(_f32)
+
+
+def unscale_f32(a, lo, hi):
+    return (lo + (_f32(0.5) * (a + _f32(1.0))) * (hi - lo)).astype(_f32)
+
+
+def unscale_env_f32(a, lo, hi):
+    """The squashed mode's env_actions: unscale_action, then the clip - at a = +-1 the float32 formula can leave [lo, hi] by one rounding
+    when hi - lo is inexact, and the env is never handed an action outside its space."""
+    return clip_f32(unscale_f32(a, lo, hi), lo, hi)
+
+
+def scale_f32(env, lo, hi):
+    return (_f32(2.0) * ((env - lo) / (hi - lo)) - _f32(1.0)).astype(_f32)
+
+
+def device_order(mode, mean, log_std, lo, hi, log_std_min=-np.inf, log_std_max=np.inf, deterministic=False, seed=0, counter=0, noise=None,
+                 shape=None):
+    """What one tg_action_head call writes: dict(actions, env, gaussian, log_prob, noise) of float32 arrays (gaussian / log_prob None in the
+    uniform mode).  mean [N, A]; log_std [A] or [N, A]; lo, hi [A]; noise: given in place of the draws.  shape: (N, A) of the uniform mode."""
+    with np.errstate(all="ignore"):                      # infinities and NaNs pass through as they do on the device
+        return _device_order(mode, mean, log_std, lo, hi, log_std_min, log_std_max, deterministic, seed, counter, noise, shape)
+
+
+def _device_order(mode, mean, log_std, lo, hi, log_std_min, log_std_max, deterministic, seed, counter, noise, shape):
+    lo, hi = np.asarray(lo, dtype=_f32), np.asarray(hi, dtype=_f32)
+    if mode == UNIFORM:
+        N, A = shape if shape is not None else np.asarray(mean).shape
+        u = np.asarray(noise, dtype=_f32) if noise is not None else uniform_draws(seed, counter, N * A).reshape(N, A)
+        span = hi - lo
+        env = np.minimum(lo + span * u, hi).astype(_f32)   # the sum can round one neighbour past hi
+        return dict(actions=scale_f32(env, lo, hi), env=env, gaussian=None, log_prob=None, noise=u)
+    mean = np.asarray(mean, dtype=_f32)
+    N, A = mean.shape
+    ls = np.broadcast_to(clamp(log_std, log_std_min, log_std_max), (N, A))
+    sigma = np.exp(ls.astype(np.float64)).astype(_f32)
+    if noise is not None:
+        eps = np.asarray(noise, dtype=_f32)
+    elif deterministic:
+        eps = np.zeros((N, A), _f32)
+    else:
+        eps = normal_draws(seed, counter, N * A).reshape(N, A)
+    x = (mean + sigma * eps).astype(_f32)
+    d = x - mean
+    t = (d * d) / (_f32(2.0) * (sigma * sigma))
+    term = ((-t - ls) - _f32(LOG_SQRT_2PI)).astype(_f32)
+    gsum = np.zeros(N, _f32)
+    for j in range(A):
+        gsum = gsum + term[:, j]
+    if mode == GAUSSIAN:
+        return dict(actions=x, env=clip_f32(x, lo, hi), gaussian=x, log_prob=gsum, noise=eps)
+    a = np.tanh(x.astype(np.float64)).astype(_f32)
+    w = (_f32(1.0) - a * a) + _f32(EPSILON)
+    c = np.log(w.astype(np.float64)).astype(_f32)
+    csum = np.zeros(N, _f32)
+    for j in range(A):
+        csum = csum + c[:, j]
+    return dict(actions=a, env=unscale_env_f32(a, lo, hi), gaussian=x, log_prob=(gsum - csum).astype(_f32), noise=eps)
+
+
+# ---------------------------------------------------------------------------------------------------------------- float64, stage by stage
+def _f64(*xs):
+    return [np.asarray(x, dtype=np.float64) for x in xs]
+
+
+def exact_x(mean, ls, eps):
+    mean, ls, eps = _f64(mean, ls, eps)
+    return mean + np.exp(ls) * eps
+
+
+def exact_tanh(x):
+    return np.tanh(_f64(x)[0])
+
+
+def exact_unscale(a, lo, hi):
+    a, lo, hi = _f64(a, lo, hi)
+    return lo + 0.5 * (a + 1.0) * (hi - lo)
+
+
+def exact_scale(env, lo, hi):
+    env, lo, hi = _f64(env, lo, hi)
+    return 2.0 * ((env - lo) / (hi - lo)) - 1.0
+
+
+def gaussian_terms(x, mean, ls):
+    """[N, A]: -(x - mean)^2 / (2 sigma^2) - ls - log sqrt(2 pi)."""
+    x, mean, ls = _f64(x, mean, ls)
+    return -(x - mean) ** 2 / (2.0 * np.exp(2.0 * ls)) - ls - LOG_SQRT_2PI
+
+
+def correction_terms(a):
+    a = _f64(a)[0]
+    return np.log(1.0 - a * a + EPSILON)
+
+
+def exact_log_prob(x, mean, ls, a=None):
+    """[N]: the Gaussian sum, minus the tanh correction when `a` (the squashed actions) is given."""
+    g = gaussian_terms(x, mean, ls).sum(axis=1)
+    return g if a is None else g - correction_terms(a).sum(axis=1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- the bounds (module docstring)
+def bound_x(mean, ls, eps):
+    mean, ls, eps = _f64(mean, ls, eps)
+    se = np.abs(np.exp(ls) * eps)
+    return SLACK * U * (np.abs(mean + np.exp(ls) * eps) + 3.0 * se)
+
+
+def bound_tanh(x):
+    return SLACK * 2.0 * U * np.abs(np.tanh(_f64(x)[0]))
+
+
+def bound_unscale(a, lo, hi):
+    a, lo, hi = _f64(a, lo, hi)
+    return SLACK * U * (np.abs(exact_unscale(a, lo, hi)) + 3.0 * np.abs(0.5 * (a + 1.0) * (hi - lo)))
+
+
+def bound_gaussian_sum(x, mean, ls, log_of_exp=False):
+    x, mean, ls = _f64(x, mean, ls)
+    ls = np.broadcast_to(ls, x.shape)
+    A = x.shape[1]
+    T = (x - mean) ** 2 / (2.0 * np.exp(2.0 * ls)) + np.abs(ls) + LOG_SQRT_2PI
+    b = U * (A + 10) * T.sum(axis=1)
+    if log_of_exp:
+        b = b + U * (2.0 + 2.0 * np.abs(ls)).sum(axis=1)
+    return SLACK * b
+
+
+def bound_correction_sum(a):
+    """The tanh correction's share of bound_squashed_sum: sum_j (e_w_j / w_j + 2 U |log w_j|) + U (A - 1) sum_j |log w_j|."""
+    a = _f64(a)[0]
+    A = a.shape[1]
+    w = 1.0 - a * a + EPSILON
+    e_w = U * (a * a + np.abs(1.0 - a * a) + w + EPSILON)
+    logw = np.abs(np.log(w))
+    return SLACK * ((e_w / w + 2.0 * U * logw).sum(axis=1) + U * (A - 1) * logw.sum(axis=1))
+
+
+def bound_squashed_sum(x, mean, ls, a, log_of_exp=False):
+    total = np.abs(exact_log_prob(x, mean, ls, a))
+    return bound_gaussian_sum(x, mean, ls, log_of_exp) + bound_correction_sum(a) + SLACK * U * total
