@@ -321,7 +321,12 @@ int tg_unpack_interior(tg_ctx* ctx, const void* src_dev, int32_t n_images, void*
  * 16 x 16 tiles, only the tiles that differ from that constant template travel (lossless; 9 % of the bytes of an edge_follow batch, 22 % of
  * object_balance at 256 x 256, 48 % surface_follow, 73 % object_push).  Message: one 16-byte header {u32 count, n_images, tiles per image,
  * magic} and `count` records of 272 bytes {u32 tile id = image * tiles_per_image + tile, 12 bytes pad, 16 rows x 16 pixels}; records are in
- * no particular order.  These entry points are context free (raw device pointers + a HIP stream; NULL = the default stream).
+ * no particular order.  A reader tolerates what no pack kernel writes: a header whose magic or tiles per image is not its own is no message
+ * (the template everywhere), a count above n_images * tiles_per_image is clamped to that, and a record whose id is not below
+ * n_images * tiles_per_image - compared as unsigned 32-bit numbers - is ignored (with a list of previous ids the id is still recorded there,
+ * and ignored again by the restore).  These entry points are context free (raw device pointers + a HIP stream; NULL = the default stream).
+ * obs_dev, template_dev, src_dev and dst_dev of the tile entries are read and written 16 bytes at a time: each must be 16-byte aligned
+ * (src_stride a multiple of 16 keeps every rank's message so); a pointer that is not is refused with -1, like a NULL one, before any launch.
  * tg_get_tile_template: the template of a context's sensor, uint8 [H][W] (device).
  * tg_pack_tiles: obs uint8 [n_images][h][w] -> dst (tg_tiles_capacity bytes; may be another GPU's memory opened with tg_ipc_open);
  *   counters_dev = two zeroed uint32 in LOCAL device memory (left zero again by every launch); tail_src_dev (may be NULL): tail_bytes (<= 1 MiB)

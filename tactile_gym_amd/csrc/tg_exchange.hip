@@ -111,8 +111,8 @@ __global__ __launch_bounds__(256) void k_scatter_tiles(const uint8_t* __restrict
     if (slot >= count) return;
     const uint4* __restrict__ rec = reinterpret_cast<const uint4*>(src + 16) + (size_t)slot * kRecWords;
     const uint32_t id = rec[0].x;
+    if (id >= cap) return;                                                  // compared unsigned: with T = 1 an id >= 2^31 would be a negative image
     const int img = (int)(id / (uint32_t)T), tile = (int)(id - (uint32_t)img * (uint32_t)T);
-    if (img >= n_img) return;
     const int tr = tile / TW, tc = tile - tr * TW;
     *reinterpret_cast<uint4*>(dst + (size_t)img * H * W + (size_t)(tr * 16 + row) * W + (size_t)tc * 16) = rec[1 + row];
 }
@@ -141,8 +141,8 @@ __global__ __launch_bounds__(256) void k_scatter_tiles_multi(const uint8_t* __re
     for (uint32_t slot = blockIdx.x * 16u + (threadIdx.x >> 4); slot < count; slot += gridDim.x * 16u) {
         const uint4* __restrict__ rec = reinterpret_cast<const uint4*>(s + 16) + (size_t)slot * kRecWords;
         const uint32_t id = rec[0].x;
+        if (id >= cap) continue;
         const int img = (int)(id / (uint32_t)T), tile = (int)(id - (uint32_t)img * (uint32_t)T);
-        if (img >= n_img) continue;
         const int tr = tile / TW, tc = tile - tr * TW;
         *reinterpret_cast<uint4*>(d + (size_t)img * H * W + (size_t)(tr * 16 + row) * W + (size_t)tc * 16) = rec[1 + row];
     }
@@ -162,8 +162,8 @@ __global__ __launch_bounds__(256) void k_restore_tiles_multi(const uint8_t* __re
     const int row = threadIdx.x & 15;
     for (uint32_t slot = blockIdx.x * 16u + (threadIdx.x >> 4); slot < count; slot += gridDim.x * 16u) {
         const uint32_t id = pl[1 + slot];
+        if (id >= cap) continue;
         const int img = (int)(id / (uint32_t)T), tile = (int)(id - (uint32_t)img * (uint32_t)T);
-        if (img >= n_img) continue;
         const int tr = tile / TW, tc = tile - tr * TW;
         const size_t off = (size_t)(tr * 16 + row) * W + (size_t)tc * 16;
         *reinterpret_cast<uint4*>(d + (size_t)img * H * W + off) = *reinterpret_cast<const uint4*>(tmpl + off);
@@ -186,8 +186,8 @@ __global__ __launch_bounds__(256) void k_scatter_tiles_multi_keep(const uint8_t*
         const uint4* __restrict__ rec = reinterpret_cast<const uint4*>(s + 16) + (size_t)slot * kRecWords;
         const uint32_t id = rec[0].x;
         if (row == 0) pl[1 + slot] = id;
+        if (id >= cap) continue;
         const int img = (int)(id / (uint32_t)T), tile = (int)(id - (uint32_t)img * (uint32_t)T);
-        if (img >= n_img) continue;
         const int tr = tile / TW, tc = tile - tr * TW;
         *reinterpret_cast<uint4*>(d + (size_t)img * H * W + (size_t)(tr * 16 + row) * W + (size_t)tc * 16) = rec[1 + row];
     }
@@ -256,6 +256,7 @@ int tg_pack_tiles(void* stream, const void* obs_dev, const void* template_dev, i
                   const void* tail_src_dev, int64_t tail_bytes, int64_t tail_offset) {
     if (!obs_dev || !template_dev || !dst_dev || !counters_dev || n_images <= 0 || !tg::tile_geometry(h, w))
         return report_error(-1, "tg_pack_tiles: bad argument (image sides must be multiples of 16)");
+    if (((uintptr_t)obs_dev | (uintptr_t)template_dev | (uintptr_t)dst_dev) & 15) return report_error(-1, "tg_pack_tiles: obs, template and dst must be 16-byte aligned");
     if (tail_src_dev && (tail_bytes < 0 || tail_bytes > (1 << 20) || tail_offset < 0 || (tail_offset & 15) || ((uintptr_t)tail_src_dev & 15)))
         return report_error(-1, "tg_pack_tiles: the tail must be at most 1 MiB, 16-byte aligned at both ends");
     const int TW = w / 16, T = TW * (h / 16), groups = (T + 63) / 64;
@@ -270,6 +271,7 @@ int tg_pack_tiles(void* stream, const void* obs_dev, const void* template_dev, i
 int tg_unpack_tiles(void* stream, const void* src_dev, const void* template_dev, int32_t n_images, int32_t h, int32_t w, void* dst_dev) {
     if (!src_dev || !template_dev || !dst_dev || n_images <= 0 || !tg::tile_geometry(h, w))
         return report_error(-1, "tg_unpack_tiles: bad argument (image sides must be multiples of 16)");
+    if (((uintptr_t)src_dev | (uintptr_t)template_dev | (uintptr_t)dst_dev) & 15) return report_error(-1, "tg_unpack_tiles: src, template and dst must be 16-byte aligned");
     const int TW = w / 16, T = TW * (h / 16);
     const int hw16 = h * w / 16;
     const size_t total16 = (size_t)n_images * hw16;
@@ -287,6 +289,8 @@ int tg_unpack_tiles_multi(void* stream, const void* src_dev, int64_t src_stride,
                           int32_t n_images, int32_t h, int32_t w, void* dst_dev, void* prev_ids_dev) {
     if (!src_dev || !template_dev || !dst_dev || n_images <= 0 || n_ranks <= 0 || n_ranks > 65535 || src_stride < 16 || (src_stride & 15) || !tg::tile_geometry(h, w))
         return report_error(-1, "tg_unpack_tiles_multi: bad argument (stride a multiple of 16, image sides multiples of 16)");
+    if (((uintptr_t)src_dev | (uintptr_t)template_dev | (uintptr_t)dst_dev) & 15 || ((uintptr_t)prev_ids_dev & 3))
+        return report_error(-1, "tg_unpack_tiles_multi: src, template and dst must be 16-byte aligned, prev_ids 4-byte aligned");
     const int TW = w / 16, T = TW * (h / 16);
     const int hw16 = h * w / 16;
     const size_t per_rank16 = (size_t)n_images * hw16;
