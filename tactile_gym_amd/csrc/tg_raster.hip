@@ -837,6 +837,70 @@ __device__ unsigned long long g_blk_pass[1 + 1024 * 2];
 #define TG_PASS_ISSUED() do { if (lane == 0 && TG_PASS_WG) atomicAdd(&g_blk_pass[1 + 2 * blockIdx.y], 1ull); } while (0)
 #define TG_PASS_LIVE() do { const unsigned long long lv_ = __ballot(1); if (lane == (int)__builtin_ctzll(lv_) && TG_PASS_WG) atomicAdd(&g_blk_pass[2 + 2 * blockIdx.y], 1ull); } while (0)
 #define TG_STAMP(i) do { if (lane == 0 && blockIdx.y < 1024 && blockIdx.x == 0 && blockIdx.z == 0) g_blk_log[(blockIdx.y * 4 + wave) * 8 + (i)] = wall_clock64(); } while (0)
+// The tail of the last launch: what a workgroup's end goes with - its own drawing load (the (record, block) pairs), the load of the four
+// workgroups that share its CU, or how late it started among them.
+static void tail_ranks(const double* v, double* r, int n) {     // average ranks (ties share)
+    for (int i = 0; i < n; ++i) { double lo = 0, eq = 0; for (int j = 0; j < n; ++j) { lo += v[j] < v[i]; eq += v[j] == v[i]; } r[i] = lo + 0.5 * (eq - 1.0); }
+}
+static double tail_rank_corr(const double* a, const double* b, int n) {
+    static double ra[1024], rb[1024];
+    tail_ranks(a, ra, n); tail_ranks(b, rb, n);
+    double ma = 0, mb = 0; for (int i = 0; i < n; ++i) { ma += ra[i]; mb += rb[i]; } ma /= n; mb /= n;
+    double sab = 0, saa = 0, sbb = 0; for (int i = 0; i < n; ++i) { sab += (ra[i] - ma) * (rb[i] - mb); saa += (ra[i] - ma) * (ra[i] - ma); sbb += (rb[i] - mb) * (rb[i] - mb); }
+    return saa > 0 && sbb > 0 ? sab / sqrt(saa * sbb) : 0.0;
+}
+static void raster_debug_tail(const unsigned long long* h, const int* nt, const unsigned long long* endt, unsigned long long t0) {
+    static int pairs[1024], cuo[1024], ord[1024], sorted[1024];
+    static unsigned long long startt[1024], s3[1024];
+    static double v_end[1024], v_own[1024], v_cu[1024], v_ord[1024];
+    for (int g = 0; g < 1024; ++g) {
+        pairs[g] = (nt[2 * g + 1] >> 8) & 0xffff; sorted[g] = pairs[g];
+        startt[g] = ~0ull; s3[g] = 0;
+        for (int w = 0; w < 4; ++w) {
+            const unsigned long long* e = h + (g * 4 + w) * 8;
+            if (e[7] && e[7] < startt[g]) startt[g] = e[7];
+            if (e[3] > s3[g]) s3[g] = e[3];
+        }
+        startt[g] = startt[g] == ~0ull ? 0 : startt[g] - t0; s3[g] = s3[g] > t0 ? s3[g] - t0 : 0;
+        cuo[g] = g;
+    }
+    for (int i = 0; i < 1024; ++i) for (int j = i + 1; j < 1024; ++j) if (sorted[j] < sorted[i]) { const int t = sorted[i]; sorted[i] = sorted[j]; sorted[j] = t; }
+    double mp = 0; for (int g = 0; g < 1024; ++g) mp += pairs[g];
+    fprintf(stderr, "  pairs per workgroup: min %d q1 %d median %d q3 %d p90 %d p95 %d p99 %d max %d mean %.2f\n", sorted[0], sorted[255], sorted[511], sorted[767],
+            sorted[921], sorted[972], sorted[1013], sorted[1023], mp / 1024);
+    fprintf(stderr, "  pairs histogram (pairs:workgroups):");
+    for (int i = 0; i < 1024;) { int j = i; while (j < 1024 && sorted[j] == sorted[i]) ++j; fprintf(stderr, " %d:%d", sorted[i], j - i); i = j; }
+    // by CU (key: xcc, se, sh, cu), then by start stamp
+    for (int i = 0; i < 1024; ++i) for (int j = i + 1; j < 1024; ++j) {
+        const int ki = nt[2 * cuo[i]] >> 8, kj = nt[2 * cuo[j]] >> 8;
+        if (kj < ki || (kj == ki && startt[cuo[j]] < startt[cuo[i]])) { const int t = cuo[i]; cuo[i] = cuo[j]; cuo[j] = t; }
+    }
+    fprintf(stderr, "\n  per CU (xcc.se.sh.cu: pairs in start order | starts | ends, x10 ns):\n");
+    double o3m[8] = {0}; unsigned long long o3x[8] = {0}; double oem[8] = {0}; int oc[8] = {0};
+    for (int i = 0; i < 1024;) {
+        int j = i; const int key = nt[2 * cuo[i]] >> 8;
+        while (j < 1024 && (nt[2 * cuo[j]] >> 8) == key) ++j;
+        int sum = 0; for (int k = i; k < j; ++k) sum += pairs[cuo[k]];
+        fprintf(stderr, "   x%d.s%d.h%d.c%d:", key & 15, (key >> 8) & 7, (key >> 12) & 1, (key >> 4) & 15);
+        for (int k = i; k < j; ++k) fprintf(stderr, " %d", pairs[cuo[k]]);
+        fprintf(stderr, " |"); for (int k = i; k < j; ++k) fprintf(stderr, " %llu", startt[cuo[k]]);
+        fprintf(stderr, " |"); for (int k = i; k < j; ++k) fprintf(stderr, " %llu", endt[cuo[k]]);
+        fprintf(stderr, "\n");
+        for (int k = i; k < j; ++k) {
+            const int g = cuo[k], o = k - i < 7 ? k - i : 7;
+            ord[g] = k - i; v_cu[g] = sum;
+            o3m[o] += (double)s3[g]; if (s3[g] > o3x[o]) o3x[o] = s3[g]; oem[o] += (double)endt[g]; ++oc[o];
+        }
+        i = j;
+    }
+    for (int g = 0; g < 1024; ++g) { v_end[g] = (double)endt[g]; v_own[g] = pairs[g]; v_ord[g] = ord[g]; }
+    fprintf(stderr, "  rank correlation of the workgroup's end with: own pairs %.3f, its CU's summed pairs %.3f, start order on the CU %.3f\n",
+            tail_rank_corr(v_end, v_own, 1024), tail_rank_corr(v_end, v_cu, 1024), tail_rank_corr(v_end, v_ord, 1024));
+    fprintf(stderr, "  by start order on the CU (workgroups: [3] mean / [3] max / mean end, x10 ns since launch start):");
+    for (int o = 0; o < 8; ++o) if (oc[o]) fprintf(stderr, " %d (%d): %.1f / %llu / %.1f |", o, oc[o], o3m[o] / oc[o], o3x[o], oem[o] / oc[o]);
+    double me = 0; unsigned long long xe = 0; for (int g = 0; g < 1024; ++g) { me += (double)endt[g]; if (endt[g] > xe) xe = endt[g]; }
+    fprintf(stderr, "\n  workgroup end: mean %.1f last %llu\n", me / 1024, xe);
+}
 void raster_debug_stats() {
     static unsigned long long h[1024 * 4 * 8];
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_blk_log), sizeof h) != hipSuccess) return;
@@ -860,18 +924,19 @@ void raster_debug_stats() {
     static int order[1024]; static unsigned long long endt[1024];
     for (int g = 0; g < 1024; ++g) { order[g] = g; endt[g] = 0; for (int w = 0; w < 4; ++w) if (h[(g * 4 + w) * 8 + 6] > endt[g]) endt[g] = h[(g * 4 + w) * 8 + 6]; endt[g] -= t0; }
     for (int i = 0; i < 1024; ++i) for (int j = i + 1; j < 1024; ++j) if (endt[order[j]] < endt[order[i]]) { int t = order[i]; order[i] = order[j]; order[j] = t; }
-    for (int i = 0; i < 1024; i += 64) fprintf(stderr, "   %llu %d %d |", endt[order[i]], nt[2 * order[i]] & 255, nt[2 * order[i] + 1]);
-    fprintf(stderr, "   %llu %d %d\n", endt[order[1023]], nt[2 * order[1023]] & 255, nt[2 * order[1023] + 1]);
+    for (int i = 0; i < 1024; i += 64) fprintf(stderr, "   %llu %d %d |", endt[order[i]], nt[2 * order[i]] & 255, (nt[2 * order[i] + 1] & 255));
+    fprintf(stderr, "   %llu %d %d\n", endt[order[1023]], nt[2 * order[1023]] & 255, (nt[2 * order[1023] + 1] & 255));
     fprintf(stderr, "  slowest 40 (end n T xcc se sh cu):");
-    for (int i = 1023; i > 983; --i) { const int v = nt[2 * order[i]]; fprintf(stderr, " %llu/%d/%d/x%d.s%d.h%d.c%d", endt[order[i]], v & 255, nt[2 * order[i] + 1], (v >> 8) & 15, (v >> 16) & 7, (v >> 20) & 1, (v >> 12) & 15); }
+    for (int i = 1023; i > 983; --i) { const int v = nt[2 * order[i]]; fprintf(stderr, " %llu/%d/%d/x%d.s%d.h%d.c%d", endt[order[i]], v & 255, (nt[2 * order[i] + 1] & 255), (v >> 8) & 15, (v >> 16) & 7, (v >> 20) & 1, (v >> 12) & 15); }
     fprintf(stderr, "\n  mean end per xcc:");
     for (int x = 0; x < 8; ++x) { double a = 0; int c = 0; for (int g = 0; g < 1024; ++g) if (((nt[2 * g] >> 8) & 15) == x) { a += (double)endt[g]; ++c; } fprintf(stderr, " x%d %.0f (%d)", x, c ? a / c : 0.0, c); }
     fprintf(stderr, "\n  workgroups per (xcc, se, sh, cu): ");
     { static int cnt[8 * 8 * 2 * 16]; for (int g = 0; g < 1024; ++g) { const int v = nt[2 * g]; ++cnt[((((v >> 8) & 15) * 8 + ((v >> 16) & 7)) * 2 + ((v >> 20) & 1)) * 16 + ((v >> 12) & 15)]; }
       int hist[16] = {0}; for (int i = 0; i < 8 * 8 * 2 * 16; ++i) if (cnt[i] < 16) ++hist[cnt[i]]; for (int i = 0; i < 12; ++i) fprintf(stderr, " %d:%d", i, hist[i]); }
     fprintf(stderr, "\n");
-    double an = 0, aT = 0; for (int g = 0; g < 1024; ++g) { an += nt[2 * g] & 255; aT += nt[2 * g + 1]; }
+    double an = 0, aT = 0; for (int g = 0; g < 1024; ++g) { an += nt[2 * g] & 255; aT += nt[2 * g + 1] & 255; }
     fprintf(stderr, "  mean n %.2f mean T %.2f\n", an / 1024, aT / 1024);
+    raster_debug_tail(h, nt, endt, t0);
     static unsigned long long ps[1 + 2048];
     if (hipMemcpyFromSymbol(ps, HIP_SYMBOL(g_blk_pass), sizeof ps) != hipSuccess || !ps[0]) return;
     double pi = 0, pl = 0; for (int g = 0; g < 1024; ++g) { pi += (double)ps[1 + 2 * g]; pl += (double)ps[2 + 2 * g]; }
@@ -905,6 +970,8 @@ void raster_debug_stats() {}
 //      blocks per round: wavefront w owned the w-th quarter of the rows of each, a lane NQ quads (one in each of NQ groups of four
 //      blocks), and a record that reached one block of a group was issued on all four wavefronts for all four blocks - 14.8 wave-passes
 //      per edge image ran the pixel loop where there are 11.1 (record, block) pairs (profiles/blk_deal.txt).
+//   The front end (set-up to the end of step 2) runs at raised wave priority, the drawing at the default (TG_BLK_PRIO, below): a
+//   workgroup that starts late on its CU is no longer held up in its latency chains by the drawing of those that started before it.
 // Against k_render_small (two workgroups per image, each lane carrying 8 quads spread over its half): half the set-ups, 4096 instead of
 // 8192 wavefronts at 1024 envs, no wavefront whose share of the image is the whole contact patch, a third of the HBM traffic.  The pixel
 // arithmetic is that of the other kernels, expression by expression; the depth test keeps the smallest d, so neither the record order
@@ -916,6 +983,15 @@ void raster_debug_stats() {}
 // four wavefronts by load (the number of records that reach them); 0 = the rounds of 4 NQ blocks described above.
 #ifndef TG_BLK_DEAL
 #define TG_BLK_DEAL 1
+#endif
+// TG_BLK_PRIO (A/B builds): 1 = the front end - set-up, lane-as-record, the reach masks: latency chains of loads, LDS round trips and two
+// barriers - issues at the top wave priority, and the wavefront drops to the default behind the barrier that ends step 2, before it
+// restores and draws; 0 = every wavefront at the default priority throughout.  s_setprio is a wave-local hint to the SIMD's arbiter: it
+// cannot change a result.  The arbiter serves priority, then age, so among the four workgroups of a CU the one that started last had its
+// front end starved by the drawing of the other three (reach masks done 3.5 / 4.2 / 5.4 / 7.0 us after launch start by start order on the
+// CU; now 3.7 / 4.4 / 5.0 / 5.6): render 15.3 -> 14.6 us, profiles/blk_tail.txt, DESIGN.md 4.2 item 8.
+#ifndef TG_BLK_PRIO
+#define TG_BLK_PRIO 1
 #endif
 template <int BW>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_render_blocks(RasterParams P, Stimulus S, const float* __restrict__ xform, int xform_soa, int n_envs,
@@ -949,6 +1025,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     if (pass == 0 && term_mask[env] == 0) return;
     const float* __restrict__ xf = pass == 0 ? term_xform : xform;
     uint8_t* __restrict__ img = pass == 0 ? term_out : out;
+#if TG_BLK_PRIO
+    __builtin_amdgcn_s_setprio(3);                             // (behind the exits of masked-out envs and of the idle terminal layer)
+#endif
     const float bmax_l = P.blockmax[reg * 64 + lane];          // lane l <-> block l: its largest undeformed depth
     // the blocks of this image that do NOT hold the untouched-sensor image now (drawn by the previous launch on it); the terminal image's
     // buffer has no such record: everything is rewritten there
@@ -1068,6 +1147,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         __syncthreads();
         reached = reach_all;
     }
+#if TG_BLK_PRIO
+    __builtin_amdgcn_s_setprio(0);
+#endif
     reached = __builtin_amdgcn_readfirstlane((unsigned)reached) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(reached >> 32)) << 32);
     stale = __builtin_amdgcn_readfirstlane((unsigned)stale) | ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(stale >> 32)) << 32);
     if (drawn_p && tid == 0) *drawn_p = reached;
@@ -1076,7 +1158,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     if (tid == 0 && blockIdx.y < 1024 && blockIdx.x == 0 && blockIdx.z == 0) {
         const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
         g_blk_nt[2 * blockIdx.y] = n | ((xcc & 15) << 8) | (((hw >> 8) & 15) << 12) | (((hw >> 13) & 7) << 16) | (((hw >> 12) & 1) << 20);
-        g_blk_nt[2 * blockIdx.y + 1] = __builtin_popcountll(reached);
+        unsigned pairs = 0u;                                  // the workgroup's (record, block) pairs: its drawing load
+#if TG_BLK_DEAL
+        for (int b = 0; b < 64; ++b) pairs += blk_cnt[b];
+#endif
+        g_blk_nt[2 * blockIdx.y + 1] = __builtin_popcountll(reached) | (int)(pairs << 8);
         if (blockIdx.y == 0) atomicAdd(&g_blk_pass[0], 1ull);
     }
 #endif
