@@ -52,6 +52,49 @@ def _check_images(x, name="x"):
         raise ValueError(f"{name} must be contiguous")
 
 
+def _unit(p):
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError(f"p must lie in [0, 1], got {p}")
+    return p
+
+
+def _chw(shape, channels_first):
+    """(C, H, W) of a sample of shape [C, H, W] or [H, W, C]."""
+    return tuple(shape) if channels_first else (shape[2], shape[0], shape[1])
+
+
+def _out_like(x, out):
+    if out is None:
+        return torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    _check_images(out, "out")
+    if out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device:
+        raise ValueError("out must be a float32 tensor of the input's shape on its device")
+    return out
+
+
+def _f32_tensor(t, name, shape, x):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError(f"{name} must be a float32 torch tensor")
+    if tuple(t.shape) != shape or t.device != x.device or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {list(shape)} tensor on the input's device")
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr() if t is not None else None)
+
+
+def _u64(v):
+    return C.c_uint64(int(v) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _translate_call(x, out, rows, B, Cn, H, W, channels_first, translate, p, seed, counter, params, pout, stream):
+    """The one place that lays out tg_random_translate_rows' arguments (random_translate, rows=None, and the device buffers' fused gathers)."""
+    capi.check(capi.lib().tg_random_translate_rows(
+        _ptr(x), _ptr(out), _DTYPES[x.dtype], int(bool(channels_first)), B, Cn, H, W, translate[0], translate[1], p, _u64(seed), _u64(counter),
+        _ptr(params), _ptr(pout), _ptr(rows), C.c_void_p(stream)))
+
+
 def random_translate(x, translate=(0.05, 0.05), p=0.5, seed=0, counter=0, params=None, channels_first=True, out=None, return_params=False):
     """One draw of the augmentation over the batch x ([B, C, H, W], or [B, H, W, C] with channels_first=False): a new float32 tensor (or `out`).
 
@@ -62,34 +105,13 @@ def random_translate(x, translate=(0.05, 0.05), p=0.5, seed=0, counter=0, params
     ax, ay = _pair(translate, "translate")
     if not (0.0 <= ax <= 1.0 and 0.0 <= ay <= 1.0):
         raise ValueError(f"translate must lie in [0, 1], got {(ax, ay)}")
-    p = float(p)
-    if not 0.0 <= p <= 1.0:
-        raise ValueError(f"p must lie in [0, 1], got {p}")
-    B = x.shape[0]
-    if channels_first:
-        Cn, H, W = x.shape[1], x.shape[2], x.shape[3]
-    else:
-        H, W, Cn = x.shape[1], x.shape[2], x.shape[3]
-    if out is None:
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    else:
-        _check_images(out, "out")
-        if out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device:
-            raise ValueError("out must be a float32 tensor of the input's shape on its device")
+    p, B, out = _unit(p), x.shape[0], _out_like(x, out)
     if params is not None:
-        if not isinstance(params, torch.Tensor) or params.dtype != torch.float32:
-            raise TypeError("params must be a float32 torch tensor")
-        if tuple(params.shape) != (B, 3) or params.device != x.device or not params.is_contiguous():
-            raise ValueError(f"params must be a contiguous [{B}, 3] tensor on the input's device")
+        _f32_tensor(params, "params", (B, 3), x)
     pout = torch.empty((B, 3), dtype=torch.float32, device=x.device) if return_params else None
-    L = capi.lib()
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        capi.check(L.tg_random_translate(
-            C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), _DTYPES[x.dtype], int(bool(channels_first)), B, Cn, H, W, ax, ay, p,
-            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(counter) & 0xFFFFFFFFFFFFFFFF),
-            C.c_void_p(params.data_ptr() if params is not None else None), C.c_void_p(pout.data_ptr() if pout is not None else None),
-            C.c_void_p(stream)))
+        _translate_call(x, out, None, B, *_chw(x.shape[1:], channels_first), channels_first, (ax, ay), p, seed, counter, params, pout, stream)
     return (out, pout) if return_params else out
 
 
@@ -97,7 +119,19 @@ def _draw_seed():
     return int(torch.randint(0, 2**62, (1,)).item())   # torch's default generator: torch.manual_seed makes the module's draws repeat
 
 
-class RandomTranslate(torch.nn.Module):
+class _FusedModule(torch.nn.Module):
+    """A module whose call is one `_fused` launch: draws (seed, counter), advances the counter, sets `_params`."""
+
+    def forward(self, x):
+        _check_images(x)
+        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            self._fused(x, out, None, x.shape[0], *_chw(x.shape[1:], self.channels_first), self.channels_first,
+                        torch.cuda.current_stream(x.device).cuda_stream)
+        return out
+
+
+class RandomTranslate(_FusedModule):
     """kornia's RandomAffine(degrees=0, translate, scale=(1, 1), p) on the device.  Call k (from 0) draws with (seed, k), so successive
     minibatches differ and a seeded run repeats.  After a call, `_params` holds kornia's names: `batch_prob` (bool [B]) and `translations`
     (float32 [B, 2], pixels)."""
@@ -107,19 +141,18 @@ class RandomTranslate(torch.nn.Module):
         self.translate = _pair(translate, "translate")
         if not all(0.0 <= t <= 1.0 for t in self.translate):
             raise ValueError(f"translate must lie in [0, 1], got {self.translate}")
-        self.p = float(p)
-        if not 0.0 <= self.p <= 1.0:
-            raise ValueError(f"p must lie in [0, 1], got {self.p}")
+        self.p = _unit(p)
         self.seed = _draw_seed() if seed is None else int(seed)
         self.channels_first = bool(channels_first)
         self.counter = 0
         self._params = None
 
-    def forward(self, x):
-        out, prm = random_translate(x, self.translate, self.p, self.seed, self.counter, channels_first=self.channels_first, return_params=True)
+    def _fused(self, src, out, rows, B, Cn, H, W, channels_first, stream):
+        """One call over a row-indexed source (rows=None: sample b reads sample b), as RandomWarp._fused."""
+        prm = torch.empty((B, 3), dtype=torch.float32, device=out.device)
+        _translate_call(src, out, rows, B, Cn, H, W, channels_first, self.translate, self.p, self.seed, self.counter, None, prm, stream)
         self.counter += 1
         self._params = {"batch_prob": prm[:, 0] != 0, "translations": prm[:, 1:3]}
-        return out
 
     def extra_repr(self):
         return f"translate={self.translate}, p={self.p}, seed={self.seed}, channels_first={self.channels_first}"
@@ -172,22 +205,13 @@ def _translate_pair(translate):
     return t
 
 
-def _f32_tensor(t, name, shape, x):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError(f"{name} must be a float32 torch tensor")
-    if tuple(t.shape) != shape or t.device != x.device or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous {list(shape)} tensor on the input's device")
-
-
 def _affine_call(x, out, rows, B, Cn, H, W, channels_first, ranges, p, seed, counter, params, pout, coeffs, cout, stream):
     """The one place that lays out tg_random_affine_rows' arguments (random_affine and the device buffers' fused gathers)."""
     (ax, ay), (d0, d1), (sc, has_y), sh = ranges
     s2, s3 = (sc[2], sc[3]) if has_y else (0.0, 0.0)
-    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)   # noqa: E731
     capi.check(capi.lib().tg_random_affine_rows(
-        ptr(x), ptr(out), _DTYPES[x.dtype], int(bool(channels_first)), B, Cn, H, W, ax, ay, d0, d1, sc[0], sc[1], s2, s3, sh[0], sh[1], sh[2], sh[3],
-        p, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(counter) & 0xFFFFFFFFFFFFFFFF), ptr(params), ptr(pout), ptr(coeffs),
-        ptr(cout), ptr(rows), C.c_void_p(stream)))
+        _ptr(x), _ptr(out), _DTYPES[x.dtype], int(bool(channels_first)), B, Cn, H, W, ax, ay, d0, d1, sc[0], sc[1], s2, s3, sh[0], sh[1], sh[2],
+        sh[3], p, _u64(seed), _u64(counter), _ptr(params), _ptr(pout), _ptr(coeffs), _ptr(cout), _ptr(rows), C.c_void_p(stream)))
 
 
 _centers = {}   # (H, W, device) -> float32 [1, 2] on the device: uploaded once, not per call
@@ -213,20 +237,7 @@ def random_affine(x, degrees=0.0, translate=None, scale=None, shear=None, p=0.5,
     parameters).  return_params=True returns (out, params, coeffs) with the [B, 8] and [B, 6] values that were used."""
     _check_images(x)
     ranges = (_translate_pair(translate), _degrees_range(degrees), _scale_range(scale), _shear_range(shear))
-    p = float(p)
-    if not 0.0 <= p <= 1.0:
-        raise ValueError(f"p must lie in [0, 1], got {p}")
-    B = x.shape[0]
-    if channels_first:
-        Cn, H, W = x.shape[1], x.shape[2], x.shape[3]
-    else:
-        H, W, Cn = x.shape[1], x.shape[2], x.shape[3]
-    if out is None:
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    else:
-        _check_images(out, "out")
-        if out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device:
-            raise ValueError("out must be a float32 tensor of the input's shape on its device")
+    p, B, out = _unit(p), x.shape[0], _out_like(x, out)
     if params is not None:
         _f32_tensor(params, "params", (B, 8), x)
     if coeffs is not None:
@@ -235,7 +246,8 @@ def random_affine(x, degrees=0.0, translate=None, scale=None, shear=None, p=0.5,
     cout = torch.empty((B, 6), dtype=torch.float32, device=x.device) if return_params else None
     with torch.cuda.device(x.device):
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        _affine_call(x, out, None, B, Cn, H, W, channels_first, ranges, p, seed, counter, params, pout, coeffs, cout, stream)
+        _affine_call(x, out, None, B, *_chw(x.shape[1:], channels_first), channels_first, ranges, p, seed, counter, params, pout, coeffs, cout,
+                     stream)
     return (out, pout, cout) if return_params else out
 
 
@@ -250,7 +262,7 @@ def _refuse_unbuilt(who, same_on_batch, align_corners, padding_mode, resample):
         raise NotImplementedError(f"{who}: resample={resample!r} (only 'bilinear' is built)")
 
 
-class RandomWarp(torch.nn.Module):
+class RandomWarp(_FusedModule):
     """kornia's RandomAffine(degrees, translate, scale, shear, p) on the device: rotation, scale and shear about the image centre, then the
     shift.  Call k (from 0) draws with (seed, k).  After a call, `_params` holds kornia's names: `batch_prob` (bool [B]),
     `translations` ([B, 2], pixels), `center` ([B, 2]), `scale` ([B, 2]), `angle` ([B], degrees), `sx`, `sy` ([B], degrees); `_coeffs` the
@@ -264,9 +276,7 @@ class RandomWarp(torch.nn.Module):
         self.translate = _translate_pair(translate)
         self.scale, self.scale_has_y = _scale_range(scale)
         self.shear = _shear_range(shear)
-        self.p = float(p)
-        if not 0.0 <= self.p <= 1.0:
-            raise ValueError(f"p must lie in [0, 1], got {self.p}")
+        self.p = _unit(p)
         self.seed = _draw_seed() if seed is None else int(seed)
         self.channels_first = bool(channels_first)
         self.counter = 0
@@ -283,15 +293,6 @@ class RandomWarp(torch.nn.Module):
         _affine_call(src, out, rows, B, Cn, H, W, channels_first, self._ranges(), self.p, self.seed, self.counter, None, prm, None, co, stream)
         self.counter += 1
         self._params, self._coeffs = _kornia_params(prm, H, W), co
-
-    def forward(self, x):
-        _check_images(x)
-        out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        B = x.shape[0]
-        Cn, H, W = (x.shape[1], x.shape[2], x.shape[3]) if self.channels_first else (x.shape[3], x.shape[1], x.shape[2])
-        with torch.cuda.device(x.device):
-            self._fused(x, out, None, B, Cn, H, W, self.channels_first, torch.cuda.current_stream(x.device).cuda_stream)
-        return out
 
     def extra_repr(self):
         scale = self.scale if self.scale_has_y else self.scale[:2]
@@ -323,15 +324,31 @@ def RandomAffine(degrees, translate=None, scale=None, shear=None, p=0.5, same_on
         raise NotImplementedError(f"RandomAffine: scale={scale!r} (only None or (1, 1) is built)")
     if shear is not None:
         raise NotImplementedError(f"RandomAffine: shear={shear!r} (only None is built)")
-    if same_on_batch:
-        raise NotImplementedError("RandomAffine: same_on_batch=True (only per-sample draws are built)")
-    if align_corners:
-        raise NotImplementedError("RandomAffine: align_corners=True (only False is built)")
-    if str(getattr(padding_mode, "name", padding_mode)).lower() != "zeros":
-        raise NotImplementedError(f"RandomAffine: padding_mode={padding_mode!r} (only 'zeros' is built)")
-    if str(getattr(resample, "name", resample)).lower() != "bilinear":
-        raise NotImplementedError(f"RandomAffine: resample={resample!r} (only 'bilinear' is built)")
+    _refuse_unbuilt("RandomAffine", same_on_batch, align_corners, padding_mode, resample)
     return RandomTranslate(translate=(0.0, 0.0) if translate is None else translate, p=p, seed=seed)
+
+
+def _unwrap_augment(augment):
+    """The RandomTranslate or RandomWarp of `augment`: the module itself or the one member of the params files' nn.Sequential."""
+    m = augment
+    if isinstance(m, torch.nn.Sequential):
+        if len(m) != 1:
+            raise TypeError(f"augment must hold exactly one RandomTranslate or RandomWarp, got an nn.Sequential of {len(m)} modules")
+        m = m[0]
+    if not isinstance(m, (RandomTranslate, RandomWarp)):
+        raise TypeError(f"augment must be a tactile_gym_amd.augment.RandomTranslate or RandomWarp (or the nn.Sequential of one), got "
+                        f"{type(m).__name__}: the fused gather needs the module's ranges, p, seed and counter, not a callable")
+    return m
+
+
+def _gather_images(module, src, out, rows, B, Cn, H, W, channels_first, stream):
+    """The device buffers' image key in one launch: out[b] = module(src[rows[b]]) as float32, B samples of [Cn, H, W] (or [H, W, Cn]) on
+    `stream`.  module: a RandomTranslate or a RandomWarp - one call of it: its counter advances, `_params` (and `_coeffs`) are set - or None
+    for the plain convert-gather (a translate that applies to no sample)."""
+    if module is None:
+        _translate_call(src, out, rows, B, Cn, H, W, channels_first, (0.0, 0.0), 0.0, 0, 0, None, None, stream)
+    else:
+        module._fused(src, out, rows, B, Cn, H, W, channels_first, stream)
 
 
 def augment_images(obs, module):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds libtactile_gym_hip.so (the product) and libtactile_gym_hip_test.so (device self-tests, loaded by tests/ only) for gfx950 (MI355X) in-tree.  hipcc cross-compiles without a GPU.
-#   tg_raster.hip, tg_scene.hip, tg_noise.hip, tg_augment.hip (the RAD translate augmentation, bit-exact specification: DESIGN.md 4.8) and tg_rollout.hip (the device rollout buffer, bit-exact GAE: DESIGN.md 4.9), tg_replay.hip (the device replay buffer: DESIGN.md 4.10), tg_affine.hip (the general affine augmentation, bit-exact warp: DESIGN.md 4.11), tg_vecnorm.hip (the device VecNormalize, bit-exact float64 statistics: DESIGN.md 4.12), tg_action_head.hip (the device action heads, one rounding per float32 operation: DESIGN.md 4.13) are compiled with -ffp-contract=off (bit-exact raster specification);
+#   tg_raster.hip, tg_scene.hip, tg_noise.hip, tg_augment.hip (the RAD translate augmentation, bit-exact specification: DESIGN.md 4.8; tg_augment_core.h holds what it shares with tg_affine.hip) and tg_rollout.hip (the device rollout buffer, bit-exact GAE: DESIGN.md 4.9), tg_replay.hip (the device replay buffer: DESIGN.md 4.10), tg_affine.hip (the general affine augmentation, bit-exact warp: DESIGN.md 4.11), tg_vecnorm.hip (the device VecNormalize, bit-exact float64 statistics: DESIGN.md 4.12), tg_action_head.hip (the device action heads, one rounding per float32 operation: DESIGN.md 4.13) are compiled with -ffp-contract=off (bit-exact raster specification);
 #   tg_api.hip (configuration, creation, step / reset launches; + tg_api_state.hip, tg_api_ops.hip: the rest of the C ABI, sharing tg_ctx.hpp), tg_contact_wave.hip (wave-per-env contact solver) and tg_exchange.hip (multi-GPU payloads, integer only), tg_stack.hip (the frame stack, byte moves only) with the default contraction (FMA); tg_narrow_test.hip (GJK / EPA self-test) switches contraction off by pragma; tg_stack_test.hip (the test entry of the frame-stack launchers, no kernel of its own) needs no flag; tg_fused.hip (step + render in one launch) keeps FMA for the physics and
 #   takes the raster from tg_raster_dev.hpp, whose pragma switches contraction off for everything after it.
 set -euo pipefail

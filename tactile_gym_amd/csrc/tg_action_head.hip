@@ -13,7 +13,7 @@
 
 #include "../../include/tactile_gym_hip.h"
 #include "tg_exchange.h"   // report_error
-#include "tg_kernels.hpp"  // mix64, kGolden: tg_sample_actions' counter-based generator
+#include "tg_kernels.hpp"  // counter_draw: tg_sample_actions' counter-based generator
 
 namespace tg {
 
@@ -40,7 +40,7 @@ struct HeadArgs {
 
 // The 24 random bits of element e of draw `counter`: tg_sample_actions' integers.
 __device__ __forceinline__ uint32_t head_bits24(uint64_t seed, uint64_t counter, uint64_t e) {
-    return (uint32_t)(mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (e + 1)) >> 40);
+    return (uint32_t)(counter_draw(seed, counter, e) >> 40);
 }
 
 // Box-Muller on elements 2 e and 2 e + 1, all in double: u1 in (0, 1], u2 in [0, 1); |result| <= sqrt(-2 ln 2^-24) = 5.768

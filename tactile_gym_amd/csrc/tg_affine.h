@@ -1,14 +1,12 @@
 // tg_affine.h - launch interface of the general affine augmentation (tg_affine.hip: k_random_affine; tg_random_affine).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "tg_augment_core.h"
 
 namespace tg {
 
 // One call of kornia's RandomAffine(degrees, translate, scale, shear, p) - its defaults otherwise: bilinear, zero padding, align_corners=False,
 // per-sample draws - over a [B][C][H][W] (channels first) or [B][H][W][C] (channels last) batch of uint8 or float32 images, out of place,
-// float32 output in the same layout.  A sample is P planes of H rows of R elements: channels first P = C, R = W, a horizontal
-// tap step of S = 1 element; channels last P = 1, R = W * C, S = C.
+// float32 output in the same layout (planes, rows and tap step: PlaneGeom).
 struct AffineArgs {
     const void* in = nullptr;
     float* out = nullptr;
@@ -26,11 +24,10 @@ struct AffineArgs {
     float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f;   // shear, degrees
     uint64_t seed = 0, counter = 0;
 };
-enum { kAffineU8 = 0, kAffineF32 = 1 };
-// 0, -1 for arguments the kernel is not built for, -2 when the launch failed.  Enqueued on `stream`; nothing is allocated or synchronised.
+// in_dtype: TG_AUGMENT_*.  0, -1 for arguments the kernel is not built for, -2 when the launch failed.  Enqueued on `stream`; nothing is
+// allocated or synchronised.
 int launch_random_affine(const AffineArgs& a, int in_dtype, int channels_first, hipStream_t stream);
 
-constexpr int kAfChunk = 4096;          // output elements per workgroup: 4 float4 per lane
 constexpr int kAfHeader = 32;           // bytes of LDS in front of the plane: the sample's coefficients, written by one lane
 constexpr int kAfMaxPlane = 32 << 10;   // bytes of a plane (as stored) that the staged path keeps in LDS: five workgroups per CU at the limit
 
@@ -41,24 +38,19 @@ constexpr int kAfMaxPlane = 32 << 10;   // bytes of a plane (as stored) that the
 //   path 1, gather: the taps are read from global memory, the output is stored as float4.  Needs planes that are a multiple of 4 floats and a
 //           16-byte aligned output.
 //   path 0, per element: anything else.
-// in_vec: samples that are not applied are copied with 16-byte loads (else element loads).  One workgroup per (sample, plane, chunk); a launch
-// holds at most 2^23 of them: spl samples, 0 when one sample alone has more.
-struct AffinePlan {
-    int path, in_vec, nchunk, lds_bytes;
-    int64_t per_sample, spl;
+// in_vec: samples that are not applied are copied with 16-byte loads (else element loads).  The workgroups and launches: ChunkPlan.
+struct AffinePlan : ChunkPlan {
+    int path, in_vec, lds_bytes;
 };
 inline AffinePlan affine_plan(int elem_bytes, bool channels_first, int C, int H, int W, uintptr_t in, uintptr_t out) {
-    const int P = channels_first ? C : 1;
-    const int64_t HR = (int64_t)H * (channels_first ? W : (int64_t)W * C);
+    const PlaneGeom g = plane_geom(channels_first, C, H, W);
+    const int64_t HR = g.HR;   // 64 bits: HR * elem_bytes
     const int V = 16 / elem_bytes;
-    AffinePlan p;
-    p.nchunk = (int)((HR + kAfChunk - 1) / kAfChunk);
+    AffinePlan p{chunk_plan(g)};
     const bool out_vec = HR % 4 == 0 && !(out & 15);
     p.in_vec = out_vec && HR % V == 0 && !(in & 15);
     p.path = p.in_vec && HR * elem_bytes <= kAfMaxPlane ? 2 : out_vec ? 1 : 0;
     p.lds_bytes = kAfHeader + (p.path == 2 ? (int)(HR * elem_bytes) : 0);
-    p.per_sample = (int64_t)P * p.nchunk;
-    p.spl = ((int64_t)1 << 23) / p.per_sample;
     return p;
 }
 

@@ -22,20 +22,9 @@
 // the staged path (affine_plan: path 2) copies the source ROWS that the chunk's corners reach - sy is monotone in j and in i also after
 // rounding, so the corners bound it - into LDS as they are stored, with aligned 16-byte loads, and reads the taps from there; the gather path
 // (1) reads them from global memory; the per-element path (0) also stores element by element.  All three run the same arithmetic (affine_px).
-#include "tg_affine.h"
-
-#include "../../include/tactile_gym_hip.h"
-#include "tg_exchange.h"   // report_error
-#include "tg_kernels.hpp"  // mix64, kGolden: tg_sample_actions' counter-based generator
+#include "tg_affine.h"   // + tg_augment_core.h: what k_random_translate shares (the draw, store16, blend, the chunk prologue, the convert-copy)
 
 namespace tg {
-
-constexpr int kAfThreads = 256;
-
-__device__ __forceinline__ float af_draw_u24(uint64_t seed, uint64_t counter, uint64_t i) {
-    const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (i + 1));
-    return (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-}
 
 // Stage (a): prm[8] of sample b.
 __device__ __forceinline__ void af_params(const AffineArgs& a, int64_t b, float prm[8]) {
@@ -48,7 +37,7 @@ __device__ __forceinline__ void af_params(const AffineArgs& a, int64_t b, float 
     const uint64_t i = 8 * (uint64_t)b;
     float u[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) u[k] = af_draw_u24(a.seed, a.counter, i + k);
+    for (int k = 0; k < 8; ++k) u[k] = draw_u24(a.seed, a.counter, i + k);
     prm[0] = u[0] < a.p ? 1.f : 0.f;
     prm[1] = a.ax_w * (2.f * u[1] - 1.f);
     prm[2] = a.ay_h * (2.f * u[2] - 1.f);
@@ -100,9 +89,7 @@ __device__ __forceinline__ float affine_px(const TSRC* __restrict__ src, const A
     const int t = y0 * R + x0 * S + cc;
     const float va = r0 && c0 ? (float)src[t] : 0.f, vb = r0 && c1 ? (float)src[t + S] : 0.f;
     const float vc = r1 && c0 ? (float)src[t + R] : 0.f, vd = r1 && c1 ? (float)src[t + R + S] : 0.f;
-    const float h0 = (1.f - fx) * va + fx * vb;
-    const float h1 = (1.f - fx) * vc + fx * vd;
-    return (1.f - fy) * h0 + fy * h1;
+    return blend(va, vb, vc, vd, fx, fy);
 }
 
 // Four consecutive elements from f (a multiple of 4; they may run on into the next row) as one float4 store.
@@ -124,29 +111,16 @@ __device__ __forceinline__ void affine_quad(const TSRC* __restrict__ src, float*
     *reinterpret_cast<float4*>(out + f) = make_float4(o[0], o[1], o[2], o[3]);
 }
 
-// 16 bytes of input converted to float32 at d: 4 floats, or 16 from uint8.
-__device__ __forceinline__ void af_store16(float* d, const float* p) { *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void af_store16(float* d, const uint8_t* p) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<float4*>(d + 4 * q) = make_float4((float)(w[q] & 0xffu), (float)((w[q] >> 8) & 0xffu), (float)((w[q] >> 16) & 0xffu),
-                                                            (float)(w[q] >> 24));
-}
-
 template <typename TIN, bool CF>
-__global__ __launch_bounds__(kAfThreads) void k_random_affine(AffineArgs a, int64_t b0, int nchunk, int path, int in_vec) {
+__global__ __launch_bounds__(kAugThreads) void k_random_affine(AffineArgs a, int64_t b0, int nchunk, int path, int in_vec) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     float* const head = reinterpret_cast<float*>(lds_raw);
     TIN* const plane = reinterpret_cast<TIN*>(lds_raw + kAfHeader);
-    const int P = CF ? a.C : 1, R = CF ? a.W : a.W * a.C, S = CF ? 1 : a.C, H = a.H, W = a.W, C = a.C;
-    const int HR = H * R;
-    const int per_sample = P * nchunk;
-    const int bl = (int)(blockIdx.x / (unsigned)per_sample), rem = (int)blockIdx.x - bl * per_sample;
-    const int64_t b = b0 + bl;
-    const int pl = rem / nchunk, f0 = (rem - pl * nchunk) * kAfChunk;
-    const int fend = HR - f0 < kAfChunk ? HR : f0 + kAfChunk;
+    const PlaneGeom g = plane_geom(CF, a.C, a.H, a.W);
+    const int R = g.R, S = g.S, H = a.H, W = a.W, C = a.C;
+    int64_t b;
+    int rem, pl, f0, fend;
+    chunk_of(g, nchunk, b0, b, rem, pl, f0, fend);
     const int tid = threadIdx.x;
 
     if (tid == 0) {   // one lane: stages (a) and (b); the sample's first workgroup reports them
@@ -181,36 +155,16 @@ __global__ __launch_bounds__(kAfThreads) void k_random_affine(AffineArgs a, int6
     k.a00 = af_uniform(head[0]), k.a01 = af_uniform(head[1]), k.a02 = af_uniform(head[2]);
     k.a10 = af_uniform(head[3]), k.a11 = af_uniform(head[4]), k.a12 = af_uniform(head[5]);
 
-    const int64_t bsrc = a.rows ? a.rows[b] : b;   // row-indexed source: only the workgroup's source base moves
-    const TIN* __restrict__ in = reinterpret_cast<const TIN*>(a.in) + (bsrc * P + pl) * (int64_t)HR;
-    float* __restrict__ out = a.out + (b * P + pl) * (int64_t)HR;
+    const TIN* __restrict__ in = plane_of(reinterpret_cast<const TIN*>(a.in), a.rows, b, pl, g);
+    float* __restrict__ out = plane_of(a.out, nullptr, b, pl, g);
 
-    if (!apply) {   // convert-copy
-        if (in_vec) {
-            if (sizeof(TIN) == 1) {
-                const int f = f0 + 16 * tid;
-                if (f < fend) af_store16(out + f, in + f);
-            } else {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int f = f0 + 4 * tid + 1024 * q;
-                    if (f < fend) af_store16(out + f, in + f);
-                }
-            }
-        } else if (path) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int f = f0 + 4 * tid + 1024 * q;
-                if (f < fend) *reinterpret_cast<float4*>(out + f) = make_float4((float)in[f], (float)in[f + 1], (float)in[f + 2], (float)in[f + 3]);
-            }
-        } else {
-            for (int f = f0 + tid; f < fend; f += kAfThreads) out[f] = (float)in[f];
-        }
+    if (!apply) {
+        convert_copy(in, out, f0, fend, tid, in_vec, path);   // paths 1 and 2 store float4: the output is aligned
         return;
     }
 
     if (path == 0) {   // per element
-        for (int f = f0 + tid; f < fend; f += kAfThreads) {
+        for (int f = f0 + tid; f < fend; f += kAugThreads) {
             const int y = f / R, e = f - y * R;
             const int j = CF ? e : e / C, cc = CF ? 0 : e - j * C;
             out[f] = affine_px(in, k, j, y, cc, H, W, R, S);
@@ -241,7 +195,7 @@ __global__ __launch_bounds__(kAfThreads) void k_random_affine(AffineArgs a, int6
         }
         constexpr int V = 16 / (int)sizeof(TIN);
         const int a_lo = ylo * R / V * V, a_hi = ((yhi + 1) * R + V - 1) / V * V;   // HR is a multiple of V: a_hi <= HR
-        for (int v = a_lo + V * tid; v < a_hi; v += V * kAfThreads)
+        for (int v = a_lo + V * tid; v < a_hi; v += V * kAugThreads)
             *reinterpret_cast<uint4*>(plane + v) = *reinterpret_cast<const uint4*>(in + v);
     }
     __syncthreads();
@@ -255,21 +209,14 @@ __global__ __launch_bounds__(kAfThreads) void k_random_affine(AffineArgs a, int6
 template <typename TIN, bool CF>
 static int launch_typed(const AffineArgs& a, hipStream_t stream) {
     const AffinePlan pl = affine_plan((int)sizeof(TIN), CF, a.C, a.H, a.W, (uintptr_t)a.in, (uintptr_t)a.out);
-    if (pl.spl < 1) return -1;
-    for (int64_t b0 = 0; b0 < a.B; b0 += pl.spl) {
-        const int64_t nb = a.B - b0 < pl.spl ? a.B - b0 : pl.spl;
-        hipLaunchKernelGGL((k_random_affine<TIN, CF>), dim3((unsigned)(nb * pl.per_sample)), dim3(kAfThreads), (size_t)pl.lds_bytes, stream, a, b0,
-                           pl.nchunk, pl.path, pl.in_vec);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_chunks(a.B, pl, [&](int64_t b0, dim3 grid) {
+        hipLaunchKernelGGL((k_random_affine<TIN, CF>), grid, dim3(kAugThreads), (size_t)pl.lds_bytes, stream, a, b0, pl.nchunk, pl.path, pl.in_vec);
+    });
 }
 
 int launch_random_affine(const AffineArgs& a, int in_dtype, int channels_first, hipStream_t stream) {
-    if (a.B <= 0) return a.B == 0 ? 0 : -1;
-    if (!a.in || !a.out || a.C < 1 || a.H < 2 || a.W < 2 || (int64_t)a.C * a.H * a.W > (1 << 30)) return -1;
-    if (in_dtype == kAffineU8) return channels_first ? launch_typed<uint8_t, true>(a, stream) : launch_typed<uint8_t, false>(a, stream);
-    if (in_dtype == kAffineF32) return channels_first ? launch_typed<float, true>(a, stream) : launch_typed<float, false>(a, stream);
-    return -1;
+    return dispatch_images(a.in, a.out, in_dtype, channels_first, a.B, a.C, a.H, a.W,
+                           [&](auto t, auto cf) { return launch_typed<decltype(t), decltype(cf)::value>(a, stream); });
 }
 
 }  // namespace tg
@@ -282,44 +229,22 @@ extern "C" int tg_random_affine_rows(const void* in_dev, void* out_dev, int32_t 
                                      float* params_out_dev, const float* coeffs_in_dev, float* coeffs_out_dev, const int64_t* rows_dev,
                                      void* hip_stream) {
     using tg::report_error;
-    if (in_dtype != TG_AUGMENT_UINT8 && in_dtype != TG_AUGMENT_FLOAT32) return report_error(-1, "tg_random_affine: unknown input dtype");
-    if (B < 0 || C < 1 || H < 2 || W < 2) return report_error(-1, "tg_random_affine: need B >= 0, C >= 1, H >= 2, W >= 2");
-    if ((int64_t)C * H * W > (1 << 30)) return report_error(-1, "tg_random_affine: more than 2^30 elements per image");
-    if (!(ax >= 0.0 && ax <= 1.0 && ay >= 0.0 && ay <= 1.0)) return report_error(-1, "tg_random_affine: translate must lie in [0, 1]");
+    if (const int bad = tg::check_image_call("tg_random_affine", in_dev, out_dev, in_dtype, B, C, H, W, ax, ay, p, rows_dev != nullptr)) return bad;
     if (!af_range(d0, d1)) return report_error(-1, "tg_random_affine: degrees must be a finite range d0 <= d1");
     if (!af_range(s0, s1) || !(s0 > 0.f)) return report_error(-1, "tg_random_affine: scale must be a finite range 0 < s0 <= s1");
     const bool scale4 = !(s2 == 0.f && s3 == 0.f);
     if (scale4 && (!af_range(s2, s3) || !(s2 > 0.f)))
         return report_error(-1, "tg_random_affine: the scale of y must be a finite range 0 < s2 <= s3, or s2 = s3 = 0 for scale_y = scale_x");
     if (!af_range(h0, h1) || !af_range(h2, h3)) return report_error(-1, "tg_random_affine: shear must be finite ranges h0 <= h1, h2 <= h3");
-    if (!(p >= 0.f && p <= 1.f)) return report_error(-1, "tg_random_affine: p must lie in [0, 1]");
     if (B == 0) return 0;
-    if (!in_dev || !out_dev) return report_error(-1, "tg_random_affine: NULL image pointer");
-    const uint64_t n = (uint64_t)B * C * H * W, ib = (uint64_t)(uintptr_t)in_dev, ob = (uint64_t)(uintptr_t)out_dev;
-    const uint64_t in_bytes = n * (in_dtype == TG_AUGMENT_UINT8 ? 1 : 4), out_bytes = n * 4;
-    if (!rows_dev && ib < ob + out_bytes && ob < ib + in_bytes) return report_error(-1, "tg_random_affine: the output overlaps the input (out of place only)");
-    tg::AffineArgs a;
-    a.in = in_dev;
-    a.out = (float*)out_dev;
-    a.params_in = params_in_dev;
-    a.params_out = params_out_dev;
+    tg::AffineArgs a = tg::image_args<tg::AffineArgs>(in_dev, out_dev, params_in_dev, params_out_dev, rows_dev, B, C, H, W, ax, ay, p, seed, counter);
     a.coeffs_in = coeffs_in_dev;
     a.coeffs_out = coeffs_out_dev;
-    a.rows = rows_dev;
-    a.B = B;
-    a.C = C;
-    a.H = H;
-    a.W = W;
-    a.ax_w = (float)(ax * W);
-    a.ay_h = (float)(ay * H);
-    a.p = p;
     a.d0 = d0, a.d1 = d1;
     a.s0 = s0, a.s1 = s1, a.s2 = s2, a.s3 = s3;
     a.scale4 = scale4;
     a.h0 = h0, a.h1 = h1, a.h2 = h2, a.h3 = h3;
-    a.seed = seed;
-    a.counter = counter;
-    const int rc = tg::launch_random_affine(a, in_dtype == TG_AUGMENT_UINT8 ? tg::kAffineU8 : tg::kAffineF32, channels_first, (hipStream_t)hip_stream);
+    const int rc = tg::launch_random_affine(a, in_dtype, channels_first, (hipStream_t)hip_stream);
     if (rc == -2) return report_error(-2, "tg_random_affine: the kernel launch failed");
     if (rc) return report_error(rc, "tg_random_affine: arguments the kernel is not built for");
     return 0;

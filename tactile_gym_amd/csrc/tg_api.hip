@@ -411,7 +411,7 @@ __global__ void k_sample_actions(int total, uint64_t seed, uint64_t counter, flo
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     TG_TL(tl, 0);
     if (i >= total) return;
-    const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (uint64_t)(i + 1));
+    const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (uint64_t)(i + 1));   // counter_draw(seed, counter, i)
     const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
     out[i] = lo + (hi - lo) * u;
 }
@@ -424,7 +424,7 @@ __global__ void k_sample_actions_ctr(int total, unsigned long long* __restrict__
     TG_TL(tl, 0);
     const uint64_t counter = ctr[0] + 1, seed = ctr[1];
     if (i < total) {
-        const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (uint64_t)(i + 1));
+        const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (uint64_t)(i + 1));   // counter_draw(seed, counter, i)
         const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
         out[i] = lo + (hi - lo) * u;
     }

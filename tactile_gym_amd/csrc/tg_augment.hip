@@ -16,26 +16,15 @@
 // convert-copy.  Shapes whose planes are not 16-byte multiples, or rows too long for the LDS span, take a per-element path with the same
 // arithmetic.  tg_random_translate_rows gives the source a row table (sample b reads source sample rows[b]: the minibatch gather of the device
 // rollout buffer): the workgroup's source base is the only thing that changes.
-#include "tg_augment.h"
-
-#include "../../include/tactile_gym_hip.h"
-#include "tg_exchange.h"   // report_error
-#include "tg_kernels.hpp"  // mix64, kGolden: tg_sample_actions' counter-based generator
+#include "tg_augment.h"   // + tg_augment_core.h: what k_random_affine shares (the draw, store16, blend, the chunk prologue, the convert-copy)
 
 namespace tg {
-
-constexpr int kTrThreads = 256;
 
 struct TrSample {
     bool apply;
     int ox, oy;
     float fx, fy;
 };
-
-__device__ __forceinline__ float draw_u24(uint64_t seed, uint64_t counter, uint64_t i) {
-    const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (i + 1));
-    return (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
-}
 
 // o = floor(-s), f = (float)(-s - o) for s = t n / (n - 1).  -s is clamped to [-(n + 2), n + 2] first (NaN goes to -(n + 2)): beyond that
 // every tap is outside the image whatever f is.
@@ -87,63 +76,29 @@ __device__ __forceinline__ void window(const float* lds, int local, int r, int l
     w1 = *reinterpret_cast<const float4*>(lds + al + 4);
 }
 
-// One aligned 16-byte load of input converted to float32 at d: 4 floats, or 16 from uint8.  (4-byte uint8 loads, which would keep every lane's
-// float4 next to its neighbour's, measured 10 % slower.)
-__device__ __forceinline__ void store16(float* d, const float* p) { *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void store16(float* d, const uint8_t* p) {
-    const uint4 u = *reinterpret_cast<const uint4*>(p);
-    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-        *reinterpret_cast<float4*>(d + 4 * q) = make_float4((float)(w[q] & 0xffu), (float)((w[q] >> 8) & 0xffu), (float)((w[q] >> 16) & 0xffu),
-                                                            (float)(w[q] >> 24));
-}
-
-__device__ __forceinline__ float blend(float a, float b, float c, float d, float fx, float fy) {
-    const float h0 = (1.f - fx) * a + fx * b;
-    const float h1 = (1.f - fx) * c + fx * d;
-    return (1.f - fy) * h0 + fy * h1;
-}
-
 // vec: the plane is a multiple of 16 bytes of input and of 4 floats of output, both pointers are 16-byte aligned and R + S <= kTrMaxRow.
 template <typename TIN, bool CF>
-__global__ __launch_bounds__(kTrThreads) void k_random_translate(TranslateArgs a, int64_t b0, int nchunk, int vec, int lds_floats) {
+__global__ __launch_bounds__(kAugThreads) void k_random_translate(TranslateArgs a, int64_t b0, int nchunk, int vec, int lds_floats) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int P = CF ? a.C : 1, R = CF ? a.W : a.W * a.C, S = CF ? 1 : a.C, H = a.H;
-    const int HR = H * R;
-    const int per_sample = P * nchunk;
-    const int bl = (int)(blockIdx.x / (unsigned)per_sample), rem = (int)blockIdx.x - bl * per_sample;
-    const int64_t b = b0 + bl;
-    const int pl = rem / nchunk, f0 = (rem - pl * nchunk) * kTrChunk;
-    const int fend = HR - f0 < kTrChunk ? HR : f0 + kTrChunk;
+    const PlaneGeom g = plane_geom(CF, a.C, a.H, a.W);
+    const int R = g.R, S = CF ? 1 : g.S, HR = g.HR, H = a.H;   // CF: S as the literal 1 (the same code as before plane_geom)
+    int64_t b;
+    int rem, pl, f0, fend;
+    chunk_of(g, nchunk, b0, b, rem, pl, f0, fend);
     const TrSample sp = sample_params(a, b, rem == 0);
-    const int64_t bsrc = a.rows ? a.rows[b] : b;   // row-indexed source: only the workgroup's source base moves
-    const TIN* __restrict__ in = reinterpret_cast<const TIN*>(a.in) + (bsrc * P + pl) * (int64_t)HR;
-    float* __restrict__ out = a.out + (b * P + pl) * (int64_t)HR;
+    const TIN* __restrict__ in = plane_of(reinterpret_cast<const TIN*>(a.in), a.rows, b, pl, g);
+    float* __restrict__ out = plane_of(a.out, nullptr, b, pl, g);
     const int tid = threadIdx.x;
 
-    if (!sp.apply) {   // convert-copy
-        if (vec) {
-            if (sizeof(TIN) == 1) {
-                const int f = f0 + 16 * tid;
-                if (f < fend) store16(out + f, in + f);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int f = f0 + 4 * tid + 1024 * k;
-                    if (f < fend) store16(out + f, in + f);
-                }
-            }
-        } else {
-            for (int f = f0 + tid; f < fend; f += kTrThreads) out[f] = (float)in[f];
-        }
+    if (!sp.apply) {
+        convert_copy(in, out, f0, fend, tid, vec, vec);
         return;
     }
 
     const int dx = sp.ox * S, oy = sp.oy;
     const float fx = sp.fx, fy = sp.fy;
     if (!vec) {   // per element, taps read from global memory
-        for (int f = f0 + tid; f < fend; f += kTrThreads) {
+        for (int f = f0 + tid; f < fend; f += kAugThreads) {
             const int y = f / R, j = f - y * R;
             const int ya = y + oy, xa = j + dx;
             const bool r0 = ya >= 0 && ya < H, r1 = ya + 1 >= 0 && ya + 1 < H;
@@ -164,7 +119,7 @@ __global__ __launch_bounds__(kTrThreads) void k_random_translate(TranslateArgs a
     const int a_lo = lo / V * V;
     if (lo < hi) {
         const int a_hi = (hi + V - 1) / V * V;
-        for (int v = a_lo + V * tid; v < a_hi; v += V * kTrThreads) store16(lds + (v - a_lo + 4), in + v);
+        for (int v = a_lo + V * tid; v < a_hi; v += V * kAugThreads) store16(lds + (v - a_lo + 4), in + v);
     }
     __syncthreads();
 
@@ -202,23 +157,15 @@ __global__ __launch_bounds__(kTrThreads) void k_random_translate(TranslateArgs a
 template <typename TIN, bool CF>
 static int launch_typed(const TranslateArgs& a, hipStream_t stream) {
     const TranslatePlan pl = translate_plan((int)sizeof(TIN), CF, a.C, a.H, a.W, (uintptr_t)a.in, (uintptr_t)a.out);
-    if (pl.spl < 1) return -1;
-    for (int64_t b0 = 0; b0 < a.B; b0 += pl.spl) {
-        const int64_t nb = a.B - b0 < pl.spl ? a.B - b0 : pl.spl;
-        hipLaunchKernelGGL((k_random_translate<TIN, CF>), dim3((unsigned)(nb * pl.per_sample)), dim3(kTrThreads), (size_t)pl.lds_floats * 4, stream,
-                           a, b0, pl.nchunk, pl.vec, pl.lds_floats);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -2;
+    return launch_chunks(a.B, pl, [&](int64_t b0, dim3 grid) {
+        hipLaunchKernelGGL((k_random_translate<TIN, CF>), grid, dim3(kAugThreads), (size_t)pl.lds_floats * 4, stream, a, b0, pl.nchunk, pl.vec,
+                           pl.lds_floats);
+    });
 }
 
 int launch_random_translate(const TranslateArgs& a, int in_dtype, int channels_first, hipStream_t stream) {
-    if (a.B <= 0) return a.B == 0 ? 0 : -1;
-    if (!a.in || !a.out || a.C < 1 || a.H < 2 || a.W < 2 || (int64_t)a.C * a.H * a.W > (1 << 30)) return -1;
-    if (in_dtype == kTranslateU8)
-        return channels_first ? launch_typed<uint8_t, true>(a, stream) : launch_typed<uint8_t, false>(a, stream);
-    if (in_dtype == kTranslateF32)
-        return channels_first ? launch_typed<float, true>(a, stream) : launch_typed<float, false>(a, stream);
-    return -1;
+    return dispatch_images(a.in, a.out, in_dtype, channels_first, a.B, a.C, a.H, a.W,
+                           [&](auto t, auto cf) { return launch_typed<decltype(t), decltype(cf)::value>(a, stream); });
 }
 
 }  // namespace tg
@@ -227,33 +174,11 @@ extern "C" int tg_random_translate_rows(const void* in_dev, void* out_dev, int32
                                         int32_t W, double ax, double ay, float p, uint64_t seed, uint64_t counter, const float* params_in_dev,
                                         float* params_out_dev, const int64_t* rows_dev, void* hip_stream) {
     using tg::report_error;
-    if (in_dtype != TG_AUGMENT_UINT8 && in_dtype != TG_AUGMENT_FLOAT32) return report_error(-1, "tg_random_translate: unknown input dtype");
-    if (B < 0 || C < 1 || H < 2 || W < 2) return report_error(-1, "tg_random_translate: need B >= 0, C >= 1, H >= 2, W >= 2");
-    if ((int64_t)C * H * W > (1 << 30)) return report_error(-1, "tg_random_translate: more than 2^30 elements per image");
-    if (!(ax >= 0.0 && ax <= 1.0 && ay >= 0.0 && ay <= 1.0)) return report_error(-1, "tg_random_translate: translate must lie in [0, 1]");
-    if (!(p >= 0.f && p <= 1.f)) return report_error(-1, "tg_random_translate: p must lie in [0, 1]");
+    if (const int bad = tg::check_image_call("tg_random_translate", in_dev, out_dev, in_dtype, B, C, H, W, ax, ay, p, rows_dev != nullptr)) return bad;
     if (B == 0) return 0;
-    if (!in_dev || !out_dev) return report_error(-1, "tg_random_translate: NULL image pointer");
-    const uint64_t n = (uint64_t)B * C * H * W, ib = (uint64_t)(uintptr_t)in_dev, ob = (uint64_t)(uintptr_t)out_dev;
-    const uint64_t in_bytes = n * (in_dtype == TG_AUGMENT_UINT8 ? 1 : 4), out_bytes = n * 4;
-    if (!rows_dev && ib < ob + out_bytes && ob < ib + in_bytes) return report_error(-1, "tg_random_translate: the output overlaps the input (out of place only)");
-    tg::TranslateArgs a;
-    a.in = in_dev;
-    a.out = (float*)out_dev;
-    a.params_in = params_in_dev;
-    a.params_out = params_out_dev;
-    a.rows = rows_dev;
-    a.B = B;
-    a.C = C;
-    a.H = H;
-    a.W = W;
-    a.ax_w = (float)(ax * W);
-    a.ay_h = (float)(ay * H);
-    a.p = p;
-    a.seed = seed;
-    a.counter = counter;
-    const int rc = tg::launch_random_translate(a, in_dtype == TG_AUGMENT_UINT8 ? tg::kTranslateU8 : tg::kTranslateF32, channels_first,
-                                               (hipStream_t)hip_stream);
+    const tg::TranslateArgs a = tg::image_args<tg::TranslateArgs>(in_dev, out_dev, params_in_dev, params_out_dev, rows_dev, B, C, H, W, ax, ay, p,
+                                                                  seed, counter);
+    const int rc = tg::launch_random_translate(a, in_dtype, channels_first, (hipStream_t)hip_stream);
     if (rc == -2) return report_error(-2, "tg_random_translate: the kernel launch failed");
     if (rc) return report_error(rc, "tg_random_translate: arguments the kernel is not built for");
     return 0;

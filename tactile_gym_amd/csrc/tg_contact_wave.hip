@@ -1514,7 +1514,7 @@ __global__ __launch_bounds__(64) void k_step_body_wave(const DevRobot<T>* __rest
         for (int j = 0; j < 6; ++j) {
             if (j < c.act_dim) {
                 const int i = env * c.act_dim + j;
-                const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (uint64_t)(i + 1));
+                const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (uint64_t)(i + 1));   // counter_draw(seed, counter, i)
                 const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
                 abuf[j] = lo + (hi - lo) * u;
                 if (w0) st.act_out[i] = abuf[j];

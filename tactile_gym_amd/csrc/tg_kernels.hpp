@@ -131,6 +131,12 @@ __host__ __device__ inline uint64_t mix64(uint64_t z) {
     return z ^ (z >> 31);
 }
 constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+// tg_sample_actions' counter-based generator: 64 bits of splitmix64 over (seed, counter, element) - element i of draw `counter`; a uniform takes
+// its 24 high bits, u = (z >> 40) 2^-24 in [0, 1).  Every device draw that promises "tg_sample_actions' generator" is this function (the
+// augmentations, the action heads; tg_replay.hip computes the inner mix64 on the host); the step path writes it out where it stands.
+__host__ __device__ inline uint64_t counter_draw(uint64_t seed, uint64_t counter, uint64_t element) {
+    return mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (element + 1));
+}
 __device__ inline double rng_uniform(uint64_t& s, double lo, double hi) {
 #pragma clang fp contract(off)   // lo + (hi - lo) * u must round like the host's two-step evaluation (no FMA)
     s += kGolden;
@@ -725,7 +731,7 @@ __device__ __forceinline__ bool step_env(const DevRobot<T>& m, const EnvConst<T>
         for (int j = 0; j < 6; ++j) {
             if (j < c.act_dim) {
                 const int i = env * c.act_dim + j;
-                const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (uint64_t)(i + 1));
+                const uint64_t z = mix64(mix64(seed + kGolden * (counter + 1)) + kGolden * (uint64_t)(i + 1));   // counter_draw(seed, counter, i)
                 const float u = (float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f);
                 abuf[j] = lo + (hi - lo) * u;
                 st.act_out[i] = abuf[j];

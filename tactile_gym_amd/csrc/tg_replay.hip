@@ -78,7 +78,8 @@ __global__ __launch_bounds__(kRoThreads) void k_replay_add(RpTable t, const uint
     move_units<u32x4>(unit, s, d, on);   // the register form: no LDS
 }
 
-// Sample b: h = mix64(head + G (b + 1)), head = mix64(seed + G (counter + 1)); slot (first + ((h >> 32) M >> 32)) % T, env (h & 0xffffffff) N >> 32.
+// Sample b: h = mix64(head + G (b + 1)), head = mix64(seed + G (counter + 1)) from the host - counter_draw(seed, counter, b) (tg_kernels.hpp) in
+// two stages; slot (first + ((h >> 32) M >> 32)) % T, env (h & 0xffffffff) N >> 32.
 __global__ __launch_bounds__(kDrawThreads) void k_replay_draw(int64_t B, uint64_t M, int64_t first, int64_t T, uint64_t N, uint64_t head,
                                                               const float* __restrict__ actions, int32_t A, const float* __restrict__ rewards,
                                                               const float* __restrict__ dones, const float* __restrict__ timeouts,

@@ -164,14 +164,13 @@ extern "C" int tg_selftest_penetration_division(int64_t* mismatches) {
 }
 
 // The launch decision of tg_random_translate for a call of that shape and those addresses, by the launcher's own function (tg_augment.h:
-// translate_plan).  The argument checks in front of it restate tg_random_translate_rows' (dtype, B, C, H, W, 2^30 elements); they are a copy,
-// not the product's code.  Host only.
+// translate_plan).  The argument checks in front of it are tg_random_translate_rows' own predicate (tg_augment_core.h: image_shape_fault).
+// Host only.
 extern "C" int tg_selftest_translate_plan(int32_t in_dtype, int32_t channels_first, int32_t C, int32_t H, int32_t W, int64_t B, uint64_t in_addr,
                                           uint64_t out_addr, int32_t* path, int32_t* chunks, int32_t* lds_bytes, int64_t* launches) {
     using tg::fail;
     if (!path || !chunks || !lds_bytes || !launches) return fail(-1, "NULL argument");
-    if (in_dtype != TG_AUGMENT_UINT8 && in_dtype != TG_AUGMENT_FLOAT32) return fail(-1, "unknown input dtype");
-    if (B < 0 || C < 1 || H < 2 || W < 2 || (int64_t)C * H * W > (1 << 30)) return fail(-1, "need B >= 0, C >= 1, H >= 2, W >= 2, C H W <= 2^30");
+    if (const char* what = tg::image_shape_fault(in_dtype, B, C, H, W)) return fail(-1, what);
     const tg::TranslatePlan p = tg::translate_plan(in_dtype == TG_AUGMENT_UINT8 ? 1 : 4, channels_first != 0, C, H, W, (uintptr_t)in_addr, (uintptr_t)out_addr);
     if (p.spl < 1) return fail(-1, "one sample has more workgroups than a launch holds");
     *path = p.vec;
@@ -186,8 +185,7 @@ extern "C" int tg_selftest_affine_plan(int32_t in_dtype, int32_t channels_first,
                                        uint64_t out_addr, int32_t* path, int32_t* in_vec, int32_t* chunks, int32_t* lds_bytes, int64_t* launches) {
     using tg::fail;
     if (!path || !in_vec || !chunks || !lds_bytes || !launches) return fail(-1, "NULL argument");
-    if (in_dtype != TG_AUGMENT_UINT8 && in_dtype != TG_AUGMENT_FLOAT32) return fail(-1, "unknown input dtype");
-    if (B < 0 || C < 1 || H < 2 || W < 2 || (int64_t)C * H * W > (1 << 30)) return fail(-1, "need B >= 0, C >= 1, H >= 2, W >= 2, C H W <= 2^30");
+    if (const char* what = tg::image_shape_fault(in_dtype, B, C, H, W)) return fail(-1, what);
     const tg::AffinePlan p = tg::affine_plan(in_dtype == TG_AUGMENT_UINT8 ? 1 : 4, channels_first != 0, C, H, W, (uintptr_t)in_addr, (uintptr_t)out_addr);
     if (p.spl < 1) return fail(-1, "one sample has more workgroups than a launch holds");
     *path = p.path;

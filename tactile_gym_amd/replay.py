@@ -1,7 +1,7 @@
 """A replay buffer in device memory: stable_baselines3's ReplayBuffer / DictReplayBuffer (the off-policy buffer of the reference's SAC / RAD_SAC)
 over torch tensors on the ROCm device, filled from obs_mode="torch" observations and sampled as augmented minibatches without a trip through
-the host (csrc/tg_replay.hip: k_replay_add, k_replay_draw; csrc/tg_augment.hip: the row-indexed k_random_translate; csrc/tg_rollout.hip:
-k_rollout_gather).
+the host (csrc/tg_replay.hip: k_replay_add, k_replay_draw; the image keys through augment.py's one fused-gather entry: csrc/tg_augment.hip,
+the row-indexed k_random_translate, or csrc/tg_affine.hip, the row-indexed k_random_affine; csrc/tg_rollout.hip: k_rollout_gather).
 
     buf = tg.DeviceReplayBuffer.for_env(venv, buffer_size=100_000, seed=0)
     buf.start(venv.reset())
@@ -29,8 +29,8 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .augment import RandomWarp
-from .rollout import DeviceRolloutBuffer, _space_shapes, _unwrap_augment
+from .augment import _chw, _gather_images, _unwrap_augment
+from .rollout import DeviceRolloutBuffer, _space_shapes
 from .vecnorm import DeviceVecNormalize
 
 __all__ = ["DeviceReplayBuffer", "ReplayBufferSamples"]
@@ -328,23 +328,7 @@ class DeviceReplayBuffer:
                 if k in self._image_keys and out_dtype == torch.float32:
                     out = torch.empty((2 * B,) + shape, dtype=torch.float32, device=dev)
                     cf = self._channels_first[k]
-                    c, h, w = shape if cf else (shape[2], shape[0], shape[1])
-                    if isinstance(module, RandomWarp):                                         # the general warp: tg_random_affine_rows
-                        module._fused(src, out, rows, 2 * B, c, h, w, cf, stream.value)
-                        obs[k], nxt[k] = out[:B], out[B:]
-                        continue
-                    if module is not None:
-                        (ax, ay), p, seed, counter = module.translate, module.p, module.seed, module.counter
-                        prm = torch.empty((2 * B, 3), dtype=torch.float32, device=dev)
-                    else:
-                        (ax, ay), p, seed, counter, prm = (0.0, 0.0), 0.0, 0, 0, None          # the plain uint8 -> float32 gather
-                    capi.check(L.tg_random_translate_rows(
-                        C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()), capi.AUGMENT_DTYPE["uint8"], int(cf), 2 * B, c, h, w, ax, ay, p,
-                        C.c_uint64(int(seed) & _M64), C.c_uint64(int(counter) & _M64), None,
-                        C.c_void_p(prm.data_ptr() if prm is not None else None), C.c_void_p(rows.data_ptr()), stream))
-                    if module is not None:
-                        module.counter += 1
-                        module._params = {"batch_prob": prm[:, 0] != 0, "translations": prm[:, 1:3]}
+                    _gather_images(module, src, out, rows, 2 * B, *_chw(shape, cf), cf, stream.value)   # one launch: augment.py
                 else:
                     out = torch.empty((2 * B,) + shape, dtype=dt, device=dev)
                     plain.append((src, out))

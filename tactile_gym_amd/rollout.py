@@ -1,6 +1,7 @@
 """A rollout buffer in device memory: stable_baselines3's RolloutBuffer / DictRolloutBuffer (the on-policy buffer of the reference's PPO /
 RAD_PPO) over torch tensors on the ROCm device, filled from obs_mode="torch" observations and read as augmented minibatches without a trip
-through the host (csrc/tg_rollout.hip: k_rollout_add, k_rollout_gae, k_rollout_gather; csrc/tg_augment.hip: the row-indexed k_random_translate; csrc/tg_affine.hip: the row-indexed k_random_affine for a RandomWarp).
+through the host (csrc/tg_rollout.hip: k_rollout_add, k_rollout_gae, k_rollout_gather; the image keys through augment.py's one fused-gather
+entry: csrc/tg_augment.hip, the row-indexed k_random_translate, or for a RandomWarp csrc/tg_affine.hip, the row-indexed k_random_affine).
 
     buf = tg.DeviceRolloutBuffer.for_env(venv, n_steps, gamma=0.95, gae_lambda=0.9)
     obs, starts = venv.reset(), torch.ones(venv.num_envs, device=buf.device)
@@ -31,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .augment import RandomTranslate, RandomWarp
+from .augment import _chw, _gather_images, _unwrap_augment
 
 __all__ = ["DeviceRolloutBuffer", "RolloutBufferSamples", "flat_rows"]
 
@@ -62,19 +63,6 @@ def _space_shapes(space, name):
     if not out:
         raise ValueError(f"{name} has no keys")
     return out
-
-
-def _unwrap_augment(augment):
-    """The RandomTranslate or RandomWarp of `augment`: the module itself or the one member of the params files' nn.Sequential."""
-    m = augment
-    if isinstance(m, torch.nn.Sequential):
-        if len(m) != 1:
-            raise TypeError(f"augment must hold exactly one RandomTranslate or RandomWarp, got an nn.Sequential of {len(m)} modules")
-        m = m[0]
-    if not isinstance(m, (RandomTranslate, RandomWarp)):
-        raise TypeError(f"augment must be a tactile_gym_amd.augment.RandomTranslate or RandomWarp (or the nn.Sequential of one), got "
-                        f"{type(m).__name__}: the fused gather needs the module's ranges, p, seed and counter, not a callable")
-    return m
 
 
 class DeviceRolloutBuffer:
@@ -288,23 +276,7 @@ class DeviceRolloutBuffer:
                 if k in self._image_keys and out_dtype == torch.float32:
                     out = torch.empty((B,) + shape, dtype=torch.float32, device=dev)
                     cf = self._channels_first[k]
-                    c, h, w = shape if cf else (shape[2], shape[0], shape[1])
-                    if isinstance(module, RandomWarp):                                         # the general warp: tg_random_affine_rows
-                        module._fused(src, out, rows, B, c, h, w, cf, stream.value)
-                        obs[k] = out
-                        continue
-                    if module is not None:
-                        (ax, ay), p, seed, counter = module.translate, module.p, module.seed, module.counter
-                        prm = torch.empty((B, 3), dtype=torch.float32, device=dev)
-                    else:
-                        (ax, ay), p, seed, counter, prm = (0.0, 0.0), 0.0, 0, 0, None          # the plain uint8 -> float32 gather
-                    capi.check(L.tg_random_translate_rows(
-                        C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()), capi.AUGMENT_DTYPE["uint8"], int(cf), B, c, h, w, ax, ay, p,
-                        C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_uint64(int(counter) & 0xFFFFFFFFFFFFFFFF), None,
-                        C.c_void_p(prm.data_ptr() if prm is not None else None), C.c_void_p(rows.data_ptr()), stream))
-                    if module is not None:
-                        module.counter += 1
-                        module._params = {"batch_prob": prm[:, 0] != 0, "translations": prm[:, 1:3]}
+                    _gather_images(module, src, out, rows, B, *_chw(shape, cf), cf, stream.value)   # one launch: augment.py
                 else:
                     out = torch.empty((B,) + shape, dtype=dt, device=dev)
                     plain.append((src, out))

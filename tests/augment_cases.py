@@ -13,7 +13,7 @@ import numpy as np
 
 from augment_ref import draw_params
 
-CHUNK = 4096          # kTrChunk: output elements per workgroup
+CHUNK = 4096          # kAugChunk: output elements per workgroup
 MAX_ROW = 8192        # kTrMaxRow: R + S of the staged path
 MAX_BLOCKS = 1 << 23  # workgroups per launch
 

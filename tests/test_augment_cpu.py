@@ -1,5 +1,5 @@
 """tactile_gym_amd.augment without a GPU: the two references of tests/augment_ref.py against each other, the draws' statistics, the kornia-style
-constructor's argument rules, the CPU refusal, the C ABI entry and the kernel's resources."""
+constructor's argument rules, the CPU refusal, the C ABI entry, the kernel's resources and the one C call of the device buffers' fused gather."""
 import os
 import re
 import subprocess
@@ -165,3 +165,53 @@ def test_random_translate_kernels_use_no_scratch(tmp_path):
     ks = {k: v for k, v in _kernel_scratch(tmp_path).items() if "k_random_translate" in k}
     assert len(ks) == 4, sorted(ks)
     assert all(v == 0 for v in ks.values()), ks
+
+
+@pytest.mark.parametrize("channels_first", [True, False])
+def test_fused_gather_entry_issues_the_one_call(monkeypatch, channels_first):
+    """augment._gather_images, the image-key branch of DeviceRolloutBuffer._gather and DeviceReplayBuffer.sample: for no module, a RandomTranslate
+    and a RandomWarp it issues exactly one C call with the arguments those branches laid out by hand, moves the module's counter on by one and
+    sets `_params` under kornia's names.  The library is replaced by a recorder, so CPU tensors do (the stream is an argument)."""
+    torch = pytest.importorskip("torch")
+    import ctypes
+    import tactile_gym_amd.augment as K
+
+    calls = []
+
+    class Recorder:
+        def __getattr__(self, name):
+            def entry(*args):
+                calls.append((name, tuple(a.value if isinstance(a, (ctypes.c_void_p, ctypes.c_uint64)) else a for a in args)))
+                return 0
+            return entry
+
+    monkeypatch.setattr(_capi, "lib", lambda: Recorder())
+    B, c, h, w, stream, M64 = 3, 2, 4, 4, 0x1234, 2**64 - 1
+    sample = (c, h, w) if channels_first else (h, w, c)
+    src = torch.zeros((5,) + sample, dtype=torch.uint8)
+    out = torch.empty((B,) + sample, dtype=torch.float32)
+    rows = torch.tensor([4, 0, 2], dtype=torch.int64)
+    head = (src.data_ptr(), out.data_ptr(), _capi.AUGMENT_DTYPE["uint8"], int(channels_first), B, c, h, w)
+
+    K._gather_images(None, src, out, rows, B, c, h, w, channels_first, stream)       # the plain uint8 -> float32 gather: a translate with p = 0
+    assert calls == [("tg_random_translate_rows", head + (0.0, 0.0, 0.0, 0, 0, None, None, rows.data_ptr(), stream))]
+
+    del calls[:]
+    t = K.RandomTranslate(translate=(0.05, 0.1), p=0.25, seed=2**64 + 5)
+    t.counter = 7
+    K._gather_images(t, src, out, rows, B, c, h, w, channels_first, stream)
+    assert t.counter == 8 and set(t._params) == {"batch_prob", "translations"}
+    assert t._params["batch_prob"].shape == (B,) and t._params["batch_prob"].dtype == torch.bool and t._params["translations"].shape == (B, 2)
+    prm = t._params["translations"].data_ptr() - 4                                    # translations = prm[:, 1:3] of the [B, 3] the call wrote
+    assert calls == [("tg_random_translate_rows", head + (0.05, 0.1, 0.25, (2**64 + 5) & M64, 7, None, prm, rows.data_ptr(), stream))]
+
+    del calls[:]
+    wp = K.RandomWarp(degrees=10, translate=(0.1, 0.2), scale=(0.9, 1.1), shear=5, p=0.5, seed=-1)
+    wp.counter = 2**64 + 3
+    K._gather_images(wp, src, out, rows, B, c, h, w, channels_first, stream)
+    assert wp.counter == 2**64 + 4 and set(wp._params) == {"batch_prob", "translations", "center", "scale", "angle", "sx", "sy"}
+    assert wp._params["translations"].shape == (B, 2) and wp._params["scale"].shape == (B, 2) and wp._params["angle"].shape == (B,)
+    assert wp._coeffs.shape == (B, 6) and wp._coeffs.dtype == torch.float32
+    prm = wp._params["translations"].data_ptr() - 4
+    assert calls == [("tg_random_affine_rows", head + (0.1, 0.2, -10.0, 10.0, 0.9, 1.1, 0.0, 0.0, -5.0, 5.0, 0.0, 0.0, 0.5, M64, 3, None, prm, None,
+                                                       wp._coeffs.data_ptr(), rows.data_ptr(), stream))]
