@@ -26,6 +26,12 @@ int tg_selftest_narrowphase(int32_t n_cases, int32_t n_hull, const double* hulls
 /* The same for two hulls (csrc/tg_spin.hip's pair; oracle/narrowphase.c: mb_gjk_epa_hull_hull): hulls [n_cases][n_hull][3] = body A's hull in body
  * B's frame, hull_b [n_b][3] = body B's in its own frame (n_b <= 256); out as above. */
 int tg_selftest_narrowphase_hulls(int32_t n_cases, int32_t n_hull, const double* hulls, int32_t n_b, const double* hull_b, double* out);
+/* Self-test of the persistent manifold of csrc/tg_narrowphase.hpp (manifold_add / manifold_refresh; oracle/narrowphase.c: mb_manifold_add /
+ * mb_manifold_refresh) under scripts of operations, one wavefront per case, the manifold in LDS and empty at the start.
+ * ops [n_cases][n_ops][36] = kind (0 add, 1 refresh, anything else: nothing), breaking, oa[3], Ra[9] (row-major), ob[3], Rb[9], pa_w[3],
+ * pb_w[3], n_w[3], depth (the last ten are read by an add only); out [n_cases][n_ops][65] = the manifold after each operation:
+ * la[4][3], lb[4][3], nrm[4][3], pa[4][3], pb[4][3], depth[4], count. */
+int tg_selftest_manifold(int32_t n_cases, int32_t n_ops, const double* ops, double* out);
 
 /* Self-test of the raster's depth division (tactile_sensor.py:239-294 reads an IEEE depth buffer): n pseudo-random operand pairs
  * with exponents 2^-40 .. 2^24 divided by the kernels' refinement and by the correctly rounded `/`; *mismatches = quotients whose

@@ -97,16 +97,33 @@ static int gjk(const double* hull, int n, const shape_b* e, sv_t S[4], int* ns_o
     int ns = 1;
     support(hull, n, e, d0, &S[0]);
     double x[3] = {S[0].w[0], S[0].w[1], S[0].w[2]}, lam[4] = {1.0, 0.0, 0.0, 0.0};
+    /* tri: x lies inside a triangle that all but holds the origin, |x| <= 1e-6 |S0| (A38a).  x is a sum of vertices a million times its size
+     * and more, so its components along the triangle carry their rounding, 1e-16 |S0|: the normal x / |x| is off by 1e-10 at the threshold and
+     * by 1e-4 at |x| = 1e-12 m, and from about 1e-10 m the vertex that -x picks is dropped again for ever, or the test on x . w passes by
+     * chance, with x up to 1e-10 m off.  The triangle's normal dn = e1 x e2 is good to the last digits: the search goes along it, the
+     * progress is measured along it ( dn . (w - S0) <= 1e-12 dn . (0 - S0)  is the test below for -x parallel to dn), and when the search ends
+     * on the triangle the distance and the normal are the plane's. */
+    int tri = 0; double dn[3] = {0.0, 0.0, 0.0}, h = 0.0;
     for (int it = 0; it < 64; ++it) {
         const double xx = dot3(x, x);
         if (xx <= 1e-28) { *ns_out = ns; *dist = 0.0; return 2; }
-        const double d[3] = {-x[0], -x[1], -x[2]};
-        sv_t w; support(hull, n, e, d, &w);
-        if (xx - dot3(x, w.w) <= 1e-12 * xx) break;                           /* no vertex of D is closer along -x: x is the closest point */
+        sv_t w;
+        tri = ns == 3 && xx <= 1e-12 * dot3(S[0].w, S[0].w);
+        if (tri) {
+            double e1[3], e2[3]; sub3(S[1].w, S[0].w, e1); sub3(S[2].w, S[0].w, e2); cross3(e1, e2, dn);
+            if (dot3(dn, x) > 0.0) { dn[0] = -dn[0]; dn[1] = -dn[1]; dn[2] = -dn[2]; }
+            support(hull, n, e, dn, &w);
+            h = -dot3(dn, S[0].w);
+            if (dot3(dn, w.w) + h <= 1e-12 * h) break;
+        } else {
+            const double d[3] = {-x[0], -x[1], -x[2]};
+            support(hull, n, e, d, &w);
+            if (xx - dot3(x, w.w) <= 1e-12 * xx) break;                       /* no vertex of D is closer along -x: x is the closest point */
+        }
         int dup = 0;
         for (int k = 0; k < ns; ++k) if (S[k].w[0] == w.w[0] && S[k].w[1] == w.w[1] && S[k].w[2] == w.w[2]) dup = 1;
         if (dup) break;
-        S[ns++] = w;
+        S[ns++] = w; tri = 0;
         if (ns == 2) closest_segment(S[0].w, S[1].w, lam);
         else if (ns == 3) closest_triangle(S[0].w, S[1].w, S[2].w, lam);
         else {
@@ -119,11 +136,12 @@ static int gjk(const double* hull, int n, const shape_b* e, sv_t S[4], int* ns_o
         ns = m;
         for (int c = 0; c < 3; ++c) { double acc = 0.0; for (int k = 0; k < ns; ++k) acc += lam[k] * S[k].w[c]; x[c] = acc; }
     }
-    const double len = sqrt(dot3(x, x));
-    *ns_out = ns; *dist = len;
+    const double len = tri ? sqrt(dot3(dn, dn)) : sqrt(dot3(x, x));
+    *ns_out = ns; *dist = tri ? h / len : len;
     for (int c = 0; c < 3; ++c) {
         double acc = 0.0; for (int k = 0; k < ns; ++k) acc += lam[k] * S[k].a[c];
-        pa[c] = acc; pb[c] = acc - x[c]; nrm[c] = x[c] / len;
+        if (tri) { nrm[c] = -dn[c] / len; pa[c] = acc; pb[c] = acc - *dist * nrm[c]; }
+        else { pa[c] = acc; pb[c] = acc - x[c]; nrm[c] = x[c] / len; }
     }
     return 0;
 }
@@ -131,14 +149,20 @@ static int gjk(const double* hull, int n, const shape_b* e, sv_t S[4], int* ns_o
 /* ---- EPA from GJK's tetrahedron.  depth > 0: how far the cores overlap along n (from the box to the hull: moving the hull by depth n separates them). */
 enum { EPA_MAXV = 48, EPA_MAXF = 96, EPA_MAXE = 48 };   /* the device's LDS capacities (tg_narrowphase.hpp) */
 typedef struct { int v[3]; double n[3], d; int alive; } face_t;
-static int make_face(const sv_t* V, int i0, int i1, int i2, face_t* f) {
+/* A face of the polytope, wound so that its normal points out of it.  A later face (opp < 0) takes its side from the sign of d, the origin
+ * being inside.  The four faces of GJK's tetrahedron take it from the opposite vertex `opp`: GJK hands the tetrahedron over with the origin
+ * inside OR ON it, and with the origin in a face's plane (touching cores, a symmetric overlap) d is +-0 or rounding noise and says
+ * nothing - a face left pointing inwards is then the closest one, and the expansion along it eats the polytope from inside (A38a). */
+static int make_face(const sv_t* V, int i0, int i1, int i2, int opp, face_t* f) {
     double e1[3], e2[3], nn[3]; sub3(V[i1].w, V[i0].w, e1); sub3(V[i2].w, V[i0].w, e2); cross3(e1, e2, nn);
     const double len = sqrt(dot3(nn, nn));
     if (!(len > 0.0)) return 0;
     f->v[0] = i0; f->v[1] = i1; f->v[2] = i2;
     for (int c = 0; c < 3; ++c) f->n[c] = nn[c] / len;
     f->d = dot3(f->n, V[i0].w);
-    if (f->d < 0.0) { f->v[1] = i2; f->v[2] = i1; for (int c = 0; c < 3; ++c) f->n[c] = -f->n[c]; f->d = -f->d; }   /* outward: away from the origin inside */
+    int flip = f->d < 0.0;
+    if (opp >= 0) { double t[3]; sub3(V[opp].w, V[i0].w, t); const double s = dot3(f->n, t); if (s != 0.0) flip = s > 0.0; }
+    if (flip) { f->v[1] = i2; f->v[2] = i1; for (int c = 0; c < 3; ++c) f->n[c] = -f->n[c]; f->d = -f->d; }
     f->alive = 1;
     return 1;
 }
@@ -147,11 +171,13 @@ static int epa(const double* hull, int n, const shape_b* e, const sv_t S[4], dou
     int nv = 4, nf = 0;
     for (int k = 0; k < 4; ++k) V[k] = S[k];
     static const int T[4][3] = {{0, 1, 2}, {0, 2, 3}, {0, 3, 1}, {1, 3, 2}};
-    for (int f = 0; f < 4; ++f) if (!make_face(V, T[f][0], T[f][1], T[f][2], &F[nf++])) return 0;
+    static const int O[4] = {3, 1, 2, 0};
+    for (int f = 0; f < 4; ++f) if (!make_face(V, T[f][0], T[f][1], T[f][2], O[f], &F[nf++])) return 0;
     int best = 0;
     for (int it = 0; it < 64; ++it) {
         best = -1;
         for (int f = 0; f < nf; ++f) if (F[f].alive && (best < 0 || F[f].d < F[best].d)) best = f;
+        if (best < 0) return 0;                                                            /* every face went and none could be added */
         sv_t w; support(hull, n, e, F[best].n, &w);
         if (dot3(F[best].n, w.w) - F[best].d <= 1e-12 || nv == EPA_MAXV) break;           /* the face lies on D's boundary */
         /* faces seen from w go; the horizon = their edges whose reverse is not an edge of another removed face */
@@ -168,7 +194,11 @@ static int epa(const double* hull, int n, const shape_b* e, const sv_t S[4], dou
             }
         }
         V[nv] = w;
-        for (int q = 0; q < ne && nf < EPA_MAXF; ++q) if (make_face(V, E[q][0], E[q][1], nv, &F[nf])) ++nf;
+        for (int q = 0; q < ne; ++q) {                                                     /* a full list takes new faces where dead ones lie */
+            int s = nf;
+            if (nf == EPA_MAXF) { s = 0; while (s < nf && F[s].alive) ++s; if (s == nf) break; }
+            if (make_face(V, E[q][0], E[q][1], nv, -1, &F[s]) && s == nf) ++nf;
+        }
         ++nv;
     }
     /* witness points: the origin's projection dn lies in the closest face; its barycentric weights carry over to the hull points */

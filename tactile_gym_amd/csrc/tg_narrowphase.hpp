@@ -170,19 +170,32 @@ template <class BT> __device__ __forceinline__ int gjk(const Hull& H, BT e, SV* 
     int ns = 1;
     support(H, e, d0, S[0], lane);
     double x[3] = {S[0].w[0], S[0].w[1], S[0].w[2]}, lam[4] = {1.0, 0.0, 0.0, 0.0};
+    // tri: x lies inside a triangle that all but holds the origin, |x| <= 1e-6 |S0| (PARITY A38a; oracle/narrowphase.c says why): the search
+    // goes along the triangle's normal dn, the progress is measured along it, and a search that ends there returns the plane's distance and normal
+    bool tri = false; double dn[3] = {0.0, 0.0, 0.0}, h = 0.0;
     for (int it = 0; it < 64; ++it) {
         const double xx = dot3(x, x);
         if (xx <= 1e-28) { dist = 0.0; return 2; }
-        const double d[3] = {-x[0], -x[1], -x[2]};
-        SV w; support(H, e, d, w, lane);
-        if (xx - dot3(x, w.w) <= 1e-12 * xx) break;
+        SV w;
+        tri = ns == 3 && xx <= 1e-12 * dot3(S[0].w, S[0].w);
+        if (tri) {
+            double e1[3], e2[3]; sub3(S[1].w, S[0].w, e1); sub3(S[2].w, S[0].w, e2); cross3(e1, e2, dn);
+            if (dot3(dn, x) > 0.0) { dn[0] = -dn[0]; dn[1] = -dn[1]; dn[2] = -dn[2]; }
+            support(H, e, dn, w, lane);
+            h = -dot3(dn, S[0].w);
+            if (dot3(dn, w.w) + h <= 1e-12 * h) break;
+        } else {
+            const double d[3] = {-x[0], -x[1], -x[2]};
+            support(H, e, d, w, lane);
+            if (xx - dot3(x, w.w) <= 1e-12 * xx) break;
+        }
         bool dup = false;
 #pragma unroll
         for (int k = 0; k < 4; ++k) if (k < ns && S[k].w[0] == w.w[0] && S[k].w[1] == w.w[1] && S[k].w[2] == w.w[2]) dup = true;
         if (dup) break;
 #pragma unroll
         for (int k = 0; k < 4; ++k) if (k == ns) S[k] = w;
-        ++ns;
+        ++ns; tri = false;
         if (ns == 2) closest_segment(S[0].w, S[1].w, lam);
         else if (ns == 3) closest_triangle(S[0].w, S[1].w, S[2].w, lam);
         else if (closest_tetra(S, lam)) { dist = 0.0; return 1; }
@@ -206,21 +219,24 @@ template <class BT> __device__ __forceinline__ int gjk(const Hull& H, BT e, SV* 
             x[c] = acc;
         }
     }
-    const double len = sqrt(dot3(x, x));
-    dist = len;
+    const double len = tri ? sqrt(dot3(dn, dn)) : sqrt(dot3(x, x));
+    dist = tri ? h / len : len;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         double acc = 0.0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) if (k < ns) acc += lam[k] * S[k].a[c];
-        pa[c] = acc; pb[c] = acc - x[c]; nrm[c] = x[c] / len;
+        if (tri) { nrm[c] = -dn[c] / len; pa[c] = acc; pb[c] = acc - dist * nrm[c]; }
+        else { pa[c] = acc; pb[c] = acc - x[c]; nrm[c] = x[c] / len; }
     }
     return 0;
 }
 
 // ---- EPA on LDS scratch `sc` (kScratchWords doubles)
 __device__ __forceinline__ void ld_v(lptr<double> sc, int i, double* w) { w[0] = sc[kOffV + 6 * i]; w[1] = sc[kOffV + 6 * i + 1]; w[2] = sc[kOffV + 6 * i + 2]; }
-__device__ __forceinline__ bool make_face(lptr<double> sc, int i0, int i1, int i2, int f, int lane) {
+// a face wound outwards: a later face (opp < 0) by the sign of d; a face of GJK's tetrahedron, which may hold the origin in its plane (d = +-0
+// or rounding noise: touching cores, a symmetric overlap), by the opposite vertex `opp` (PARITY A38a)
+__device__ __forceinline__ bool make_face(lptr<double> sc, int i0, int i1, int i2, int opp, int f, int lane) {
 #pragma clang fp contract(off)
     double p0[3], p1[3], p2[3], e1[3], e2[3], nn[3];
     ld_v(sc, i0, p0); ld_v(sc, i1, p1); ld_v(sc, i2, p2);
@@ -230,7 +246,13 @@ __device__ __forceinline__ bool make_face(lptr<double> sc, int i0, int i1, int i
     double n[3] = {nn[0] / len, nn[1] / len, nn[2] / len};
     double d = dot3(n, p0);
     int a1 = i1, a2 = i2;
-    if (d < 0.0) { a1 = i2; a2 = i1; n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; d = -d; }
+    bool flip = d < 0.0;
+    if (opp >= 0) {
+        double po[3], t[3]; ld_v(sc, opp, po); sub3(po, p0, t);
+        const double s = dot3(n, t);
+        if (s != 0.0) flip = s > 0.0;
+    }
+    if (flip) { a1 = i2; a2 = i1; n[0] = -n[0]; n[1] = -n[1]; n[2] = -n[2]; d = -d; }
     if (lane == 0) {
         lptr<int> fv = (lptr<int>)(sc + kOffFV);
         sc[kOffFN + 4 * f] = n[0]; sc[kOffFN + 4 * f + 1] = n[1]; sc[kOffFN + 4 * f + 2] = n[2]; sc[kOffFN + 4 * f + 3] = d;
@@ -252,10 +274,10 @@ template <class BT> __device__ __forceinline__ bool epa(const Hull& H, BT e, con
             for (int c = 0; c < 3; ++c) { sc[kOffV + 6 * k + c] = S[k].w[c]; sc[kOffV + 6 * k + 3 + c] = S[k].a[c]; }
     }
     __syncthreads();
-    if (!make_face(sc, 0, 1, 2, nf++, lane)) return false;
-    if (!make_face(sc, 0, 2, 3, nf++, lane)) return false;
-    if (!make_face(sc, 0, 3, 1, nf++, lane)) return false;
-    if (!make_face(sc, 1, 3, 2, nf++, lane)) return false;
+    if (!make_face(sc, 0, 1, 2, 3, nf++, lane)) return false;
+    if (!make_face(sc, 0, 2, 3, 1, nf++, lane)) return false;
+    if (!make_face(sc, 0, 3, 1, 2, nf++, lane)) return false;
+    if (!make_face(sc, 1, 3, 2, 0, nf++, lane)) return false;
     int best = 0;
     for (int it = 0; it < 64; ++it) {
         best = -1; double bd = 0.0;
@@ -263,6 +285,7 @@ template <class BT> __device__ __forceinline__ bool epa(const Hull& H, BT e, con
             const double fd = sc[kOffFN + 4 * f + 3];
             if (fv[4 * f + 3] && (best < 0 || fd < bd)) { best = f; bd = fd; }
         }
+        if (best < 0) return false;                          // every face went and none could be added
         const double bn[3] = {sc[kOffFN + 4 * best], sc[kOffFN + 4 * best + 1], sc[kOffFN + 4 * best + 2]};
         SV w; support(H, e, bn, w, lane);
         if (dot3(bn, w.w) - bd <= 1e-12 || nv == kMaxV) break;
@@ -293,7 +316,15 @@ template <class BT> __device__ __forceinline__ bool epa(const Hull& H, BT e, con
             for (int c = 0; c < 3; ++c) { sc[kOffV + 6 * nv + c] = w.w[c]; sc[kOffV + 6 * nv + 3 + c] = w.a[c]; }
         }
         __syncthreads();
-        for (int q = 0; q < ne && nf < kMaxF; ++q) if (make_face(sc, ed[2 * q], ed[2 * q + 1], nv, nf, lane)) ++nf;
+        for (int q = 0; q < ne; ++q) {                        // a full list takes new faces where dead ones lie
+            int s = nf;
+            if (nf == kMaxF) {
+                s = 0;
+                while (s < nf && fv[4 * s + 3]) ++s;
+                if (s == nf) break;
+            }
+            if (make_face(sc, ed[2 * q], ed[2 * q + 1], nv, -1, s, lane) && s == nf) ++nf;
+        }
         ++nv;
     }
     const int i0 = fv[4 * best], i1 = fv[4 * best + 1], i2 = fv[4 * best + 2];
