@@ -455,6 +455,14 @@ typedef struct {
 int tg_get_state(tg_ctx* ctx, const tg_state_view* view);
 /* Overwrite joint state (tests): q, qd [num_envs][ndof]; re-evaluates the cached TCP pose. */
 int tg_set_joint_state(tg_ctx* ctx, const double* q, const double* qd);
+/* Inspection (tests): int32 [num_envs], the env steps for which each env's step may still take the analytic fixed point qd = target,
+ * q += dt target without a new full solve.  0: the env's next step starts with a full solve; 8: the last step's full
+ * solve converged within 80 % of the sweep budget; 7 .. 1: steps since then; a reset renews it or leaves 0, tg_set_joint_state leaves 0.
+ * The arm steps take the shortcut only when every env of the wavefront holds a positive value (64 envs, 16 on the quad mapping,
+ * tg_get_step_mode; the env's own on object_balance's wave mapping) AND the a-priori bound on the motor impulses holds in the tick.
+ * Always 0 for the MG400, in threshold mode and on the kernels that solve every tick.  Synchronises.  A function added, no struct changed:
+ * TG_ABI_VERSION stays. */
+int tg_copy_step_licence(tg_ctx* ctx, int32_t* host_dst);
 
 /* Per-kernel timing (bench.py's roofline leg).  enable = 1: HIP event pairs around every launch class on the launch stream, between the step's
  * launches; every figure carries what an EMPTY event pair measures (3 - 5 us).  enable = 2: only the kernels' own clock

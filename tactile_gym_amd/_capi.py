@@ -254,6 +254,7 @@ SYMBOLS = {
                                  C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tg_get_state": (C.c_int, [_ctx, C.POINTER(TgStateView)]),
     "tg_set_joint_state": (C.c_int, [_ctx, _dp, _dp]),
+    "tg_copy_step_licence": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),
     "tg_profile_enable": (C.c_int, [_ctx, C.c_int32]),
     "tg_profile_get": (C.c_int, [_ctx, C.c_int32, _dp, C.POINTER(C.c_int64)]),
     "tg_inverse_dynamics": (C.c_int, [C.POINTER(TgRobot), C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),

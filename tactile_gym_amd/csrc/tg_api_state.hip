@@ -124,6 +124,12 @@ int tg_get_step_mode(tg_ctx* c, int32_t* mode, int32_t* envs_per_wavefront) {
     return 0;
 }
 
+int tg_copy_step_licence(tg_ctx* c, int32_t* host_dst) {
+    if (!c || !host_dst) return fail(-1, "NULL argument");
+    TG_ENTER(c);
+    return fetch_soa(c, c->st.licence, 1, host_dst);   // synchronises: the value the last step (reset, tg_set_joint_state) left
+}
+
 int tg_get_actions(tg_ctx* c, void** dev_actions) {
     if (!c || !dev_actions) return fail(-1, "NULL argument");
     *dev_actions = c->d_actions;

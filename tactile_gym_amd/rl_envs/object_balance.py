@@ -128,8 +128,10 @@ def build_config(num_envs, max_steps, image_size, env_modes, physics_dtype="f64"
 
 class ObjectBalanceVecEnv(TactileVecEnv):
     def __init__(self, num_envs, max_steps=1000, image_size=(64, 64), env_modes=env_modes_default, physics_dtype="f64", auto_reset=True,
-                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False):
+                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False, max_force=None):
         cfg, robot, sensor, mesh, modes = build_config(num_envs, max_steps, image_size, env_modes, physics_dtype, auto_reset, device)
+        if max_force is not None:
+            robot.max_force = float(max_force)               # the arm's motor force limit (ur5.py:19 / mg400.py:27: 1000), as object_push's keyword
         if modes["object_mode"] == "ball_on_plate" and contact_mapping == "wave":
             raise ValueError("object_mode ball_on_plate runs on the lane mapping (contact_mapping 'auto' or 'lane')")
         cfg.reset_bank = capi.RESET_BANK[reset_bank]              # "off": every reset recomputes the arm's blocking move (k_reset_body's template)

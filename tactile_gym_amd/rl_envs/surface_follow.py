@@ -110,8 +110,10 @@ def build_config(num_envs, max_steps, image_size, env_modes, physics_dtype="f64"
 
 class SurfaceFollowAutoVecEnv(TactileVecEnv):
     def __init__(self, num_envs, max_steps=200, image_size=(64, 64), env_modes=env_modes_default, physics_dtype="f64", auto_reset=True,
-                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False):
+                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False, max_force=None):
         cfg, robot, sensor, modes = build_config(num_envs, max_steps, image_size, env_modes, physics_dtype, auto_reset, device)
+        if max_force is not None:
+            robot.max_force = float(max_force)               # the arm's motor force limit (ur5.py:19 / mg400.py:27: 1000), as object_push's keyword
         cfg.pgs_full_sweeps = int(bool(pgs_full_sweeps))   # run all solver sweeps instead of leaving at convergence
         cfg.solver_residual_threshold = float(solver_residual_threshold)   # btContactSolverInfo::m_leastSquaresResidualThreshold (PARITY A7b): 0 = exit at convergence only, 1e-7 = what PyBullet is believed to run
         cfg.contact_mapping = capi.CONTACT_MAP[contact_mapping]   # \"wave\": every tick a full tick on the env's own wavefront (k_step_arm_wave; measured slower)
@@ -151,9 +153,11 @@ class SurfaceFollowGoalVecEnv(SurfaceFollowAutoVecEnv):
     """surface_follow-v1: the agent drives every dimension; `tactile_and_feature` adds [tcp_pos, goal_pos] in the work frame."""
 
     def __init__(self, num_envs, max_steps=200, image_size=(64, 64), env_modes=env_modes_default, physics_dtype="f64", auto_reset=True,
-                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False):
+                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False, max_force=None):
         cfg, robot, sensor, modes = build_config(num_envs, max_steps, image_size, env_modes, physics_dtype, auto_reset, device,
                                                  goal_variant=True)
+        if max_force is not None:
+            robot.max_force = float(max_force)               # the arm's motor force limit (ur5.py:19 / mg400.py:27: 1000), as object_push's keyword
         cfg.pgs_full_sweeps = int(bool(pgs_full_sweeps))
         cfg.solver_residual_threshold = float(solver_residual_threshold)   # btContactSolverInfo::m_leastSquaresResidualThreshold (PARITY A7b): 0 = exit at convergence only, 1e-7 = what PyBullet is believed to run
         cfg.contact_mapping = capi.CONTACT_MAP[contact_mapping]   # \"wave\": every tick a full tick on the env's own wavefront (k_step_arm_wave; measured slower, DESIGN 4.1g)
@@ -200,8 +204,10 @@ class SurfaceFollowVertVecEnv(SurfaceFollowGoalVecEnv):
     [tcp_pos, goal_pos] in the work frame (surface_follow_vert_env.py:83-100)."""
 
     def __init__(self, num_envs, max_steps=200, image_size=(64, 64), env_modes=env_modes_default_vert, physics_dtype="f64", auto_reset=True,
-                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False):
+                 device=0, obs_mode="numpy", seed=None, pgs_full_sweeps=False, solver_residual_threshold=0.0, copy_obs=True, contact_mapping="auto", reset_bank="auto", frame_stack=1, channels_first=False, max_force=None):
         cfg, robot, sensor, modes = build_config(num_envs, max_steps, image_size, env_modes, physics_dtype, auto_reset, device)
+        if max_force is not None:
+            robot.max_force = float(max_force)               # the arm's motor force limit (ur5.py:19 / mg400.py:27: 1000), as object_push's keyword
         cfg.pgs_full_sweeps = int(bool(pgs_full_sweeps))
         cfg.solver_residual_threshold = float(solver_residual_threshold)   # btContactSolverInfo::m_leastSquaresResidualThreshold (PARITY A7b): 0 = exit at convergence only, 1e-7 = what PyBullet is believed to run
         cfg.contact_mapping = capi.CONTACT_MAP[contact_mapping]   # \"wave\": every tick a full tick on the env's own wavefront (k_step_arm_wave; measured slower, DESIGN 4.1g)

@@ -844,6 +844,13 @@ class TactileVecEnv(_VecEnvBase):
         dp = C.POINTER(C.c_double)
         capi.check(self._L.tg_set_joint_state(self._ctx, q.ctypes.data_as(dp), qd.ctypes.data_as(dp)))
 
+    def step_licence(self):
+        """int32 [N]: the env steps for which each env may still take the analytic fixed point without a new full solve (tg_copy_step_licence;
+        DESIGN.md 4.1 item 3).  0 after set_joint_state, for the MG400, in threshold mode and wherever every tick is solved in full."""
+        out = np.zeros(self.num_envs, np.int32)
+        capi.check(self._L.tg_copy_step_licence(self._ctx, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
     def profile(self, enable=True):
         """True / 1: HIP events around every launch class + the kernels' own clock; 2 / "clock": the own clock only, no host call between the
         step's launches; False: off."""
