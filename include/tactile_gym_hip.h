@@ -768,6 +768,33 @@ int tg_action_head(const float* mean_dev, const float* log_std_dev, int32_t log_
                    float log_std_min, float log_std_max, int32_t mode, int32_t deterministic, uint64_t seed, uint64_t counter,
                    const float* noise_in_dev, float* actions_out, float* env_actions_out, float* gaussian_out, float* log_prob_out,
                    float* noise_out, void* hip_stream);
+
+/* ---- device conv stem: NatureCNN's first layer on this project's observations -------------------------------------------------
+ * stable_baselines3's preprocess_obs (obs.float() / 255), Conv2d(Cn, 32, kernel_size=8, stride=4) and ReLU as ONE launch, and the layer's
+ * backward pass for the weight and the bias (the input is data: there is no input gradient).  Context free; the launches go to hip_stream,
+ * nothing is allocated or synchronised.  x_dev: uint8 (x_is_float 0) or float32 (x_is_float 1), [B][Cn][H][W] (channels_first 1) or
+ * [B][H][W][Cn] (channels_first 0); weight_dev: float32 [32][Cn][8][8] (torch's Conv2d layout); bias_dev: float32 [32]; y_dev: float32
+ * [B][32][OH][OW], OH = (H - 8) / 4 + 1, OW = (W - 8) / 4 + 1 (floor: trailing input rows and columns are not read).  Per output element,
+ * with k = (c 8 + ky) 8 + kx and K = 64 Cn:
+ *     acc = 0;  for k = 0 .. K-1 ascending: acc = fmaf((float) x_k, w[co][k], acc);  y = fmaxf(fmaf(acc, scale, bias[co]), 0)
+ * in float32, bit for bit, whatever B is and wherever the image sits in the batch (scale: 1 / 255 for uint8 images).
+ *
+ * The backward call (at most TWO launches): with g = dy (y > 0),  dbias[co] = sum of g,  dweight[co][k] = scale * sum over (b, oy, ox) of
+ * g (float) x_k.  The sums are split over workgroups into partials in workspace_dev (the caller's, at least the size that
+ * tg_conv_stem_bwd_workspace (B, Cn, H, W) returns, in bytes; overwritten) and reduced in a fixed order without atomics: the same inputs give
+ * the same bits on every run.  dweight_dev: float32 [32][Cn][8][8]; dbias_dev: float32 [32]; both overwritten.
+ * B = 0 does nothing.  Errors, each without a launch: a NULL pointer, Cn outside [1, TG_STEM_MAX_CIN], H < 8 or W < 8, B < 0, more than
+ * 2^24 - 1 workgroups' worth of output (128 output positions each), a workspace that is too small (the size query returns the negative code). */
+#define TG_STEM_KERNEL 8
+#define TG_STEM_STRIDE 4
+#define TG_STEM_OUT 32
+#define TG_STEM_MAX_CIN 12
+int tg_conv_stem(const void* x_dev, int32_t x_is_float, int32_t channels_first, int64_t B, int32_t Cn, int32_t H, int32_t W,
+                 const float* weight_dev, const float* bias_dev, float scale, float* y_dev, void* hip_stream);
+int64_t tg_conv_stem_bwd_workspace(int64_t B, int32_t Cn, int32_t H, int32_t W);
+int tg_conv_stem_bwd(const void* x_dev, int32_t x_is_float, int32_t channels_first, int64_t B, int32_t Cn, int32_t H, int32_t W,
+                     const float* y_dev, const float* dy_dev, float scale, float* dweight_dev, float* dbias_dev, void* workspace_dev,
+                     int64_t workspace_bytes, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

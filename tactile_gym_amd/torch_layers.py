@@ -1,0 +1,185 @@
+"""stable_baselines3.common.torch_layers' NatureCNN with its first layer on the device conv stem (csrc/tg_conv_stem.hip: k_conv_stem,
+k_conv_stem_bwd).
+
+Every params file of the reference builds its policy with `CustomCombinedExtractor(cnn_base=NatureCNN)`; with `cnn_base=tg.NatureCNN` the
+same line builds this module.  Its first stage - SB3's preprocess_obs (obs.float() / 255), Conv2d(C, 32, kernel_size=8, stride=4), ReLU - is
+ONE launch that reads the uint8 image once and writes the activated float32 output once; everything after it stays on torch.  Each output
+element is one float32 fmaf chain over k = (c 8 + ky) 8 + kx ascending, then fmaxf(fmaf(acc, scale, bias), 0): an image's features do not
+depend on the batch it sits in, so PPO's first-epoch ratio exp(log_prob_new - log_prob_old) of a minibatch row is computed from the very bits
+the collection batch produced.  The input is data and gets no gradient; the backward pass is dweight and dbias, summed in a fixed order
+(the same bits on every run).
+
+What reaches the module, and the scale that goes with it:
+
+    uint8 images (collect.py's loops, buf.get(out_dtype=torch.uint8), rb.sample(...))   scale 1 / 255, always
+    float32 in [0, 1] (SB3's own preprocess_obs has divided already)                    float_scale=1 (the default)
+    float32 in 0 ... 255 (this project's buffers: get / sample with float32 output,     float_scale=1 / 255
+                          the augmentation's output)
+
+Device tensors run the HIP kernels on torch's current stream.  CPU tensors take a plain-torch path of the same meaning (F.conv2d on
+x.float() * scale, then relu) that is not bit-specified: SB3 can save, load and evaluate the module on the host.
+"""
+import ctypes as C
+
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _capi as capi
+from .vec_env import _optional_base
+
+__all__ = ["conv_stem", "ConvStem", "NatureCNN"]
+
+_U8_SCALE = float(np.float32(1.0) / np.float32(255.0))      # 1 / 255f
+_FeaturesBase = _optional_base("stable_baselines3.common.torch_layers", "BaseFeaturesExtractor")
+
+
+def _check_stem(x, weight, bias, channels_first):
+    """(Cn, H, W) of the batch x after augment._check_images' checks (a CPU tensor is allowed here) and the parameters' own."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"x must be a torch tensor, got {type(x).__name__}")
+    if x.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"x must be uint8 or float32, got {x.dtype}")
+    if x.dim() != 4:
+        raise ValueError(f"x must be a 4-D image batch, got shape {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous")
+    if x.requires_grad:
+        raise ValueError("x requires a gradient: the conv stem treats its input as data and computes none")
+    Cn, H, W = tuple(x.shape[1:]) if channels_first else (x.shape[3], x.shape[1], x.shape[2])
+    if not 1 <= Cn <= capi.STEM_MAX_CIN:
+        raise ValueError(f"x has {Cn} channels (channels_first={bool(channels_first)}): 1 to {capi.STEM_MAX_CIN} are built")
+    if H < capi.STEM_KERNEL or W < capi.STEM_KERNEL:
+        raise ValueError(f"x is {H} x {W}: the 8 x 8 kernel needs H, W >= 8")
+    for t, name, shape in ((weight, "weight", (capi.STEM_OUT, Cn, capi.STEM_KERNEL, capi.STEM_KERNEL)), (bias, "bias", (capi.STEM_OUT,))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise TypeError(f"{name} must be a float32 torch tensor")
+        if tuple(t.shape) != shape or t.device != x.device or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {list(shape)} tensor on x's device, got {list(t.shape)} on {t.device}")
+    return Cn, H, W
+
+
+def _out_hw(H, W):
+    return (H - capi.STEM_KERNEL) // capi.STEM_STRIDE + 1, (W - capi.STEM_KERNEL) // capi.STEM_STRIDE + 1
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+class _ConvStem(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, channels_first, scale):
+        B = x.shape[0]
+        Cn, H, W = tuple(x.shape[1:]) if channels_first else (x.shape[3], x.shape[1], x.shape[2])
+        y = torch.empty((B, capi.STEM_OUT) + _out_hw(H, W), dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            capi.check(capi.lib().tg_conv_stem(_ptr(x), int(x.dtype == torch.float32), int(channels_first), B, Cn, H, W, _ptr(weight.detach()),
+                                               _ptr(bias.detach()), scale, _ptr(y), C.c_void_p(stream)))
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:          # under no_grad, or with frozen parameters, nothing is kept
+            ctx.save_for_backward(x, y)
+            ctx.stem = (bool(channels_first), scale, Cn, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y = ctx.saved_tensors
+        channels_first, scale, Cn, H, W = ctx.stem
+        B = x.shape[0]
+        dy = dy.contiguous()
+        if dy.dtype != torch.float32:
+            raise TypeError(f"the output's gradient must be float32, got {dy.dtype}")
+        alloc = torch.empty if B else torch.zeros                         # B = 0 launches nothing: the gradients are zero
+        dweight = alloc((capi.STEM_OUT, Cn, capi.STEM_KERNEL, capi.STEM_KERNEL), dtype=torch.float32, device=x.device)
+        dbias = alloc((capi.STEM_OUT,), dtype=torch.float32, device=x.device)
+        L = capi.lib()
+        nbytes = L.tg_conv_stem_bwd_workspace(B, Cn, H, W)
+        if nbytes < 0:
+            capi.check(int(nbytes))
+        work = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            capi.check(L.tg_conv_stem_bwd(_ptr(x), int(x.dtype == torch.float32), int(channels_first), B, Cn, H, W, _ptr(y), _ptr(dy), scale,
+                                          _ptr(dweight), _ptr(dbias), _ptr(work), int(nbytes), C.c_void_p(stream)))
+        return None, dweight, dbias, None, None
+
+
+def conv_stem(x, weight, bias, channels_first=True, scale=None):
+    """relu(conv2d(x * scale, weight, bias, stride=4)) for the 8 x 8 kernel and 32 output channels of NatureCNN's first layer: float32
+    [B, 32, (H - 8) // 4 + 1, (W - 8) // 4 + 1] from x, a contiguous uint8 or float32 batch [B, C, H, W] (channels_first) or [B, H, W, C].
+    scale: None is 1 / 255 for uint8 and 1 for float32 (see the module's table).  Differentiable in weight and bias; x must not require a
+    gradient.  On the device: one launch forward, two backward, on torch's current stream.  On the CPU: plain torch, not bit-specified."""
+    Cn, H, W = _check_stem(x, weight, bias, channels_first)
+    if scale is None:
+        scale = _U8_SCALE if x.dtype == torch.uint8 else 1.0
+    scale = float(np.float32(scale))
+    if not x.is_cuda:
+        xf = x.float() * scale
+        return F.relu(F.conv2d(xf if channels_first else xf.permute(0, 3, 1, 2), weight, bias, stride=capi.STEM_STRIDE))
+    return _ConvStem.apply(x, weight, bias, bool(channels_first), scale)
+
+
+class ConvStem(nn.Module):
+    """NatureCNN's Conv2d(n_input_channels, 32, kernel_size=8, stride=4) with SB3's preprocessing in front and the ReLU behind it, as
+    `conv_stem`.  weight [32, C, 8, 8] and bias [32] are nn.Conv2d's parameters under nn.Conv2d's names and initialisation.  uint8 input is
+    scaled by 1 / 255, float32 input by float_scale."""
+
+    def __init__(self, n_input_channels, channels_first=True, float_scale=1.0):
+        super().__init__()
+        if not 1 <= int(n_input_channels) <= capi.STEM_MAX_CIN:
+            raise ValueError(f"n_input_channels={n_input_channels}: 1 to {capi.STEM_MAX_CIN} are built")
+        self.n_input_channels, self.channels_first, self.float_scale = int(n_input_channels), bool(channels_first), float(float_scale)
+        conv = nn.Conv2d(self.n_input_channels, capi.STEM_OUT, kernel_size=capi.STEM_KERNEL, stride=capi.STEM_STRIDE)
+        self.weight, self.bias = conv.weight, conv.bias
+
+    def forward(self, x):
+        return conv_stem(x, self.weight, self.bias, self.channels_first, _U8_SCALE if x.dtype == torch.uint8 else self.float_scale)
+
+    def extra_repr(self):
+        return f"{self.n_input_channels}, 32, kernel_size=8, stride=4, channels_first={self.channels_first}, float_scale={self.float_scale}"
+
+
+class NatureCNN(_FeaturesBase if _FeaturesBase is not object else nn.Module):
+    """stable_baselines3's NatureCNN (a BaseFeaturesExtractor subclass when SB3 is importable, the same surface where it is not) over an
+    image space: `cnn_base=tg.NatureCNN` in the reference's CustomCombinedExtractor.
+
+    cnn = Sequential(ConvStem, Identity, Conv2d(32, 64, 4, 2), ReLU, Conv2d(64, 64, 3, 1), ReLU, Flatten), linear = Sequential(Linear, ReLU):
+    the state_dict keys are SB3's (cnn.0, cnn.2, cnn.4, linear.0: the Identity stands where SB3 has the first ReLU), so a checkpoint loads
+    either way.  channels_first: the layout of the observations, [C, H, W] or [H, W, C] per sample; None applies SB3's rule as
+    DeviceRolloutBuffer does (the smallest of the three dimensions comes first).  normalized_image is accepted for SB3's signature.
+
+    Inputs (see the module's table): uint8 images are scaled by 1 / 255; float32 images that SB3's preprocess_obs has divided already need
+    float_scale=1 (the default), float32 images in 0 ... 255 from this project's buffers and augmentation need float_scale=1 / 255."""
+
+    def __init__(self, observation_space, features_dim=512, normalized_image=False, channels_first=None, float_scale=1.0):
+        shape = tuple(int(s) for s in observation_space.shape)
+        if len(shape) != 3:
+            raise ValueError(f"NatureCNN needs an image space [C, H, W] or [H, W, C], got shape {shape}")
+        if channels_first is not None and not isinstance(channels_first, (bool, np.bool_)):
+            raise ValueError(f"channels_first={channels_first!r}: True, False or None")
+        cf = bool(np.argmin(shape) == 0) if channels_first is None else bool(channels_first)
+        Cn, H, W = shape if cf else (shape[2], shape[0], shape[1])
+        if H < 36 or W < 36:
+            raise ValueError(f"NatureCNN's three convolutions need H, W >= 36, got {H} x {W} (channels_first={cf})")
+        if _FeaturesBase is not object:
+            super().__init__(observation_space, features_dim)
+        else:
+            super().__init__()
+            self._observation_space, self._features_dim = observation_space, int(features_dim)
+        h, w = _out_hw(H, W)
+        h, w = (h - 4) // 2 + 1, (w - 4) // 2 + 1
+        h, w = h - 2, w - 2
+        self.n_flatten = 64 * h * w
+        self.cnn = nn.Sequential(ConvStem(Cn, cf, float_scale), nn.Identity(), nn.Conv2d(32, 64, kernel_size=4, stride=2, padding=0), nn.ReLU(),
+                                 nn.Conv2d(64, 64, kernel_size=3, stride=1, padding=0), nn.ReLU(), nn.Flatten())
+        self.linear = nn.Sequential(nn.Linear(self.n_flatten, int(features_dim)), nn.ReLU())
+
+    if _FeaturesBase is object:
+        @property
+        def features_dim(self):
+            return self._features_dim
+
+    def forward(self, observations):
+        return self.linear(self.cnn(observations))
