@@ -502,7 +502,8 @@ int tg_set_scene(tg_ctx* ctx, const tg_scene* scene);
  * object_push_env.py:249): the guard checks per env step that no OTHER pair can touch - one oriented box per URDF link with <collision> geometry
  * (the robot's, the table, the plane, the stimulus, the free objects), world AABBs sorted and swept on x in the env's wavefront (stage 1: what
  * Bullet's broadphase would report), the pairs found narrowed by an oriented-box separating-axis test (stage 2) and, for a robot link against the
- * table, by the link's convex hull against the table top (stage 3).  Results per env in tg_state_view.broadphase_pairs / _hits / _mask; a
+ * table, by the world extents of the link's convex hull (every vertex; grown by hull_margin + margin) against the table's margin box (stage 3).  Two
+ * shapes within 2 * margin of each other at a check are always reported: every shape lies inside its box.  Results per env in tg_state_view.broadphase_pairs / _hits / _mask; a
  * non-zero hit count means PyBullet may generate a contact this library has no solver row for.
  * Slots: 0-15 the robot's boxes in URDF link order, 16 table, 17 plane, 18 edge stimulus, 19 / 20 the object's boxes, 21 the ball of
  * ball_on_plate.  src: where a slot's pose comes from - TG_BP_LINK the robot's moving link `link` (-1: the fixed base), TG_BP_WORLD none (center is
@@ -523,7 +524,7 @@ typedef struct {
 } tg_bp_box;
 typedef struct {
     tg_bp_box box[TG_BP_SLOTS];
-    double margin;                          /* added to every half extent: what a box travels inside one env step + contactBreakingThreshold */
+    double margin;                          /* added to every half extent: shapes within 2 * margin at a check are reported (what that covers inside a step) */
     double hull_margin;                     /* Bullet inflates a URDF convex hull by gUrdfDefaultCollisionMargin = 0.001 */
     double sphere_half;                     /* half extent of the TG_BP_SPHERE / TG_BP_BALL asset boxes (= the asset's radius) */
     double ball_radius;                     /* TG_BP_BALL: the ball's radius in the world */

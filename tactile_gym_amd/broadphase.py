@@ -24,8 +24,19 @@ import numpy as np
 from . import _capi as capi
 
 ASSETS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "collision")
-MARGIN = 0.0015          # per box: the distance a box travels inside one env step (<= 1 mm at the envs' action ranges) + contactBreakingThreshold 1e-4
+MARGIN = 0.0015          # per box (every hull vertex lies inside its link's box): two shapes within 2 * MARGIN = 3 mm of each other at a check are reported
 HULL_MARGIN = 0.001      # gUrdfDefaultCollisionMargin
+# What one check per env step says about the ticks between two checks.  Bullet makes a contact once two hulls are HULL_MARGIN +
+# contactBreakingThreshold (1e-4) = 1.1 mm apart; a pair that a check clears is more than 3 mm apart: a vertex may travel STEP_TRAVEL_BUDGET = 1.9 mm
+# per step before a contact can begin unseen.  STEP_TRAVEL: the largest travel of a robot hull vertex in one env step, measured on the CPU oracle at the
+# corners of each env family's action box (tests/test_broadphase_exact_cpu.py pins the figures to 10 %).  Six families stay inside the budget: a
+# clear check there covers the step's every tick.  The UR5 in surface_follow (xyzRxRy) and in object_push does not: there a clear check covers the
+# state it looked at and the ticks within 1.9 mm of travel of it; a contact that begins later in the step is reported by the NEXT step's check (the
+# link is then within 3 mm), one step late, and a graze that begins and ends between two checks is not seen.  Raising MARGIN would close that; it
+# would also move the guard's one finding (PARITY_ASSUMPTIONS A40) and is left for a change of its own.
+STEP_TRAVEL_BUDGET = 2 * MARGIN - HULL_MARGIN - 1e-4
+STEP_TRAVEL = {"edge_ur5": 0.00151, "edge_mg400": 0.00135, "surface_ur5_digit": 0.00323, "surface_v2_mg400": 0.00171, "push_mg400_digitac": 0.00170,
+               "push_ur5_tactip": 0.00230, "roll": 0.00152, "balance_pole": 0.00076}      # metres per env step
 TABLE, PLANE, STIM, OBJ_A, OBJ_B, BALL = 16, 17, 18, 19, 20, 21
 BODY_ROBOT, BODY_TABLE, BODY_PLANE, BODY_STIM, BODY_OBJ, BODY_BALL = range(6)
 

@@ -8,8 +8,11 @@
 //   2. sort by the AABBs' lower x bound: rank = number of boxes that come before (ties by slot index) - 22 compares per lane, no exchange network;
 //   3. sweep: lane k walks the boxes behind it in that order while their lower x bound is not past its upper one; y / z intervals, then the pair
 //      rules (different bodies, not both static, not an expected pair) - a pair that passes is what Bullet's broadphase would hand on (stage 1);
-//      then the oriented-box separating-axis test (stage 2) and, for a robot link against the table, the link's convex hull against the table top
-//      (stage 3: a box bounds a round link loosely - the UR5's upper arm is a 6 cm cylinder about its joint, its box's corners reach 2.5 cm further);
+//      then the oriented-box separating-axis test (stage 2) and, for a robot link against the table, the world extents of the link's convex hull
+//      against the table's margin box (stage 3: a box bounds a round link loosely - the UR5's upper arm is a 6 cm cylinder about its joint, its box's
+//      corners reach 2.5 cm further).  Every hull lies inside its box (a mesh link's box is its vertices' box grown by the 1 mm collision margin, as
+//      btCollisionShape::getAabb grows it; a box-shaped link's is exact): two shapes within 2 * margin of each other overlap in stages 1 and 2 by
+//      construction, and stage 3 is three more separating-axis tests over every hull vertex, so it clears no such pair either;
 //   4. wave reduction of (pairs, hits, mask of slots in hits) -> tg_state_view.broadphase_*; hits also go to the context's totals.
 // HBM traffic: the env's joint angles and object pose in, three int32 out; the scene (8 KB) and the hull vertices (< 100 KB) are L2 resident.
 #include "tg_broadphase.h"
@@ -167,28 +170,37 @@ __global__ __launch_bounds__(64) void k_broadphase(const DevRobot<T>* __restrict
     if (pairs) atomicAdd(&acc[0], pairs);
     if (hits) { atomicAdd(&acc[1], hits); atomicOr(&acc[2], (int)mask); }
     __syncthreads();
-    // stage 3: a robot link whose BOX reaches the table - its convex hull decides (lowest vertex over the table top, less the hull's collision margin
-    // and the guard's).  The lanes share a candidate's vertices (a sensor tip's hull has 1089), the minimum is a wave reduction; min is exact in any order.
+    // stage 3: a robot link whose BOX reaches the table - its convex hull decides: three separating-axis tests (x, y, z), each over ALL of the hull's
+    // vertices - the hull's world extents, grown by the hull's collision margin and the guard's, against the table's margin box (all of its faces: a
+    // link past the table's edge, across a corner or against a side face from below the top counts like one that comes down on the top).  The lanes
+    // share a candidate's vertices (a sensor tip's hull has 1089), the six extents are wave reductions; min and max are exact in any order.
     for (int k = 0; k < n_cand; ++k) {
         const int rl = cand[k];
         const tg_bp_box& rb = sc.box[rl];
         const double* tb = bx[sc.table_slot];
         const double* F = fr[rb.link >= 0 ? rb.link : 0];
-        double zmin = 1e300;
+        double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
         for (int v = lane; v < rb.hull_n; v += 64) {
             const double* hv = sc.hull + 3 * (size_t)(rb.hull_off + v);
-            double wx = hv[0], wy = hv[1], wz = hv[2];
+            double w[3] = {hv[0], hv[1], hv[2]};
             if (rb.link >= 0) {
-                wx = (F[0] * hv[0] + F[1] * hv[1] + F[2] * hv[2]) + F[9];
-                wy = (F[3] * hv[0] + F[4] * hv[1] + F[5] * hv[2]) + F[10];
-                wz = (F[6] * hv[0] + F[7] * hv[1] + F[8] * hv[2]) + F[11];
+                w[0] = (F[0] * hv[0] + F[1] * hv[1] + F[2] * hv[2]) + F[9];
+                w[1] = (F[3] * hv[0] + F[4] * hv[1] + F[5] * hv[2]) + F[10];
+                w[2] = (F[6] * hv[0] + F[7] * hv[1] + F[8] * hv[2]) + F[11];
             }
-            if (wx >= tb[0] && wx <= tb[3] && wy >= tb[1] && wy <= tb[4] && wz < zmin) zmin = wz;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { lo[i] = w[i] < lo[i] ? w[i] : lo[i]; hi[i] = w[i] > hi[i] ? w[i] : hi[i]; }
         }
-        for (int o = 1; o < 64; o <<= 1) { const double other = __shfl_xor(zmin, o); zmin = other < zmin ? other : zmin; }
-        if (lane == 0 && zmin < 1e299 && (zmin - sc.hull_margin) - sc.margin <= tb[5]) {
-            acc[1] += 1; acc[2] |= (1 << rl) | (1 << sc.table_slot);
+        bool reach = true;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            for (int o = 1; o < 64; o <<= 1) {
+                const double l = __shfl_xor(lo[i], o), h = __shfl_xor(hi[i], o);
+                lo[i] = l < lo[i] ? l : lo[i]; hi[i] = h > hi[i] ? h : hi[i];
+            }
+            reach = reach && (lo[i] - sc.hull_margin) - sc.margin <= tb[3 + i] && (hi[i] + sc.hull_margin) + sc.margin >= tb[i];
         }
+        if (lane == 0 && reach) { acc[1] += 1; acc[2] |= (1 << rl) | (1 << sc.table_slot); }
     }
     __syncthreads();
     if (lane == 0) {
