@@ -796,6 +796,53 @@ int64_t tg_conv_stem_bwd_workspace(int64_t B, int32_t Cn, int32_t H, int32_t W);
 int tg_conv_stem_bwd(const void* x_dev, int32_t x_is_float, int32_t channels_first, int64_t B, int32_t Cn, int32_t H, int32_t W,
                      const float* y_dev, const float* dy_dev, float scale, float* dweight_dev, float* dbias_dev, void* workspace_dev,
                      int64_t workspace_bytes, void* hip_stream);
+
+/* ---- device loss heads: what stable_baselines3 does between the network's output and the scalar loss ---------------------------
+ * Context free; the launches go to hip_stream, nothing is allocated or synchronised.  Float32 arithmetic with one rounding per operation; exp,
+ * tanh and log are evaluated in double on the float32 argument and rounded once.  Every sum over rows is taken in double and rounded to float32
+ * once: rows in chunks of 256 consecutive rows, a fixed lane tree inside a chunk, the chunk sums added in ascending order, no atomics - the same
+ * inputs give the same bits on every run and on both paths.
+ *
+ * tg_ppo_loss: PPO.train from evaluate_actions to `loss`.  mean_dev, actions_dev: float32 [B][A]; log_std_dev: [A] (log_std_stride 0) or [B][A]
+ * (log_std_stride A), not clamped; values_dev, old_log_prob_dev, advantages_dev, returns_dev: [B]; old_values_dev: [B], needed when
+ * clip_range_vf >= 0 (negative: no value clip).  Per row, with d = actions - mean and sigma = (float) exp(log_std):
+ *     log_prob = sum_j (-d^2 / (2 sigma^2) - log_std - log sqrt(2 pi))       tg_action_head's TG_HEAD_GAUSSIAN chain: its bits on its own sample
+ *     entropy  = sum_j (1.4189385332046727f + log_std)
+ *     adv      = (advantages - adv_mean) / (adv_std + 1e-8f) when normalize_advantage != 0 and B > 1 (the unbiased std), else advantages
+ *     ratio    = (float) exp(log_prob - old_log_prob);   surrogate = min(adv ratio, adv clamp(ratio, 1 - clip_range, 1 + clip_range))
+ *     values_pred = values, or old_values + clamp(values - old_values, -clip_range_vf, clip_range_vf)
+ * stats_out, float32 [8]: loss = policy_loss + ent_coef entropy_loss + vf_coef value_loss, policy_loss = -mean(surrogate), value_loss =
+ * mean((returns - values_pred)^2), entropy_loss = -mean(entropy), approx_kl = mean((ratio - 1) - (log_prob - old_log_prob)), clip_fraction =
+ * mean(|ratio - 1| > clip_range), adv_mean, adv_std (0 and 1 when the advantages are not normalised).  Nullable: log_prob_out [B] and the
+ * gradients of loss by torch autograd's rules, dmean_out [B][A], dlog_std_out ([A], summed over rows in the chunk order, or [B][A]) and
+ * dvalues_out [B]; advantages, returns, old values and old log-probs are data.  path: TG_LOSS_PATH_ONE, one workgroup and one launch
+ * (B <= TG_LOSS_ONE_MAX_ROWS); TG_LOSS_PATH_GRID, three launches with the chunk sums in workspace_dev (the caller's, at least the bytes that
+ * tg_ppo_loss_workspace (B, A) returns; overwritten); TG_LOSS_PATH_AUTO, the first where it applies.
+ * Errors, each without a launch: a NULL input or stats_out, A outside [1, TG_HEAD_MAX_ACT], a stride other than 0 or A, B < 1, clip_range < 0
+ * or a NaN, clip_range_vf >= 0 without old_values_dev, an unknown path, TG_LOSS_PATH_ONE with too many rows, a workspace that is missing or
+ * too small on the grid path (the size query returns the negative code).
+ *
+ * tg_squashed_rsample: SAC's actor.action_log_prob, TG_HEAD_SQUASHED's arithmetic at (seed, counter) (noise_in_dev as there): actions_out
+ * [B][A] and log_prob_out [B], and for the backward pass (nullable) eps_out and sigma_out [B][A].  tg_squashed_rsample_bwd: from
+ * g_actions_dev [B][A] and g_log_prob_dev [B] (each nullable: zero), the saved actions, eps, sigma and the forward's log_std_dev, with
+ * w = (1 - a^2) + 1e-6f and s = g_a (1 - a^2) + g_lp 2 a (1 - a^2) / w:  dmean_out = s,  dlog_std_out = (s sigma eps - g_lp) m, both
+ * [B][A] and nullable, m = 1 where log_std lies in [log_std_min, log_std_max] (inclusive, torch.clamp's rule) and 0 elsewhere.  One launch each. */
+#define TG_LOSS_PATH_AUTO 0
+#define TG_LOSS_PATH_ONE 1
+#define TG_LOSS_PATH_GRID 2
+#define TG_LOSS_ONE_MAX_ROWS 4096
+int64_t tg_ppo_loss_workspace(int64_t B, int32_t A);
+int tg_ppo_loss(const float* mean_dev, const float* log_std_dev, int32_t log_std_stride, const float* values_dev, const float* actions_dev,
+                const float* old_log_prob_dev, const float* advantages_dev, const float* returns_dev, const float* old_values_dev, int64_t B,
+                int32_t A, float clip_range, float clip_range_vf, float ent_coef, float vf_coef, int32_t normalize_advantage, int32_t path,
+                float* stats_out, float* log_prob_out, float* dmean_out, float* dlog_std_out, float* dvalues_out, void* workspace_dev,
+                int64_t workspace_bytes, void* hip_stream);
+int tg_squashed_rsample(const float* mean_dev, const float* log_std_dev, int32_t log_std_stride, int64_t B, int32_t A, float log_std_min,
+                        float log_std_max, uint64_t seed, uint64_t counter, const float* noise_in_dev, float* actions_out, float* log_prob_out,
+                        float* eps_out, float* sigma_out, void* hip_stream);
+int tg_squashed_rsample_bwd(const float* g_actions_dev, const float* g_log_prob_dev, const float* actions_dev, const float* eps_dev,
+                            const float* sigma_dev, const float* log_std_dev, int32_t log_std_stride, int64_t B, int32_t A, float log_std_min,
+                            float log_std_max, float* dmean_out, float* dlog_std_out, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

@@ -19,6 +19,8 @@ loudly when the HIP library or a GPU is missing.
     actions, env_actions, log_prob = head.sample(mean, log_std)   # tg.DeviceSquashedDiagGaussian: SAC's tanh head and its uniform warm-up
     obs, starts = tg.collect.collect_rollouts(venv, policy, buf, head, n_steps, obs, starts)   # SB3's two collection loops over the device pieces
     obs, num_timesteps = tg.collect.collect_transitions(venv, actor, rb, head, n_steps, num_timesteps, learning_starts, obs)
+    loss, stats = tg.ppo_loss(mean, log_std, values, b.actions, b.old_log_prob, b.advantages, b.returns)   # PPO.train's loss and its gradients in one launch (tg.loss_head); head.rsample: SAC's
+    stats = tg.train.ppo_train(policy, optimizer, buf, n_epochs, 64, 0.2, None, 0.0, 0.5, 0.5, None)      # PPO.train over the device pieces
     CustomCombinedExtractor(observation_space, cnn_base=tg.NatureCNN)   # SB3's NatureCNN, its first layer one launch on the uint8 images (tg.torch_layers; imports torch)
 """
 from . import rl_envs  # noqa: F401  (registers the env ids)
@@ -29,7 +31,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("augment", "rollout", "replay", "vecnorm", "action_head", "collect", "torch_layers"):   # imported on first use: they need torch, the rest of the package does not
+    if name in ("augment", "rollout", "replay", "vecnorm", "action_head", "collect", "torch_layers", "loss_head", "train"):   # imported on first use: they need torch, the rest of the package does not
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "DeviceRolloutBuffer":
@@ -44,6 +46,9 @@ def __getattr__(name):
     if name in ("DeviceDiagGaussian", "DeviceSquashedDiagGaussian"):
         import importlib
         return getattr(importlib.import_module(".action_head", __name__), name)
+    if name == "ppo_loss":
+        import importlib
+        return importlib.import_module(".loss_head", __name__).ppo_loss
     if name in ("NatureCNN", "ConvStem", "conv_stem"):
         import importlib
         return getattr(importlib.import_module(".torch_layers", __name__), name)

@@ -164,3 +164,15 @@ class DeviceSquashedDiagGaussian(_DeviceHead):
         self._c_head(capi.HEAD_UNIFORM, None, None, 0, False)
         self.counter += 1
         return self.actions, self.env_actions
+
+    def rsample(self, mean, log_std, noise=None):
+        """(actions, log_prob): SAC.train's actor.action_log_prob(obs) - sample()'s arithmetic at the head's next (seed, counter), as FRESH
+        tensors [B, A] and [B] that carry gradients to mean and log_std (loss_head.squashed_rsample), for any B >= 1: the
+        minibatch, not the env batch.  The counter moves on by one.  Under torch.no_grad() (SAC's next actions) nothing is saved.  noise:
+        float32 [B, A] used in place of the draws."""
+        from .loss_head import squashed_rsample
+        if self.device is not None and isinstance(mean, torch.Tensor) and mean.is_cuda and mean.device != self.device:
+            raise ValueError(f"mean must be on the head's device {self.device}, got {mean.device}")
+        out = squashed_rsample(mean, log_std, self.log_std_min, self.log_std_max, self.seed, self.counter, noise)
+        self.counter += 1
+        return out

@@ -13,7 +13,7 @@
 
 #include "../../include/tactile_gym_hip.h"
 #include "tg_exchange.h"   // report_error
-#include "tg_kernels.hpp"  // counter_draw: tg_sample_actions' counter-based generator
+#include "tg_head_core.h"  // the draw and the per-element chains, shared with tg_loss_head.hip
 
 namespace tg {
 
@@ -37,20 +37,6 @@ struct HeadArgs {
     float lo[TG_HEAD_MAX_ACT];
     float hi[TG_HEAD_MAX_ACT];
 };
-
-// The 24 random bits of element e of draw `counter`: tg_sample_actions' integers.
-__device__ __forceinline__ uint32_t head_bits24(uint64_t seed, uint64_t counter, uint64_t e) {
-    return (uint32_t)(counter_draw(seed, counter, e) >> 40);
-}
-
-// Box-Muller on elements 2 e and 2 e + 1, all in double: u1 in (0, 1], u2 in [0, 1); |result| <= sqrt(-2 ln 2^-24) = 5.768
-__device__ __forceinline__ float head_normal(uint64_t seed, uint64_t counter, uint64_t e) {
-    const double u1 = (double)(head_bits24(seed, counter, 2 * e) + 1u) * (1.0 / 16777216.0);
-    const double u2 = (double)head_bits24(seed, counter, 2 * e + 1) * (1.0 / 16777216.0);
-    const double r = sqrt(-2.0 * log(u1));
-    const double c = cos(6.283185307179586 * u2);
-    return (float)(r * c);
-}
 
 template <int MODE>
 __global__ __launch_bounds__(kHeadThreads) void k_action_head(HeadArgs a) {
@@ -82,8 +68,8 @@ __global__ __launch_bounds__(kHeadThreads) void k_action_head(HeadArgs a) {
         const int64_t e = i * A + j;
         const float mean = a.mean[e];
         float ls = a.log_std[a.ls_stride ? e : (int64_t)j];
-        ls = ls < a.ls_min ? a.ls_min : (ls > a.ls_max ? a.ls_max : ls);          // a NaN passes, as torch.clamp
-        const float sigma = (float)exp((double)ls);
+        ls = head_clamp(ls, a.ls_min, a.ls_max);                                   // a NaN passes, as torch.clamp
+        const float sigma = head_sigma(ls);
         const float eps = a.noise_in ? a.noise_in[e] : (a.deterministic ? 0.0f : head_normal(a.seed, a.counter, (uint64_t)e));
         const float se = sigma * eps;
         const float x = mean + se;
@@ -91,12 +77,7 @@ __global__ __launch_bounds__(kHeadThreads) void k_action_head(HeadArgs a) {
         if (a.gauss) a.gauss[e] = x;
         // torch's Normal.log_prob with log_std for log(exp(log_std)): -(x - mean)^2 / (2 sigma^2) - log_std - log sqrt(2 pi)
         const float d = x - mean;
-        const float q = d * d;
-        const float var = sigma * sigma;
-        const float den = 2.0f * var;
-        const float t = q / den;
-        const float t1 = -t - ls;
-        const float term = t1 - 0.9189385332046727f;
+        const float term = head_gaussian_term(d, sigma, ls);
         gsum = gsum + term;
         if (MODE == TG_HEAD_GAUSSIAN) {
             if (a.actions) a.actions[e] = x;
@@ -106,7 +87,7 @@ __global__ __launch_bounds__(kHeadThreads) void k_action_head(HeadArgs a) {
                 a.env[e] = up > hi ? hi : up;
             }
         } else {
-            const float act = (float)tanh((double)x);
+            const float act = head_tanh(x);
             if (a.actions) a.actions[e] = act;
             if (a.env) {                                          // SB3's unscale_action: lo + (0.5 (a + 1) (hi - lo))
                 const float lo = a.lo[j], hi = a.hi[j];
@@ -118,10 +99,7 @@ __global__ __launch_bounds__(kHeadThreads) void k_action_head(HeadArgs a) {
                 const float up = un < lo ? lo : un;               // at a = +-1 the formula can leave [lo, hi] by one rounding when hi - lo
                 a.env[e] = up > hi ? hi : up;                     // is inexact: the env is never handed an action outside its space
             }
-            const float aa = act * act;
-            const float om = 1.0f - aa;
-            const float w = om + 1e-6f;
-            const float c = (float)log((double)w);
+            const float c = head_squash_term(act);                // log(1 - a^2 + 1e-6)
             csum = csum + c;
         }
     }

@@ -1,0 +1,166 @@
+"""Loss heads in device memory: what stable_baselines3 does between the network's output and the scalar loss, with the gradients at the head's
+inputs (csrc/tg_loss_head.hip).
+
+    mean, log_std, values = policy(batch.observations)                                   # PPO.train, per minibatch
+    loss, stats = tg.ppo_loss(mean, log_std, values, batch.actions, batch.old_log_prob, batch.advantages, batch.returns,
+                              old_values=batch.old_values, clip_range=0.2, clip_range_vf=None, ent_coef=0.0, vf_coef=0.5)
+    loss.backward()                                                                      # one launch made loss and gradients (B <= 4096)
+
+    actions, log_prob = head.rsample(mean, log_std)                                      # SAC.train: actor.action_log_prob(obs), tg.DeviceSquashedDiagGaussian
+    actor_loss = (ent_coef * log_prob - q(obs, actions)).mean()
+
+`stats` is a float32 device tensor [8]: loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, adv_mean, adv_std; nothing here
+reads it.  The gradients are the fused ones of the kernel (torch autograd's rules written out), scaled by the incoming gradient; advantages,
+returns, old values and old log-probs are data and get none.  The arithmetic is restated in tests/loss_head_ref.py.  There is no CPU path.
+"""
+import ctypes as C
+
+import torch
+
+from . import _capi as capi
+
+__all__ = ["ppo_loss", "squashed_rsample", "STATS"]
+
+STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
+
+
+def _checked(x, name, shapes, device=None):
+    """What the action heads refuse (action_head._checked); the tensor itself comes back, with its autograd history."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name} must be a torch tensor, got {type(x).__name__}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32, got {x.dtype}")
+    if tuple(x.shape) not in shapes:
+        raise ValueError(f"{name} must have shape {' or '.join(str(s) for s in shapes)}, got {tuple(x.shape)}")
+    if not x.is_cuda:
+        raise ValueError(f"{name} must be on the ROCm device (there is no CPU path), got {x.device}")
+    if device is not None and x.device != device:
+        raise ValueError(f"{name} must be on the device {device}, got {x.device}")
+    if not x.is_contiguous():
+        raise ValueError(f"{name} must be contiguous (a copy would be a launch and a temporary of its own)")
+    return x
+
+
+def _ptr(t):
+    return C.c_void_p(None if t is None else t.data_ptr())
+
+
+class _PpoLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, log_std, values, actions, old_log_prob, advantages, returns, old_values, clip_range, clip_range_vf, ent_coef, vf_coef,
+                normalize_advantage, path):
+        B, A = mean.shape
+        need = ctx.needs_input_grad[:3]
+        f32 = dict(dtype=torch.float32, device=mean.device)
+        stats = torch.empty(8, **f32)
+        dmean = torch.empty_like(mean) if need[0] else None
+        dls = torch.empty_like(log_std) if need[1] else None
+        dvalues = torch.empty_like(values) if need[2] else None
+        grid = path == capi.LOSS_PATH_GRID or (path == capi.LOSS_PATH_AUTO and B > capi.LOSS_ONE_MAX_ROWS)
+        nbytes = capi.lib().tg_ppo_loss_workspace(B, A) if grid else 0
+        if nbytes < 0:
+            capi.check(int(nbytes))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=mean.device) if grid else None
+        with torch.cuda.device(mean.device):
+            stream = torch.cuda.current_stream(mean.device).cuda_stream
+            capi.check(capi.lib().tg_ppo_loss(_ptr(mean), _ptr(log_std), 0 if log_std.dim() == 1 else A, _ptr(values), _ptr(actions),
+                                              _ptr(old_log_prob), _ptr(advantages), _ptr(returns), _ptr(old_values), B, A, clip_range,
+                                              clip_range_vf, ent_coef, vf_coef, 1 if normalize_advantage else 0, path, _ptr(stats), _ptr(None),
+                                              _ptr(dmean), _ptr(dls), _ptr(dvalues), _ptr(work), nbytes, C.c_void_p(stream)))
+        ctx.grads = (dmean, dls, dvalues)
+        ctx.mark_non_differentiable(stats)
+        return stats[0], stats
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_stats):
+        kept = [g for g in ctx.grads if g is not None]
+        scaled = iter(torch._foreach_mul(kept, g_loss) if kept else ())      # one launch for the (up to) three products
+        return tuple(None if g is None else next(scaled) for g in ctx.grads) + (None,) * 11
+
+
+def ppo_loss(mean, log_std, values, actions, old_log_prob, advantages, returns, old_values=None, clip_range=0.2, clip_range_vf=None, ent_coef=0.0,
+             vf_coef=0.5, normalize_advantage=True, path=capi.LOSS_PATH_AUTO):
+    """(loss, stats): stable_baselines3's PPO.train from evaluate_actions to `loss` on a minibatch.  mean, actions: float32 [B, A]; log_std: [A]
+    (PPO's parameter) or [B, A]; values, old_log_prob, advantages, returns, old_values: [B] ([B, 1] is refused: flatten, as SB3 does); all
+    contiguous device tensors (anything else is refused, not copied).  loss: a 0-dim float32 tensor with gradients for mean, log_std and
+    values; stats: float32 [8] (STATS), on the device.  clip_range_vf=None: no value clip (old_values is then not read).  The advantages are
+    normalised only when B > 1, as in SB3.  path: capi.LOSS_PATH_* (tests)."""
+    if not isinstance(mean, torch.Tensor):
+        raise TypeError(f"mean must be a torch tensor, got {type(mean).__name__}")
+    B, A = (int(mean.shape[0]), int(mean.shape[1])) if mean.dim() == 2 else (-1, -1)
+    mean = _checked(mean, "mean", [(B, A)])
+    if B < 1 or not 1 <= A <= capi.HEAD_MAX_ACT:
+        raise ValueError(f"mean must be [B, A] with B >= 1 and 1 <= A <= {capi.HEAD_MAX_ACT}, got {tuple(mean.shape)}")
+    dev = mean.device
+    log_std = _checked(log_std, "log_std", [(A,), (B, A)], dev)
+    values = _checked(values, "values", [(B,)], dev)
+    actions = _checked(actions, "actions", [(B, A)], dev).detach()
+    old_log_prob = _checked(old_log_prob, "old_log_prob", [(B,)], dev).detach()
+    advantages = _checked(advantages, "advantages", [(B,)], dev).detach()
+    returns = _checked(returns, "returns", [(B,)], dev).detach()
+    if clip_range_vf is not None:
+        if old_values is None:
+            raise ValueError("clip_range_vf needs old_values")
+        if not clip_range_vf >= 0:
+            raise ValueError(f"clip_range_vf must be None or >= 0, got {clip_range_vf}")
+        old_values = _checked(old_values, "old_values", [(B,)], dev).detach()
+    else:
+        old_values = None
+    if not clip_range >= 0:
+        raise ValueError(f"clip_range must be >= 0, got {clip_range}")
+    return _PpoLoss.apply(mean, log_std, values, actions, old_log_prob, advantages, returns, old_values, float(clip_range),
+                          -1.0 if clip_range_vf is None else float(clip_range_vf), float(ent_coef), float(vf_coef), bool(normalize_advantage),
+                          int(path))
+
+
+class _SquashedRsample(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mean, log_std, ls_min, ls_max, seed, counter, noise):
+        B, A = mean.shape
+        stride = 0 if log_std.dim() == 1 else A
+        save = any(ctx.needs_input_grad[:2])          # under torch.no_grad() nothing needs a gradient: nothing is saved
+        actions, log_prob = torch.empty_like(mean), torch.empty(B, dtype=torch.float32, device=mean.device)
+        eps = torch.empty_like(mean) if save else None
+        sigma = torch.empty_like(mean) if save else None
+        with torch.cuda.device(mean.device):
+            stream = torch.cuda.current_stream(mean.device).cuda_stream
+            capi.check(capi.lib().tg_squashed_rsample(_ptr(mean), _ptr(log_std), stride, B, A, ls_min, ls_max, seed, counter, _ptr(noise),
+                                                      _ptr(actions), _ptr(log_prob), _ptr(eps), _ptr(sigma), C.c_void_p(stream)))
+        if save:
+            ctx.save_for_backward(actions, eps, sigma, log_std)
+            ctx.clamp = (ls_min, ls_max)
+        return actions, log_prob
+
+    @staticmethod
+    def backward(ctx, g_a, g_lp):
+        actions, eps, sigma, log_std = ctx.saved_tensors
+        B, A = actions.shape
+        g_a = None if g_a is None else g_a.contiguous()
+        g_lp = None if g_lp is None else g_lp.contiguous()
+        need_mean, need_ls = ctx.needs_input_grad[:2]
+        dmean = torch.empty_like(actions) if need_mean else None
+        dls = torch.empty_like(actions) if need_ls else None
+        with torch.cuda.device(actions.device):
+            stream = torch.cuda.current_stream(actions.device).cuda_stream
+            capi.check(capi.lib().tg_squashed_rsample_bwd(_ptr(g_a), _ptr(g_lp), _ptr(actions), _ptr(eps), _ptr(sigma), _ptr(log_std),
+                                                          0 if log_std.dim() == 1 else A, B, A, ctx.clamp[0], ctx.clamp[1], _ptr(dmean), _ptr(dls),
+                                                          C.c_void_p(stream)))
+        if dls is not None and log_std.dim() == 1:
+            dls = dls.sum(dim=0)                      # a state-independent log_std [A] (not SAC's): the rows' sum, on torch
+        return dmean, dls, None, None, None, None, None
+
+
+def squashed_rsample(mean, log_std, log_std_min=-20.0, log_std_max=2.0, seed=0, counter=0, noise=None):
+    """(actions, log_prob): SAC's actor.action_log_prob - DeviceSquashedDiagGaussian.sample's arithmetic at (seed, counter) as fresh tensors
+    [B, A] and [B] that carry gradients to mean [B, A] and log_std ([B, A] or [A]), for any B >= 1.  noise: float32 [B, A] used in place of the
+    draws.  DeviceSquashedDiagGaussian.rsample calls this with the head's clamp, seed and next counter."""
+    if not isinstance(mean, torch.Tensor):
+        raise TypeError(f"mean must be a torch tensor, got {type(mean).__name__}")
+    B, A = (int(mean.shape[0]), int(mean.shape[1])) if mean.dim() == 2 else (-1, -1)
+    mean = _checked(mean, "mean", [(B, A)])
+    if B < 1 or not 1 <= A <= capi.HEAD_MAX_ACT:
+        raise ValueError(f"mean must be [B, A] with B >= 1 and 1 <= A <= {capi.HEAD_MAX_ACT}, got {tuple(mean.shape)}")
+    log_std = _checked(log_std, "log_std", [(A,), (B, A)], mean.device)
+    if noise is not None:
+        noise = _checked(noise, "noise", [(B, A)], mean.device).detach()
+    return _SquashedRsample.apply(mean, log_std, float(log_std_min), float(log_std_max), int(seed), int(counter), noise)
