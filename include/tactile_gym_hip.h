@@ -843,6 +843,38 @@ int tg_squashed_rsample(const float* mean_dev, const float* log_std_dev, int32_t
 int tg_squashed_rsample_bwd(const float* g_actions_dev, const float* g_log_prob_dev, const float* actions_dev, const float* eps_dev,
                             const float* sigma_dev, const float* log_std_dev, int32_t log_std_stride, int64_t B, int32_t A, float log_std_min,
                             float log_std_max, float* dmean_out, float* dlog_std_out, void* hip_stream);
+
+/* ---- SAC's device losses: SAC.train between the networks' outputs and its scalar losses ----------------------------------------
+ * Context free; one launch each on hip_stream, nothing is allocated or synchronised.  The arithmetic rules of the loss heads above: float32 with
+ * one rounding per operation in the order written, exp in double on the float32 argument and rounded once, every mean over rows accumulated in
+ * double in the chunk order (256 consecutive rows, the lane tree, the wave sums in wave order, the chunks ascending) and rounded once, no
+ * atomics.  One workgroup walks the chunks for every 1 <= B <= TG_SAC_MAX_ROWS.  The critics' outputs are n_critics separate float32 [B]
+ * device arrays (1 <= n_critics <= TG_SAC_MAX_CRITICS), named by HOST arrays of n_critics device pointers, read before the call returns.
+ * alpha, the entropy coefficient: (float) exp((double) *log_ent_coef_dev) where log_ent_coef_dev (a float32 device scalar) is given, else the
+ * argument ent_coef.  alpha is data in both losses (SB3 detaches it).
+ *
+ * tg_sac_critic_loss.  Per row: m = fminf chain over q_next_i, i ascending;  y = m - alpha next_log_prob;  target = rewards +
+ * ((1 - dones) gamma) y;  e_i = q_cur_i - target.  mse_i = (float) (sum_b (double) (e_i e_i) / B);  critic_loss = 0.5f (((0 + mse_0) +
+ * mse_1) + ...).  stats_out, float32 [8]: critic_loss, ent_coef (alpha), target_q_mean, min_next_q_mean, mse_0 .. mse_3 (0 beyond n_critics).
+ * Nullable: target_out [B];  dq_cur_out, a host array of n_critics device pointers, each nullable: dq_cur_i [B] = e_i / (float) B, the
+ * gradient of critic_loss.  The target, rewards, dones and the target networks' outputs are data.
+ *
+ * tg_sac_actor_loss.  Per row: m = min_i q_pi_i, k the lowest index that attains it;  a = alpha log_prob - m;  c = log_prob + target_entropy.
+ * actor_loss = (float) (sum a / B);  with want_ent_coef_loss != 0 (log_ent_coef_dev is then required) ent_coef_loss = -(float) (sum (double)
+ * (log_ent_coef c) / B) and dlog_ent_coef = -(float) (sum c / B).  stats_out, float32 [8]: actor_loss, ent_coef_loss, ent_coef (alpha),
+ * log_prob_mean, min_q_pi_mean, dlog_ent_coef, 0, 0 (ent_coef_loss and dlog_ent_coef 0 when not asked).  Nullable, for an upstream gradient
+ * of 1: dlog_prob_out [B] = alpha / (float) B;  dq_pi_out, a host array of n_critics device pointers, each nullable: dq_pi_i [B] =
+ * -1 / (float) B where i == k, else 0 (torch.min(dim)'s rule).
+ * Errors, each without a launch: n_critics or B out of range, a NULL input, pointer array, critic output or stats_out, the entropy-coefficient
+ * loss asked without log_ent_coef_dev. */
+#define TG_SAC_MAX_CRITICS 4
+#define TG_SAC_MAX_ROWS 65536
+int tg_sac_critic_loss(const float* const* q_cur_dev, const float* const* q_next_dev, int32_t n_critics, const float* next_log_prob_dev,
+                       const float* rewards_dev, const float* dones_dev, int64_t B, float gamma, const float* log_ent_coef_dev, float ent_coef,
+                       float* stats_out, float* target_out, float* const* dq_cur_out, void* hip_stream);
+int tg_sac_actor_loss(const float* log_prob_dev, const float* const* q_pi_dev, int32_t n_critics, int64_t B, const float* log_ent_coef_dev,
+                      float ent_coef, float target_entropy, int32_t want_ent_coef_loss, float* stats_out, float* dlog_prob_out,
+                      float* const* dq_pi_out, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

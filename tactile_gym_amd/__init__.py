@@ -21,6 +21,9 @@ loudly when the HIP library or a GPU is missing.
     obs, num_timesteps = tg.collect.collect_transitions(venv, actor, rb, head, n_steps, num_timesteps, learning_starts, obs)
     loss, stats = tg.ppo_loss(mean, log_std, values, b.actions, b.old_log_prob, b.advantages, b.returns)   # PPO.train's loss and its gradients in one launch (tg.loss_head); head.rsample: SAC's
     stats = tg.train.ppo_train(policy, optimizer, buf, n_epochs, 64, 0.2, None, 0.0, 0.5, 0.5, None)      # PPO.train over the device pieces
+    critic_loss, stats = tg.sac_critic_loss(q_cur, q_next, next_log_prob, b.rewards, b.dones, gamma, log_ent_coef=log_ent_coef)   # SAC.train's TD target and critic loss, one launch
+    actor_loss, ent_coef_loss, stats = tg.sac_actor_loss(log_prob, q_pi, log_ent_coef=log_ent_coef, target_entropy=-A)              # its actor and entropy-coefficient losses, one launch
+    critic_stats, actor_stats, n_updates = tg.train.sac_train(actor, critic, critic_target, actor_opt, critic_opt, rb, head, 1, 64, 0.95, 0.005, log_ent_coef=log_ent_coef, ent_coef_optimizer=ent_opt, target_entropy=-A)   # SAC.train over the device pieces
     CustomCombinedExtractor(observation_space, cnn_base=tg.NatureCNN)   # SB3's NatureCNN, its first layer one launch on the uint8 images (tg.torch_layers; imports torch)
 """
 from . import rl_envs  # noqa: F401  (registers the env ids)
@@ -46,9 +49,9 @@ def __getattr__(name):
     if name in ("DeviceDiagGaussian", "DeviceSquashedDiagGaussian"):
         import importlib
         return getattr(importlib.import_module(".action_head", __name__), name)
-    if name == "ppo_loss":
+    if name in ("ppo_loss", "sac_critic_loss", "sac_actor_loss"):
         import importlib
-        return importlib.import_module(".loss_head", __name__).ppo_loss
+        return getattr(importlib.import_module(".loss_head", __name__), name)
     if name in ("NatureCNN", "ConvStem", "conv_stem"):
         import importlib
         return getattr(importlib.import_module(".torch_layers", __name__), name)

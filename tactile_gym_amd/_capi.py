@@ -36,6 +36,7 @@ ROLLOUT_DONES = {"uint8": 0, "float32": 1}   # TG_ROLLOUT_DONES_* (tg_rollout_ga
 VECNORM_MAX_ARRAYS, VECNORM_MAX_WIDTH, VECNORM_MAX_ROWS = 4, 512, 65535   # TG_VECNORM_* (tg_vecnorm_update, tg_vecnorm_apply)
 HEAD_GAUSSIAN, HEAD_SQUASHED, HEAD_UNIFORM, HEAD_MAX_ACT = 0, 1, 2, 16   # TG_HEAD_* (tg_action_head)
 LOSS_PATH_AUTO, LOSS_PATH_ONE, LOSS_PATH_GRID, LOSS_ONE_MAX_ROWS = 0, 1, 2, 4096   # TG_LOSS_* (tg_ppo_loss)
+SAC_MAX_CRITICS, SAC_MAX_ROWS = 4, 65536   # TG_SAC_* (tg_sac_critic_loss, tg_sac_actor_loss)
 STEM_KERNEL, STEM_STRIDE, STEM_OUT, STEM_MAX_CIN = 8, 4, 32, 12   # TG_STEM_* (tg_conv_stem, tg_conv_stem_bwd)
 OBS_STACK_KEY = dict(OBS_KEY, visual=3)   # + TG_OBS_KEY_VISUAL (ABI v16: the scene camera's images)
 NARROWPHASE = {"closed_form": 0, "gjk_manifold": 1, "gjk_single": 2}
@@ -267,6 +268,10 @@ SYMBOLS = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tg_squashed_rsample_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tg_sac_critic_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p,
+                                     C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tg_sac_actor_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "tg_get_state": (C.c_int, [_ctx, C.POINTER(TgStateView)]),
     "tg_set_joint_state": (C.c_int, [_ctx, _dp, _dp]),
     "tg_copy_step_licence": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),

@@ -5,7 +5,7 @@
 //   tg_squashed_rsample_bwd  its backward pass
 // Compiled with -ffp-contract=off: float32 arithmetic with one rounding per operation in the order written below, which tests/loss_head_ref.py
 // (device_order) restates; exp, tanh and log are evaluated in double on the float32 argument and rounded once.  Every sum over rows is taken in
-// double: rows in chunks of 256 consecutive rows (one row per lane), inside a chunk the shuffle tree of chunk_sums below (offsets 32 .. 1 inside
+// double: rows in chunks of 256 consecutive rows (one row per lane), inside a chunk the shuffle tree of tg_loss_core.h (offsets 32 .. 1 inside
 // each wave, then the four wave sums in wave order), the chunk sums added in ascending order.  No atomics: the same inputs give the same bits.
 //
 //   k_ppo_one      one workgroup: advantage statistics, every chunk in turn, the finish.  B <= 4096 (path 1).
@@ -19,11 +19,10 @@
 #include "../../include/tactile_gym_hip.h"
 #include "tg_exchange.h"   // report_error
 #include "tg_head_core.h"  // the draw and the per-element chains, shared with tg_action_head.hip
+#include "tg_loss_core.h"  // the chunk and its sum (wave_sum, slot_put, slot_get), shared with tg_sac_loss.hip
 
 namespace tg {
 
-constexpr int kLossThreads = 256;                 // the chunk
-constexpr int kLossWaves = kLossThreads / 64;
 constexpr int kLossStats = 5;                     // slots 0 .. 4: the surrogate, the value loss, the entropy, the KL term, the clip indicator
 constexpr int kLossSlots = kLossStats + TG_HEAD_MAX_ACT;   // slots 5 .. 5 + A - 1: the columns of dlog_std [A]
 constexpr int kLossHeadBytes = 16;                // the workspace's head: adv_mean, adv_std (float32), then padding
@@ -50,22 +49,6 @@ struct PpoArgs {
     int32_t normalize;          // already 0 when B == 1
     float clip, clip_vf, ent_coef, vf_coef;
 };
-
-// Lane 0 of each wave: the sum of the wave's 64 values by the tree v[i] += v[i + off], off = 32, 16, 8, 4, 2, 1.
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off >= 1; off >>= 1) v = v + __shfl_down(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ void slot_put(double* lds, int slot, double v) {
-    const double s = wave_sum(v);
-    if ((threadIdx.x & 63) == 0) lds[slot * kLossWaves + (threadIdx.x >> 6)] = s;
-}
-
-// The sum that thread `slot` owns, after a barrier: the wave sums in wave order.
-__device__ __forceinline__ double slot_get(const double* lds, int slot) {
-    return ((lds[slot * kLossWaves] + lds[slot * kLossWaves + 1]) + lds[slot * kLossWaves + 2]) + lds[slot * kLossWaves + 3];
-}
 
 // One value per row summed over all rows, chunk by chunk, by the whole workgroup: every thread returns the total.
 template <typename F>

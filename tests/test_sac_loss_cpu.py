@@ -1,0 +1,376 @@
+"""SAC's device losses without a GPU (tactile_gym_amd.loss_head.sac_critic_loss / sac_actor_loss, tactile_gym_amd.train.polyak_update; DESIGN.md
+4.16): at the shapes the GPU tests use, torch's own float32 composition and the numpy restatement of the kernels (tests/sac_loss_ref.py) stay
+inside every derived bound against the float64 composition; each usual mistake, put into the float64 formula, lands outside by the factor
+measured here (asserted with a margin of two); the input conditions are asserted; polyak_update gives SB3's bits; sac_train's loop on fake pieces gives SB3's own order's bits; the C ABI entries, the build
+line and the kernels' resources."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+sys.path.insert(0, HERE)
+sys.path.insert(0, ROOT)
+import sac_loss_ref as ref  # noqa: E402
+
+from tactile_gym_amd import _capi  # noqa: E402
+
+BOUND_ENTRY = _capi.SYMBOLS["tg_sac_critic_loss"]            # at import: the whole file needs the feature
+torch = pytest.importorskip("torch")
+
+ROWS = (1, 2, 63, 64, 65, 255, 256, 257, 1000, 4097)         # tests/test_gpu_sac_loss_abi.py's shapes
+CRITICS = (1, 2, 3, 4)
+GAMMA, TARGET_ENTROPY = 0.95, -2.0
+CRITIC_KEYS = ("critic_loss", "ent_coef", "target_q_mean", "min_next_q_mean", "mse", "target", "dq_cur")
+ACTOR_KEYS = ("actor_loss", "ent_coef_loss", "ent_coef", "log_prob_mean", "min_q_pi_mean", "dlog_ent_coef", "dlog_prob", "dq_pi")
+
+
+def alpha_sources(B, n):
+    """Both sources of alpha at every shape: a learnt log_ent_coef (its value moves with the shape) and SB3's fixed coefficient."""
+    return (dict(log_ent_coef=-1.5 + 0.25 * n + 0.001 * (B % 7)), dict(ent_coef=0.2))
+
+
+def worst(got, ex, bounds, names):
+    """name -> worst error / bound over every element (no row is left out); an error of 0 counts as 0 whatever the bound."""
+    out = {}
+    for k in names:
+        err = np.abs(np.asarray(got[k], np.float64) - ex[k])
+        b = np.broadcast_to(bounds[k], err.shape)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out[k] = float(np.max(np.where(err == 0, 0.0, err / b)))
+    return out
+
+
+@pytest.mark.parametrize("n", CRITICS)
+@pytest.mark.parametrize("B", ROWS)
+def test_float32_compositions_stay_within_the_bounds_of_float64(B, n):
+    """torch's own float32 ops (its means accumulate in float32, its autograd rounds more often: acc=U, autograd32) and the kernels' order in
+    numpy (double accumulators)."""
+    for src in alpha_sources(B, n):
+        inp = ref.sac_critic_inputs(B, n, seed=100 * B + n)
+        assert ref.critics_apart(inp["q_next"])
+        ex = ref.sac_critic_exact(**inp, gamma=GAMMA, **src)
+        w32 = worst(ref.sac_critic_exact(**inp, gamma=GAMMA, **src, dtype=torch.float32), ex,
+                    ref.sac_critic_bounds(ex, **inp, gamma=GAMMA, **src, acc=ref.U, autograd32=True), CRITIC_KEYS)
+        wdev = worst(ref.critic_named(ref.sac_critic_device_order(**inp, gamma=GAMMA, **src), n), ex,
+                     ref.sac_critic_bounds(ex, **inp, gamma=GAMMA, **src), CRITIC_KEYS)
+        print(f"critic B={B} n={n} {src}: torch float32 {max(w32.values()):.3f} ({max(w32, key=w32.get)}), device order "
+              f"{max(wdev.values()):.3f} ({max(wdev, key=wdev.get)}) of the bound")
+        assert max(w32.values()) <= 1.0, w32
+        assert max(wdev.values()) <= 1.0, wdev
+        done = inp["dones"] == 1
+        assert np.array_equal(ex["target"][done], inp["rewards"][done].astype(np.float64))
+        act = ref.sac_actor_inputs(B, n, seed=100 * B + n + 50)
+        assert ref.critics_apart(act["q_pi"])
+        for te in ((TARGET_ENTROPY, None) if "log_ent_coef" in src else (None,)):
+            kw = dict(src, target_entropy=te)
+            ex = ref.sac_actor_exact(**act, **kw)
+            w32 = worst(ref.sac_actor_exact(**act, **kw, dtype=torch.float32), ex, ref.sac_actor_bounds(ex, **act, **kw, acc=ref.U, autograd32=True),
+                        ACTOR_KEYS)
+            wdev = worst(ref.actor_named(ref.sac_actor_device_order(**act, **kw)), ex, ref.sac_actor_bounds(ex, **act, **kw), ACTOR_KEYS)
+            print(f"actor B={B} n={n} {kw}: torch float32 {max(w32.values()):.3f} ({max(w32, key=w32.get)}), device order "
+                  f"{max(wdev.values()):.3f} ({max(wdev, key=wdev.get)}) of the bound")
+            assert max(w32.values()) <= 1.0, w32
+            assert max(wdev.values()) <= 1.0, wdev
+            assert (ex["dq_pi"] != 0).sum() == B and np.allclose(ex["dq_pi"].sum(axis=0), -1.0 / B)      # one critic per row takes the gradient
+            if te is None:
+                assert ex["ent_coef_loss"] == 0 and ex["dlog_ent_coef"] == 0
+
+
+def test_the_input_makers_move_near_ties_apart_and_keep_every_row():
+    a = np.array([0.0, 1.0, 2.0, 3.0], np.float32)
+    qs = ref._apart([a.copy(), (a + np.float32(5e-5)).copy(), a.copy()])
+    assert ref.critics_apart(qs) and all(q.shape == (4,) for q in qs)
+    assert not ref.critics_apart([a, a + np.float32(5e-5)])
+    for B in (1, 2, 64):
+        inp = ref.sac_critic_inputs(B, 2, seed=B)
+        assert all(v.shape == (B,) for v in inp["q_cur"] + inp["q_next"] + [inp["next_log_prob"], inp["rewards"], inp["dones"]])
+        if B >= 2:
+            assert set(inp["dones"].tolist()) == {0.0, 1.0}
+
+
+# ---------------------------------------------------------------------------------------------------------------- the usual mistakes
+# name -> (the quantity that shows it, the worst error / bound measured here at B = 64, n_critics = 2); half of it is asserted
+MEASURED = {
+    "max for min": ("target", 65540000.0),
+    "(1 - dones) left out": ("target", 2388000000.0),
+    "entropy sign in the target": ("target", 9078000.0),
+    "gamma on the reward": ("target", 838900.0),
+    "0.5 left out": ("critic_loss", 2227000.0),
+    "mse as a sum": ("critic_loss", 140300000.0),
+    "min passes gradient to every critic": ("dq_pi", 16780000.0),
+    "alpha not detached": ("dlog_ent_coef", 735600.0),
+    "target_entropy sign": ("dlog_ent_coef", 11630000.0),
+    "ent_coef_loss not negated": ("ent_coef_loss", 10950000.0),
+}
+MISTAKE_ALPHA = dict(log_ent_coef=-1.2)
+
+
+@pytest.mark.parametrize("name", sorted(MEASURED))
+def test_usual_sac_mistakes_break_the_bound(name):
+    key, measured = MEASURED[name]
+    assert name in ref.CRITIC_MISTAKES + ref.ACTOR_MISTAKES
+    if name in ref.CRITIC_MISTAKES:
+        inp = ref.sac_critic_inputs(64, 2, seed=64)
+        ex = ref.sac_critic_exact(**inp, gamma=GAMMA, **MISTAKE_ALPHA)
+        bounds = ref.sac_critic_bounds(ex, **inp, gamma=GAMMA, **MISTAKE_ALPHA)
+        bad = ref.sac_critic_exact(**inp, gamma=GAMMA, **MISTAKE_ALPHA, mistake=name)
+    else:
+        inp = ref.sac_actor_inputs(64, 2, seed=65)
+        kw = dict(MISTAKE_ALPHA, target_entropy=TARGET_ENTROPY)
+        ex = ref.sac_actor_exact(**inp, **kw)
+        bounds = ref.sac_actor_bounds(ex, **inp, **kw)
+        bad = ref.sac_actor_exact(**inp, **kw, mistake=name)
+    ratio = worst(bad, ex, bounds, (key,))[key]
+    print(f"{name}: {key} lands {ratio:.4g} x its bound outside (measured {measured:.4g}, asserted {measured / 2:.4g})")
+    assert ratio > measured / 2 > 1
+
+
+# ---------------------------------------------------------------------------------------------------------------- polyak_update
+def _sb3_polyak(params, target_params, tau):
+    """stable_baselines3.common.utils.polyak_update's loop."""
+    with torch.no_grad():
+        for param, target_param in zip(params, target_params):
+            target_param.data.mul_(1 - tau)
+            torch.add(target_param.data, param.data, alpha=tau, out=target_param.data)
+
+
+@pytest.mark.parametrize("tau", [0.005, 1.0])
+def test_polyak_update_gives_sb3s_bits_on_cpu_tensors(tau):
+    from tactile_gym_amd import train
+    gen = torch.Generator().manual_seed(7)
+    shapes = [(32, 3, 8, 8), (32,), (0,), (256, 18), (1,), (7, 5)]
+    params = [torch.randn(s, generator=gen) for s in shapes]
+    targets = [torch.randn(s, generator=gen) for s in shapes]
+    kept, want = [p.clone() for p in params], [t.clone() for t in targets]
+    _sb3_polyak(params, want, tau)
+    train.polyak_update(params, targets, tau)
+    for p, k, t, w in zip(params, kept, targets, want):
+        assert torch.equal(p, k) and t.shape == w.shape
+        assert np.array_equal(t.numpy().view(np.uint32), w.numpy().view(np.uint32))
+    if tau == 1.0:
+        assert all(torch.equal(t, p) for t, p in zip(targets, params))
+    with pytest.raises(ValueError, match="polyak_update"):
+        train.polyak_update(params, targets[:-1], tau)
+    train.polyak_update([], [], tau)                                          # no batch-norm statistics: nothing to do
+
+
+def test_polyak_update_takes_parameters_with_gradients():
+    from tactile_gym_amd import train
+    a, b = torch.nn.Linear(3, 2), torch.nn.Linear(3, 2)
+    want = [0.75 * t.detach() + 0.25 * p.detach() for p, t in zip(a.parameters(), b.parameters())]
+    train.polyak_update(a.parameters(), b.parameters(), 0.25)
+    assert all(torch.allclose(t, w) for t, w in zip(b.parameters(), want)) and all(t.requires_grad for t in b.parameters())
+
+
+# ---------------------------------------------------------------------------------------------------------------- sac_train's loop on fake pieces
+class _FakeCritics(torch.nn.Module):
+    """Two linear critics on cat(obs, actions) -> (q_0 [B, 1], q_1 [B, 1]); keeps what every call was given."""
+
+    def __init__(self):
+        super().__init__()
+        self.q = torch.nn.ModuleList([torch.nn.Linear(5, 1) for _ in range(2)])
+        self.seen = []
+
+    def forward(self, obs, actions):
+        self.seen.append((obs, actions, torch.is_grad_enabled()))
+        x = torch.cat([obs, actions], dim=1)
+        return tuple(q(x) for q in self.q)
+
+
+class _FakeActor(torch.nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.out, self.seen = torch.nn.Linear(3, 4), []
+
+    def forward(self, obs):
+        self.seen.append(obs)
+        o = self.out(obs)
+        return o[:, :2], o[:, 2:] - 1.0
+
+
+class _FakeHead:
+    """A squashed Gaussian in torch ops with the noise of call k given; keeps each call's outputs and grad mode."""
+
+    def __init__(self, noises):
+        self.noises, self.calls = noises, []
+
+    def rsample(self, mean, log_std):
+        z = self.noises[len(self.calls)]
+        a = torch.tanh(mean + log_std.exp() * z)
+        log_prob = (-0.5 * z * z - log_std).sum(dim=1) - torch.log(1 - a ** 2 + 1e-6).sum(dim=1)
+        self.calls.append((a, log_prob, torch.is_grad_enabled()))
+        return a, log_prob
+
+
+def _torch_critic_loss(q_cur, q_next, next_log_prob, rewards, dones, gamma, log_ent_coef=None, ent_coef=None):
+    """SB3's lines, in place of tg.sac_critic_loss."""
+    alpha = torch.exp(log_ent_coef.detach()) if log_ent_coef is not None else torch.tensor(ent_coef)
+    with torch.no_grad():
+        next_q = torch.min(torch.cat(q_next, dim=1), dim=1, keepdim=True)[0] - alpha * next_log_prob.reshape(-1, 1)
+        target = rewards + (1 - dones) * gamma * next_q
+    loss = 0.5 * sum(torch.nn.functional.mse_loss(q, target) for q in q_cur)
+    return loss, torch.zeros(8)
+
+
+def _torch_actor_loss(log_prob, q_pi, log_ent_coef=None, ent_coef=None, target_entropy=None):
+    alpha = torch.exp(log_ent_coef.detach()) if log_ent_coef is not None else torch.tensor(ent_coef)
+    log_prob = log_prob.reshape(-1, 1)
+    ent_loss = None if target_entropy is None else -(log_ent_coef * (log_prob + target_entropy).detach()).mean()
+    actor_loss = (alpha * log_prob - torch.min(torch.cat(q_pi, dim=1), dim=1, keepdim=True)[0]).mean()
+    return actor_loss, ent_loss, torch.zeros(8)
+
+
+@pytest.mark.parametrize("learn_ent", [True, False])
+def test_sac_train_is_sb3s_loop_on_fake_pieces(monkeypatch, learn_ent):
+    """The loop alone on CPU tensors, with the two fused losses replaced by SB3's lines in torch: what each network is called on, in which
+    order and grad mode, what the buffer and the losses are handed, and - three gradient steps with target_update_interval = 2 - every
+    parameter bit-equal to SB3's own order (the entropy step first, two backward passes, the per-tensor polyak loop) on deep copies."""
+    import copy
+
+    from tactile_gym_amd import train
+    from tactile_gym_amd.replay import ReplayBufferSamples
+    torch.manual_seed(3)
+    B, STEPS, GAMMA_, TAU, TE = 6, 3, 0.9, 0.25, -2.0
+    batches = [ReplayBufferSamples(torch.randn(B, 3), torch.rand(B, 2) * 2 - 1, torch.randn(B, 3), (torch.rand(B, 1) < 0.3).float(), torch.randn(B, 1))
+               for _ in range(STEPS)]
+    noises = [torch.randn(B, 2) for _ in range(2 * STEPS)]
+
+    class Buf:
+        asked = []
+
+        def sample(self, batch_size, **kw):
+            self.asked.append((batch_size, kw))
+            return batches[len(self.asked) - 1]
+
+    actor, critic, target = _FakeActor(), _FakeCritics(), _FakeCritics()
+    twins = [copy.deepcopy(m) for m in (actor, critic, target)]
+    target_before = [p.detach().clone() for p in target.parameters()]
+    lec = torch.tensor([0.3], requires_grad=True)
+    lec2 = lec.detach().clone().requires_grad_()
+    adam = lambda p: torch.optim.Adam(p, lr=1e-2)   # noqa: E731
+    opts = [adam(actor.parameters()), adam(critic.parameters()), adam([lec])]
+    opts2 = [adam(twins[0].parameters()), adam(twins[1].parameters()), adam([lec2])]
+    handed = []
+    monkeypatch.setattr(train, "sac_critic_loss", lambda *a, **kw: (handed.append(("critic", a, kw)), _torch_critic_loss(*a, **kw))[1])
+    monkeypatch.setattr(train, "sac_actor_loss", lambda *a, **kw: (handed.append(("actor", a, kw)), _torch_actor_loss(*a, **kw))[1])
+    head, buf = _FakeHead(noises), Buf()
+    ent = dict(log_ent_coef=lec, ent_coef_optimizer=opts[2], target_entropy=TE) if learn_ent else dict(ent_coef=0.2)
+    cstats, astats, n_updates = train.sac_train(actor, critic, target, opts[0], opts[1], buf, head, STEPS, B, GAMMA_, TAU, target_update_interval=2,
+                                                n_updates=1, augment="aug", env="vn", **ent)
+    assert n_updates == 1 + STEPS and cstats.shape == (8,) and astats.shape == (8,)
+    assert buf.asked == [(B, dict(env="vn", augment="aug", out_dtype=torch.float32))] * STEPS
+    alpha_kw = dict(log_ent_coef=lec) if learn_ent else dict(ent_coef=0.2)
+    for k, b in enumerate(batches):                                           # what every piece was called on, step by step
+        (a_pi, lp, grad_pi), (a_next, lp_next, grad_next) = head.calls[2 * k], head.calls[2 * k + 1]
+        assert grad_pi and not grad_next and lp.requires_grad and not lp_next.requires_grad           # SB3's draw order: actions_pi first
+        assert actor.seen[2 * k] is b.observations and actor.seen[2 * k + 1] is b.next_observations
+        assert target.seen[k][0] is b.next_observations and target.seen[k][1] is a_next and not target.seen[k][2]
+        assert critic.seen[2 * k][0] is b.observations and critic.seen[2 * k][1] is b.actions and critic.seen[2 * k][2]
+        assert critic.seen[2 * k + 1][0] is b.observations and critic.seen[2 * k + 1][1] is a_pi
+        (kind_c, args_c, kw_c), (kind_a, args_a, kw_a) = handed[2 * k], handed[2 * k + 1]
+        assert kind_c == "critic" and kind_a == "actor"
+        assert len(args_c) == 6 and len(args_c[0]) == 2 and len(args_c[1]) == 2 and not any(q.requires_grad for q in args_c[1])
+        assert args_c[2] is lp_next and args_c[3] is b.rewards and args_c[4] is b.dones and args_c[5] == GAMMA_
+        assert set(kw_c) == set(alpha_kw) and all(kw_c[key] is alpha_kw[key] or kw_c[key] == alpha_kw[key] for key in alpha_kw)
+        assert args_a[0] is lp and len(args_a[1]) == 2 and kw_a == dict(alpha_kw, target_entropy=TE if learn_ent else None)
+    assert len(actor.seen) == 2 * STEPS and len(critic.seen) == 2 * STEPS and len(target.seen) == STEPS
+    # SB3's own order on the copies
+    for k, b in enumerate(batches):
+        a2, c2, t2 = twins
+        mean, log_std = a2(b.observations)
+        actions_pi, log_prob = _FakeHead([noises[2 * k]]).rsample(mean, log_std)
+        log_prob = log_prob.reshape(-1, 1)
+        if learn_ent:
+            ent_coef = torch.exp(lec2.detach())
+            ent_coef_loss = -(lec2 * (log_prob + TE).detach()).mean()
+            opts2[2].zero_grad()
+            ent_coef_loss.backward()
+            opts2[2].step()
+        else:
+            ent_coef = torch.tensor(0.2)
+        with torch.no_grad():
+            next_actions, next_log_prob = _FakeHead([noises[2 * k + 1]]).rsample(*a2(b.next_observations))
+            next_q = torch.min(torch.cat(t2(b.next_observations, next_actions), dim=1), dim=1, keepdim=True)[0]
+            target_q = b.rewards + (1 - b.dones) * GAMMA_ * (next_q - ent_coef * next_log_prob.reshape(-1, 1))
+        critic_loss = 0.5 * sum(torch.nn.functional.mse_loss(q, target_q) for q in c2(b.observations, b.actions))
+        opts2[1].zero_grad()
+        critic_loss.backward()
+        opts2[1].step()
+        min_q = torch.min(torch.cat(c2(b.observations, actions_pi), dim=1), dim=1, keepdim=True)[0]
+        actor_loss = (ent_coef * log_prob - min_q).mean()
+        opts2[0].zero_grad()
+        actor_loss.backward()
+        opts2[0].step()
+        if (2 + k) % 2 == 0:                                                  # n_updates started at 1
+            _sb3_polyak(list(c2.parameters()), list(t2.parameters()), TAU)
+    for ours, theirs in zip((actor, critic, target), twins):
+        for p, q in zip(ours.parameters(), theirs.parameters()):
+            assert np.array_equal(p.detach().numpy().view(np.uint32), q.detach().numpy().view(np.uint32))
+    assert np.array_equal(lec.detach().numpy().view(np.uint32), lec2.detach().numpy().view(np.uint32))
+    assert (lec.detach() != 0.3).all() == learn_ent
+    assert all(not torch.equal(p, q) for p, q in zip(target.parameters(), target_before))          # the polyak updates happened
+
+
+# ---------------------------------------------------------------------------------------------------------------- C ABI, exports, resources
+def test_c_abi_entries_are_declared_bound_and_built():
+    header = open(os.path.join(ROOT, "include", "tactile_gym_hip.h")).read()
+    assert re.search(r"#define TG_ABI_VERSION 16\b", header) and _capi.ABI_VERSION == 16      # only functions were added
+    nm = subprocess.run(["nm", "-D", "--defined-only", _capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    for name, n_args in (("tg_sac_critic_loss", 14), ("tg_sac_actor_loss", 12)):
+        decl = re.search(rf"\bint {name}\s*\(([^;]*)\);", header).group(1)
+        assert len(decl.split(",")) == n_args == len(_capi.SYMBOLS[name][1]), name
+        assert re.search(rf"\bT {name}\b", nm), name
+    for name, value in (("MAX_CRITICS", 4), ("MAX_ROWS", 65536)):
+        assert re.search(rf"#define TG_SAC_{name} {value}\b", header) and getattr(_capi, "SAC_" + name) == value
+    build = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", "build.sh")).read()
+    assert "cc tg_sac_loss -ffp-contract=off" in build and "$OUT/tg_sac_loss.o" in build and "fast-math" not in build
+    for unit in ("tg_loss_head.hip", "tg_sac_loss.hip"):                      # one copy of the chunk sum, in the header both include
+        text = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", unit)).read()
+        assert '#include "tg_loss_core.h"' in text and "__shfl_down(" not in text and not re.search(r"atomic\w*\s*\(", text)
+    assert open(os.path.join(ROOT, "tactile_gym_amd", "csrc", "tg_loss_core.h")).read().count("__shfl_down(") == 1
+
+
+def test_python_entries_are_exported_and_refuse_cpu_tensors():
+    import tactile_gym_amd as tg
+    from tactile_gym_amd import loss_head, train
+    assert tg.sac_critic_loss is loss_head.sac_critic_loss and tg.sac_actor_loss is loss_head.sac_actor_loss
+    assert callable(train.sac_train) and callable(train.polyak_update)
+    assert loss_head.SAC_CRITIC_STATS == ref.CRITIC_STATS and loss_head.SAC_ACTOR_STATS == ref.ACTOR_STATS
+    z = torch.zeros
+    with pytest.raises(ValueError, match="ROCm device"):
+        tg.sac_critic_loss((z(4), z(4)), (z(4), z(4)), z(4), z(4), z(4), 0.95, ent_coef=0.2)
+    with pytest.raises(ValueError, match="ROCm device"):
+        tg.sac_actor_loss(z(4), (z(4), z(4)), ent_coef=0.2)
+    with pytest.raises(ValueError, match="float32"):
+        tg.sac_actor_loss(z(4).double(), (z(4),), ent_coef=0.2)
+    with pytest.raises(TypeError):
+        tg.sac_critic_loss(z(4), (z(4),), z(4), z(4), z(4), 0.95, ent_coef=0.2)          # one tensor is not a tuple of tensors
+    with pytest.raises(ValueError, match="sac_train|exactly one"):
+        train.sac_train(None, None, None, None, None, None, None, 1, 4, 0.95, 0.005)
+
+
+def test_sac_loss_kernels_use_no_scratch_and_a_few_wave_sums_of_lds(tmp_path):
+    from test_kstep_quad_resources_cpu import LIB, _kernel_scratch, _tool
+    if not os.path.exists(LIB):
+        pytest.skip("library not built")
+    scratch = _kernel_scratch(tmp_path)
+    ours = {k: v for k, v in scratch.items() if "k_sac_" in k}
+    assert len(ours) == 2, sorted(ours)                                       # k_sac_critic, k_sac_actor
+    assert all(v == 0 for v in ours.values()), ours
+    lds = {}
+    for co in tmp_path.glob("b*.co"):                                         # the code objects _kernel_scratch unbundled
+        notes = subprocess.run([_tool("llvm-readelf"), "--notes", str(co)], capture_output=True, text=True, check=True).stdout
+        for block in re.split(r"\n\s*- \.", notes):
+            name, size = re.search(r"\.name:\s+(\S+)", block), re.search(r"\.group_segment_fixed_size:\s+(\d+)", block)
+            if name and size and "k_sac_" in name.group(1):
+                lds[name.group(1)] = int(size.group(1))
+    # slots x 4 wave sums x 8 bytes: the critic's 4 squared errors, target and min; the actor's 5 row sums
+    assert sorted(lds.values()) == [5 * 4 * 8, 6 * 4 * 8], lds
+    assert [v for k, v in lds.items() if "k_sac_critic" in k] == [192]
+    ppo = {k: v for k, v in scratch.items() if "k_ppo_" in k}                 # PPO's kernels, now over the shared header
+    assert len(ppo) == 4 and all(v == 0 for v in ppo.values()), ppo
