@@ -875,6 +875,60 @@ int tg_sac_critic_loss(const float* const* q_cur_dev, const float* const* q_next
 int tg_sac_actor_loss(const float* log_prob_dev, const float* const* q_pi_dev, int32_t n_critics, int64_t B, const float* log_ent_coef_dev,
                       float ent_coef, float target_entropy, int32_t want_ent_coef_loss, float* stats_out, float* dlog_prob_out,
                       float* const* dq_pi_out, void* hip_stream);
+
+/* ---- device MLP towers: stable_baselines3's policy, value and critic heads -----------------------------------------------------
+ * Context free; the launches go to hip_stream, nothing is allocated or synchronised.  A tower is a chain of n_layers layers (1 ..
+ * TG_MLP_MAX_LAYERS):  z_l = h_{l-1} W_l^T + b_l,  h_l = act_l(z_l),  W_l torch's float32 [out][in], every out in 1 .. TG_MLP_MAX_WIDTH.  A call
+ * runs T towers (1 .. TG_MLP_MAX_TOWERS) on ONE input of B rows given as two column blocks x0_dev [B][Ka] and x1_dev [B][Kb] (Kb = 0: one block,
+ * x1_dev is not read), K0 = Ka + Kb in 1 .. TG_MLP_MAX_IN.  A tower's LAST layer may have a second row block (weight2, bias2, out2 rows, out +
+ * out2 <= TG_MLP_MAX_WIDTH) whose outputs and gradients go to buffers of their own (h2, dweight2, dbias2).  Per output element, in float32:
+ *     acc = 0;  for k = 0 .. in-1 ascending: acc = fmaf(h_{l-1}[row][k], W_l[co][k], acc);  z = acc + b_l[co]
+ *     TG_MLP_ACT_NONE: h = z;  TG_MLP_ACT_RELU: h = fmaxf(z, 0);  TG_MLP_ACT_TANH: h = (float) tanh((double) z)
+ * bit for bit: an output depends on its own row only, whatever B is, wherever the row sits and whatever other towers the call runs.
+ * tg_mlp_forward (ONE launch) writes every layer's h [B][out] when save_all != 0 (the backward pass reads them), else only each tower's last.
+ *
+ * tg_mlp_backward (at most TWO launches): dh_L = dy (dy2 for the second block; NULL: zeros); for l = L .. 1:  g_l = dh_l act'(h_l)  (Tanh:
+ * t = h h, u = 1 - t, g = dh u, one rounding each; ReLU: h > 0; none: 1);  dbias_l[co] = sum over rows of g_l;  dweight_l[co][k] = sum over
+ * rows of g_l[row][co] h_{l-1}[row][k];  dh_{l-1}[row][k] = the fmaf chain over co ascending of g_l[row][co] W_l[co][k];  dx = the towers'
+ * dh_0 added in tower order, split into dx0_dev [B][Ka] and dx1_dev [B][Kb], each nullable (both NULL: not computed).  Every dweight / dbias
+ * pointer is nullable (not written).  The sums over rows run over tiles of 32 rows in ascending order without atomics, split over at most 64
+ * workgroups per tower whose partials lie in workspace_dev (the caller's, at least tg_mlp_backward_workspace's bytes, which may be 0 - then
+ * workspace_dev may be NULL; overwritten) and are added in ascending order: the same inputs give the same bits on every call.
+ * B = 0 does nothing.  Errors, each without a launch and without a write: a NULL required pointer, T, n_layers, a width or K0 out of range,
+ * in_l != out_{l-1} (in_1 != K0), a second row block on a layer that is not the last, an unknown activation, B < 0 or above TG_MLP_MAX_ROWS,
+ * a workspace that is too small (the size query returns the negative code). */
+#define TG_MLP_MAX_TOWERS 4
+#define TG_MLP_MAX_LAYERS 4
+#define TG_MLP_MAX_WIDTH 256
+#define TG_MLP_MAX_IN 1024
+#define TG_MLP_MAX_ROWS 2147483616
+#define TG_MLP_ACT_NONE 0
+#define TG_MLP_ACT_TANH 1
+#define TG_MLP_ACT_RELU 2
+typedef struct tg_mlp_layer {
+    const float* weight;                    /* [out][in] */
+    const float* bias;                      /* [out] */
+    const float* weight2;                   /* the last layer's second row block [out2][in]; NULL with out2 = 0 */
+    const float* bias2;                     /* [out2] */
+    float* h;                               /* [B][out]: written by the forward call (the last layer's always), read by the backward call */
+    float* h2;                              /* [B][out2] */
+    float* dweight;                         /* the backward call's outputs, each nullable */
+    float* dbias;
+    float* dweight2;
+    float* dbias2;
+    int32_t in, out, out2, act;             /* act: TG_MLP_ACT_* */
+} tg_mlp_layer;
+typedef struct tg_mlp_tower {
+    int32_t n_layers, reserved;
+    const float* dy;                        /* backward: the gradient of the last layer's h [B][out], of h2 [B][out2]; NULL: zeros */
+    const float* dy2;
+    tg_mlp_layer layer[TG_MLP_MAX_LAYERS];
+} tg_mlp_tower;
+int tg_mlp_forward(const float* x0_dev, int32_t Ka, const float* x1_dev, int32_t Kb, int64_t B, const tg_mlp_tower* towers, int32_t T,
+                   int32_t save_all, void* hip_stream);
+int64_t tg_mlp_backward_workspace(int64_t B, int32_t Ka, int32_t Kb, const tg_mlp_tower* towers, int32_t T);
+int tg_mlp_backward(const float* x0_dev, int32_t Ka, const float* x1_dev, int32_t Kb, int64_t B, const tg_mlp_tower* towers, int32_t T,
+                    float* dx0_dev, float* dx1_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,7 @@ loudly when the HIP library or a GPU is missing.
     critic_loss, stats = tg.sac_critic_loss(q_cur, q_next, next_log_prob, b.rewards, b.dones, gamma, log_ent_coef=log_ent_coef)   # SAC.train's TD target and critic loss, one launch
     actor_loss, ent_coef_loss, stats = tg.sac_actor_loss(log_prob, q_pi, log_ent_coef=log_ent_coef, target_entropy=-A)              # its actor and entropy-coefficient losses, one launch
     critic_stats, actor_stats, n_updates = tg.train.sac_train(actor, critic, critic_target, actor_opt, critic_opt, rb, head, 1, 64, 0.95, 0.005, log_ent_coef=log_ent_coef, ent_coef_optimizer=ent_opt, target_entropy=-A)   # SAC.train over the device pieces
+    heads = tg.ActorCriticHeads(features_dim, A, dict(pi=[256, 256], vf=[256, 256])); policy = lambda obs: heads(extractor(obs))   # SB3's MlpExtractor, action_net and value_net in one launch (tg.mlp; imports torch); tg.SacActorHeads, tg.ContinuousCriticHeads: SAC's
     CustomCombinedExtractor(observation_space, cnn_base=tg.NatureCNN)   # SB3's NatureCNN, its first layer one launch on the uint8 images (tg.torch_layers; imports torch)
 """
 from . import rl_envs  # noqa: F401  (registers the env ids)
@@ -34,7 +35,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("augment", "rollout", "replay", "vecnorm", "action_head", "collect", "torch_layers", "loss_head", "train"):   # imported on first use: they need torch, the rest of the package does not
+    if name in ("augment", "rollout", "replay", "vecnorm", "action_head", "collect", "torch_layers", "loss_head", "train", "mlp"):   # imported on first use: they need torch, the rest of the package does not
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "DeviceRolloutBuffer":
@@ -55,4 +56,7 @@ def __getattr__(name):
     if name in ("NatureCNN", "ConvStem", "conv_stem"):
         import importlib
         return getattr(importlib.import_module(".torch_layers", __name__), name)
+    if name in ("mlp_towers", "ActorCriticHeads", "SacActorHeads", "ContinuousCriticHeads"):
+        import importlib
+        return getattr(importlib.import_module(".mlp", __name__), name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

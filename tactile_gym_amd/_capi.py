@@ -38,6 +38,8 @@ HEAD_GAUSSIAN, HEAD_SQUASHED, HEAD_UNIFORM, HEAD_MAX_ACT = 0, 1, 2, 16   # TG_HE
 LOSS_PATH_AUTO, LOSS_PATH_ONE, LOSS_PATH_GRID, LOSS_ONE_MAX_ROWS = 0, 1, 2, 4096   # TG_LOSS_* (tg_ppo_loss)
 SAC_MAX_CRITICS, SAC_MAX_ROWS = 4, 65536   # TG_SAC_* (tg_sac_critic_loss, tg_sac_actor_loss)
 STEM_KERNEL, STEM_STRIDE, STEM_OUT, STEM_MAX_CIN = 8, 4, 32, 12   # TG_STEM_* (tg_conv_stem, tg_conv_stem_bwd)
+MLP_MAX_TOWERS, MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_IN, MLP_MAX_ROWS = 4, 4, 256, 1024, 2147483616   # TG_MLP_* (tg_mlp_forward, tg_mlp_backward)
+MLP_ACT = {"none": 0, "tanh": 1, "relu": 2}   # TG_MLP_ACT_*
 OBS_STACK_KEY = dict(OBS_KEY, visual=3)   # + TG_OBS_KEY_VISUAL (ABI v16: the scene camera's images)
 NARROWPHASE = {"closed_form": 0, "gjk_manifold": 1, "gjk_single": 2}
 BALANCE_OBJECT = {"pole": 0, "ball_on_plate": 1, "spinning_plate": 2}
@@ -159,6 +161,15 @@ class TgStateView(C.Structure):
     ]
 
 
+class TgMlpLayer(C.Structure):       # tg_mlp_layer: device pointers as plain addresses
+    _fields_ = ([(k, C.c_void_p) for k in ("weight", "bias", "weight2", "bias2", "h", "h2", "dweight", "dbias", "dweight2", "dbias2")]
+                + [(k, C.c_int32) for k in ("in_", "out", "out2", "act")])
+
+
+class TgMlpTower(C.Structure):       # tg_mlp_tower
+    _fields_ = [("n_layers", C.c_int32), ("reserved", C.c_int32), ("dy", C.c_void_p), ("dy2", C.c_void_p), ("layer", TgMlpLayer * MLP_MAX_LAYERS)]
+
+
 # name -> (restype, argtypes); every symbol include/tactile_gym_hip.h declares
 _dp, _fp, _u8p, _vpp = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_void_p)
 _ctx = C.c_void_p
@@ -260,6 +271,10 @@ SYMBOLS = {
     "tg_conv_stem_bwd_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "tg_conv_stem_bwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "tg_mlp_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(TgMlpTower), C.c_int32, C.c_int32, C.c_void_p]),
+    "tg_mlp_backward_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(TgMlpTower), C.c_int32]),
+    "tg_mlp_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(TgMlpTower), C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_int64, C.c_void_p]),
     "tg_ppo_loss_workspace": (C.c_int64, [C.c_int64, C.c_int32]),
     "tg_ppo_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
                               C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
