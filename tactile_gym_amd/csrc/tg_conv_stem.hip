@@ -4,7 +4,8 @@
 // data and gets no gradient).  Compiled with -ffp-contract=off; the only fused multiply-adds are the ones written: the MFMA's and __builtin_fmaf.
 //
 // Specification per output element, k = (c 8 + ky) 8 + kx (torch's [32][Cn][8][8] weight, flattened), K = 64 Cn:
-//     acc = 0;  for k = 0 .. K-1 ascending: acc = fmaf((float) x_k, w[co][k], acc);  y = fmaxf(fmaf(acc, scale, bias[co]), 0)
+//     acc = 0;  for k = 0 .. K-1 ascending: acc = fmaf((float) x_k, w[co][k], acc);  z = fmaf(acc, scale, bias[co]);  y = relu(z)
+// relu(z) = z > 0 ? z : (z != z ? z : 0): fmaxf(z, 0)'s bits for every number, and a NaN stays a NaN as in torch.relu.
 // v_mfma_f32_32x32x2_f32 is bit for bit that chain (two k per instruction, the lower first), so every output element has ONE arithmetic order,
 // whatever the batch it sits in and wherever its tile falls.
 //
@@ -147,7 +148,8 @@ __global__ __launch_bounds__(kStemThreads) void k_conv_stem(StemArgs a) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
             const int32_t co = (i & 3) + 8 * (i >> 2) + 4 * h;
-            a.y[(r.b * TG_STEM_OUT + co) * plane + at] = __builtin_fmaxf(__builtin_fmaf(acc[i], a.scale, a.bias[co]), 0.0f);
+            const float z = __builtin_fmaf(acc[i], a.scale, a.bias[co]);
+            a.y[(r.b * TG_STEM_OUT + co) * plane + at] = z > 0.0f ? z : (z != z ? z : 0.0f);   // torch.relu: a NaN stays a NaN
         }
     }
 }

@@ -4,6 +4,7 @@
 //
 // Specification per output element (W torch's [out][in]):
 //     acc = 0;  for k = 0 .. in-1 ascending: acc = fmaf(h_{l-1}[row][k], W[co][k], acc);  z = acc + b[co];  h = act(z)
+// (ReLU: z > 0 ? z : (z != z ? z : 0) - a NaN stays a NaN, as in torch.relu.)
 // v_mfma_f32_32x32x2_f32 is bit for bit that chain (two k per instruction, the lower first), so an output has ONE arithmetic order,
 // whatever the batch it sits in, wherever its tile falls and whatever other towers run beside it.  The k tail (in odd, or no multiple of the
 // 32-wide staging chunk) is finished with the operand pair (-0.0, +0.0): the product is -0.0 and acc + (-0.0) has acc's bits for EVERY acc, where
@@ -56,6 +57,9 @@ struct MlpArgs {
 };
 
 __device__ __forceinline__ int mlp_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+// torch.relu: fmaxf's bits for every number (-0.0 -> +0.0 included), and a NaN stays a NaN where fmaxf would return 0
+__device__ __forceinline__ float mlp_relu(float z) { return z > 0.0f ? z : (z != z ? z : 0.0f); }
 
 __device__ __forceinline__ const float* mlp_input_at(const MlpArgs& a, int64_t row, int32_t k) {
     return k < a.Ka ? a.x0 + row * a.Ka + k : a.x1 + row * a.Kb + (k - a.Ka);
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(kMlpThreads) void k_mlp_fwd(MlpArgs a) {
                 float v = -0.0f;                                          // past the layer's width: the next layer's k tail
                 if (co < outT) {
                     const float z = acc[i] + bias;
-                    v = ly.act == TG_MLP_ACT_RELU ? __builtin_fmaxf(z, 0.0f) : ly.act == TG_MLP_ACT_TANH ? (float)tanh((double)z) : z;
+                    v = ly.act == TG_MLP_ACT_RELU ? mlp_relu(z) : ly.act == TG_MLP_ACT_TANH ? (float)tanh((double)z) : z;
                 }
                 hs[r * kMlpPitch + (co ^ r)] = v;
                 const int64_t row = row0 + r;

@@ -11,7 +11,8 @@ values bounded by scale sum|x w| + |b|.  With 2^-23 = 2 u in place of u, and K +
 They are derived, not measured.
 
 Grid cases.  With integer x (uint8 values), integer w in [-64, 64], integer b, scale = 2^-8 and integer g in [-4, 4], every partial sum of
-every order is an integer below 2^24 in magnitude (K <= 768: 768 * 255 * 64 < 2^24; M <= 16000: 16000 * 4 * 255 < 2^24), so float32
+every order is an integer below 2^24 in magnitude (K <= 768: 768 * 255 * 64 < 2^24; M gmax 255 < 2^24 with g in [-gmax, gmax], which
+grid_backward_case asserts: M <= 16448 at gmax = 4, M <= 21930 at gmax = 3), so float32
 arithmetic is exact and the float64 result, rounded to float32, is the ONLY correct answer: the kernels must give those bits.  The weights
 and gradients are drawn at random: a pattern symmetric in two indices would hide a row <-> column swap of an MFMA operand or result."""
 import numpy as np
@@ -39,7 +40,42 @@ BWD_CASES = [
     (8, 8, 1, 1, True, False), (8, 8, 3, 5, False, False), (8, 8, 3, 3, True, True),
     (40, 52, 1, 3, False, False), (40, 52, 3, 5, True, False), (40, 52, 3, 1, False, True),
     (128, 128, 1, 5, True, False), (128, 128, 3, 3, False, False), (128, 128, 1, 1, True, True),
+    # more regions than the 256 workgroups of a channel, so a workgroup walks on: its barrier between regions, its accumulator tile and its
+    # bias sum carried over
+    (8, 8, 2, 257, True, False),              # 257 regions of one position: workgroup 0 walks two
+    (12, 12, 1, 600, False, False),           # 600 regions of 4 positions: workgroups walk 2 or 3; the second MFMA phase stays idle
+    (16, 176, 1, 129, True, False),           # OW = 43, R = 2: strips of 2 rows and of 1 row; 258 regions; M = 16641
+    (8, 530, 1, 129, False, True),            # OW = 131: chunks of 128 and 3; 258 regions; float32 NHWC; M = 16899
+    (12, 530, 2, 3, True, False),             # chunks x strips without a wrap; two channels
 ]
+# the gradient range of a backward grid case: two regions an image mean more than 128 positions an image, so a wrap with several strips or
+# chunks needs M > 16448 and a narrower range
+GMAX = {(16, 176, 1, 129, True, False): 3, (8, 530, 1, 129, False, True): 3}
+POS, BWD_GROUPS = 128, 256                           # kStemPos, kStemBwdGroups
+
+
+def gmax_of(case):
+    return GMAX.get(tuple(case), 4)
+
+
+def geometry(B, H, W):
+    """stem_geom and stem_groups of csrc/tg_conv_stem.hip: how the OH x OW output positions of an image are cut into regions of at most 128
+    (column chunks of Cw, strips of R rows) and how many workgroups a channel's backward pass runs."""
+    OH, OW = out_hw(H, W)
+    Cw = min(OW, POS)
+    n_chunks = (OW + Cw - 1) // Cw
+    R = min(POS // Cw, OH)
+    n_strips = (OH + R - 1) // R
+    regions = B * n_strips * n_chunks
+    return dict(OH=OH, OW=OW, Cw=Cw, n_chunks=n_chunks, R=R, n_strips=n_strips, regions=regions, G=min(regions, BWD_GROUPS))
+
+
+def region(geom, index):
+    """stem_region: (image, first row, first column, rows, columns) of region `index`."""
+    chunk, rest = index % geom["n_chunks"], index // geom["n_chunks"]
+    strip, b = rest % geom["n_strips"], rest // geom["n_strips"]
+    oy0, ox0 = strip * geom["R"], chunk * geom["Cw"]
+    return b, oy0, ox0, min(geom["OH"] - oy0, geom["R"]), min(geom["OW"] - ox0, geom["Cw"])
 
 
 def out_hw(H, W):
@@ -106,12 +142,12 @@ def random_forward_case(rng, B, Cn, H, W, channels_first, x_is_float):
     return _images(rng, B, Cn, H, W, channels_first, x_is_float), w, b, U8_SCALE
 
 
-def grid_backward_case(rng, B, Cn, H, W, channels_first, x_is_float):
-    """(x, y, dy, scale): y has zeros (about half), so the mask matters; dy is an integer in [-4, 4] everywhere."""
+def grid_backward_case(rng, B, Cn, H, W, channels_first, x_is_float, gmax=4):
+    """(x, y, dy, scale): y has zeros (about half), so the mask matters; dy is an integer in [-gmax, gmax] everywhere."""
     OH, OW = out_hw(H, W)
-    assert B * OH * OW <= 16000
+    assert B * OH * OW * gmax * 255 < 2 ** 24                             # every partial sum of every order is an integer float32 holds
     y = np.maximum(rng.integers(-3, 4, (B, OUT, OH, OW)), 0).astype(f32)
-    dy = rng.integers(-4, 5, (B, OUT, OH, OW)).astype(f32)
+    dy = rng.integers(-gmax, gmax + 1, (B, OUT, OH, OW)).astype(f32)
     return _images(rng, B, Cn, H, W, channels_first, x_is_float), y, dy, GRID_SCALE
 
 

@@ -78,7 +78,7 @@ def test_reference_backward_equals_torch_float64_autograd(case):
     _close(dw, wt.grad.numpy())
     _close(db, bt.grad.numpy())
     assert dw_bound.shape == dw.shape and db_bound.shape == db.shape and (dw_bound >= 0).all()
-    x, yg, dyg, scale = ref.grid_backward_case(rng, B, Cn, H, W, cf, fl)
+    x, yg, dyg, scale = ref.grid_backward_case(rng, B, Cn, H, W, cf, fl, gmax=ref.gmax_of(case))
     dw, db, _, _ = ref.backward(x, yg, dyg, scale, cf)
     assert np.array_equal(dw.astype(f32).astype(np.float64), dw) and np.array_equal(db.astype(f32).astype(np.float64), db)
     assert (yg == 0).any() and (yg > 0).any()
@@ -258,3 +258,80 @@ def test_conv_stem_kernels_use_no_scratch(tmp_path):
     stem = {k: v for k, v in scratch.items() if "k_conv_stem" in k}
     assert len(stem) == 9, sorted(stem)              # forward and backward x {uint8, float32} x {channels first, last}, and the reduction
     assert all(v == 0 for v in stem.values()), stem
+
+
+# ---------------------------------------------------------------------------------------------------------------------- the backward's walk
+def _position_mask(case, keep_region):
+    """bool [B, OH, OW]: the output positions of the regions keep_region(index, geometry) picks."""
+    H, W, Cn, B, cf, fl = case
+    g = ref.geometry(B, H, W)
+    mask = np.zeros((B, g["OH"], g["OW"]), bool)
+    for index in range(g["regions"]):
+        if keep_region(index, g):
+            b, oy0, ox0, rv, cv = ref.region(g, index)
+            mask[b, oy0:oy0 + rv, ox0:ox0 + cv] = True
+    return mask
+
+
+def test_geometry_restates_stem_geom_and_the_backward_cases_reach_every_edge_of_the_walk():
+    assert ref.geometry(1, 128, 128) == dict(OH=31, OW=31, Cw=31, n_chunks=1, R=4, n_strips=8, regions=8, G=8)       # DESIGN 4.14's example
+    assert ref.geometry(129, 16, 176) == dict(OH=3, OW=43, Cw=43, n_chunks=1, R=2, n_strips=2, regions=258, G=256)
+    assert ref.geometry(129, 8, 530) == dict(OH=1, OW=131, Cw=128, n_chunks=2, R=1, n_strips=1, regions=258, G=256)
+    L = _capi.lib()
+    reached = set()
+    for case in ref.BWD_CASES:
+        H, W, Cn, B, cf, fl = case
+        g = ref.geometry(B, H, W)
+        assert L.tg_conv_stem_bwd_workspace(B, Cn, H, W) == 4 * (g["G"] * 2 * 32 * 64 * Cn + g["G"] * 8 * 32)          # stem_workspace on this G
+        regions = [ref.region(g, i) for i in range(g["regions"])]
+        assert sum(rv * cv for _, _, _, rv, cv in regions) == B * g["OH"] * g["OW"] and max(rv * cv for _, _, _, rv, cv in regions) <= ref.POS
+        assert _position_mask(case, lambda i, g: True).all()                  # the regions tile every image
+        wrap = g["regions"] > g["G"]
+        reached |= {name for name, hit in (
+            ("regions > G", wrap), ("regions % G != 0", wrap and g["regions"] % g["G"] != 0),
+            ("a workgroup with three regions", -(-g["regions"] // g["G"]) >= 3), ("n_chunks > 1", g["n_chunks"] > 1),
+            ("n_strips > 1 with regions > G", g["n_strips"] > 1 and wrap), ("n_chunks > 1 with regions > G", g["n_chunks"] > 1 and wrap),
+            ("a last chunk smaller than the others", g["OW"] % g["Cw"] != 0), ("a last strip smaller than the others", g["OH"] % g["R"] != 0),
+            ("npos <= 64", min(rv * cv for _, _, _, rv, cv in regions) <= 64)) if hit}
+    assert reached == {"regions > G", "regions % G != 0", "a workgroup with three regions", "n_chunks > 1", "n_strips > 1 with regions > G",
+                       "n_chunks > 1 with regions > G", "a last chunk smaller than the others", "a last strip smaller than the others", "npos <= 64"}
+    with pytest.raises(AssertionError):                                       # the exactness check does refuse what is not exact
+        ref.grid_backward_case(np.random.default_rng(0), 129, 1, 16, 176, True, False, gmax=4)
+    with pytest.raises(AssertionError):
+        ref.grid_backward_case(np.random.default_rng(0), 6, 1, 128, 128, True, False, gmax=18)
+
+
+def test_mutants_of_the_backward_walk_change_the_grid_cases_bits():
+    """What k_conv_stem_bwd would return were it wrong at one edge of its walk over the regions: the sums are linear in g = dy (y > 0), so a
+    lost region is a masked dy."""
+    def bits(a):
+        return np.asarray(a).astype(f32).view(np.uint32)
+
+    seen = {"first": 0, "chunk": 0, "bias": 0}
+    for case in ref.BWD_CASES:
+        H, W, Cn, B, cf, fl = case
+        g = ref.geometry(B, H, W)
+        wrap, chunks = g["regions"] > g["G"], g["n_chunks"] > 1
+        if not (wrap or chunks):
+            continue
+        rng = np.random.default_rng(hash(case) % 2**32)                       # the GPU test's draw
+        x, y, dy, scale = ref.grid_backward_case(rng, B, Cn, H, W, cf, fl, gmax=ref.gmax_of(case))
+        dw, db, _, _ = ref.backward(x, y, dy, scale, cf)
+
+        def masked(keep):
+            m = _position_mask(case, keep)
+            assert not m.all()
+            return ref.backward(x, y, dy * m[:, None], scale, cf)[:2]
+        if wrap:
+            dw1, db1 = masked(lambda i, g: i < g["G"])                        # only each workgroup's first region contributes
+            assert (bits(dw1) != bits(dw)).any() and (bits(db1) != bits(db)).any(), case
+            last = lambda i, g: i + g["G"] >= g["regions"]   # noqa: E731        the bias sum restarted at every region: the last one is left
+            _, db3 = masked(last)
+            assert (bits(db3) != bits(db)).any(), case
+            seen["first"] += 1
+            seen["bias"] += 1
+        if chunks:
+            dw2, db2 = masked(lambda i, g: i % g["n_chunks"] != 1)            # the second column chunk dropped
+            assert (bits(dw2) != bits(dw)).any() and (bits(db2) != bits(db)).any(), case
+            seen["chunk"] += 1
+    assert seen == {"first": 4, "chunk": 2, "bias": 4}, seen

@@ -94,7 +94,9 @@ def _backward(x, y, dy, scale, channels_first, shrink=0, twice=False):
 
 def _within(got, want, bound, what):
     err = np.abs(got.astype(np.float64) - want)
-    assert (err <= bound).all(), (what, float((err / np.maximum(bound, 1e-300)).max()))
+    ratio = float((err / np.maximum(bound, 1e-300)).max())
+    print(f"{what}: largest error / bound = {ratio:.3g}")
+    assert (err <= bound).all(), (what, ratio)
 
 
 def _id(case):
@@ -133,7 +135,7 @@ def test_an_image_alone_equals_the_image_in_a_batch_of_65(shape):
 def test_backward_grid_bits_random_bound_and_repeat(case):
     H, W, Cn, B, cf, fl = case
     rng = np.random.default_rng(hash(case) % 2**32)
-    x, y, dy, scale = ref.grid_backward_case(rng, B, Cn, H, W, cf, fl)
+    x, y, dy, scale = ref.grid_backward_case(rng, B, Cn, H, W, cf, fl, gmax=ref.gmax_of(case))
     assert (y == 0).any() and (dy[y == 0] != 0).any()                      # the mask matters
     dw_want, db_want, _, _ = ref.backward(x, y, dy, scale, cf)
     dw, db = _backward(x, y, dy, scale, cf)
@@ -196,3 +198,47 @@ def test_error_returns_write_nothing_and_name_the_function():
     torch.cuda.synchronize()
     for g in outs:
         assert g.guards_intact() and bool((g.payload() == PATTERN).all())
+
+
+WRAPPING = [c for c in ref.BWD_CASES if ref.geometry(c[3], c[0], c[1])["regions"] > 256 or ref.geometry(c[3], c[0], c[1])["n_chunks"] > 1]
+
+
+@pytest.mark.parametrize("case", WRAPPING, ids=_id)
+def test_forward_of_a_wrapping_backward_grid_case_feeds_the_backward(case):
+    """As above on the cases whose workgroups walk more than one region, or whose images have more than one column chunk."""
+    H, W, Cn, B, cf, fl = case
+    assert len(WRAPPING) == 5
+    rng = np.random.default_rng(11)
+    x, w, b, scale = ref.grid_forward_case(rng, B, Cn, H, W, cf, fl)
+    y = _forward(x, w, b, scale, cf)
+    want, _ = ref.forward(x, w, b, scale, cf)
+    assert _bits(y, want.astype(f32))
+    gmax = ref.gmax_of(case)
+    assert y.size // 32 * gmax * 255 < 2 ** 24                             # grid_backward_case's condition, on this dy
+    dy = rng.integers(-gmax, gmax + 1, y.shape).astype(f32)
+    dw_want, db_want, _, _ = ref.backward(x, y, dy, scale, cf)
+    dw, db = _backward(x, y, dy, scale, cf)
+    assert _bits(dw, dw_want.astype(f32)) and _bits(db, db_want.astype(f32))
+
+
+@pytest.mark.parametrize("channels_first", [True, False], ids=["chw", "hwc"])
+@pytest.mark.parametrize("hw", [(37, 39), (40, 52)], ids=["37x39", "40x52"])
+def test_forward_a_nan_pixel_is_nan_where_its_windows_are_and_changes_nothing_else(hw, channels_first):
+    """float32 input, one NaN pixel inside the window of position 0 of its region.  (40, 52) has 9 x 12 = 108 positions a region, no multiple of
+    32: the lanes past the region's last position compute on position 0, so they hold the NaN - and store nothing.  (37, 39) has 8 x 8 = 64."""
+    (H, W), Cn, B = hw, 2, 3
+    g = ref.geometry(B, H, W)
+    assert g["regions"] == B and (g["OH"] * g["OW"]) % 32 == (0 if hw == (37, 39) else 12)
+    rng = np.random.default_rng(13)
+    x, w, b, scale = ref.random_forward_case(rng, B, Cn, H, W, channels_first, True)
+    clean = _forward(x, w, b, scale, channels_first)
+    py, px = 5, 6                                                          # inside the windows of positions (0, 0), (0, 1), (1, 0), (1, 1)
+    if channels_first:
+        x[1, 1, py, px] = np.nan
+    else:
+        x[1, py, px, 1] = np.nan
+    got = _forward(x, w, b, scale, channels_first)
+    hit = np.zeros(clean.shape, bool)
+    hit[1, :, :2, :2] = True
+    assert np.isnan(got[hit]).all()                                        # all 32 channels: ReLU hands the NaN on, as torch.relu does
+    assert not np.isnan(got[~hit]).any() and _bits(got[~hit], clean[~hit])  # everything else, in every image, has the clean run's bits

@@ -14,6 +14,7 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+import mlp_cases as mc  # noqa: E402
 import mlp_ref as ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -97,6 +98,8 @@ CASES = [
     (64, 258, 256, [([256, 256, 1], ["relu", "relu", "none"], 0), ([256, 256, 1], ["relu", "relu", "none"], 0)]),      # SAC's critic
     (65, 33, 33, [([64, 33, 2], ["tanh", "tanh", "none"], 0), ([33, 2], ["relu", "tanh"], 2)]),
     (3, 5, 5, [([7], ["tanh"], 0)]),
+    # four towers of mixed depth, all three activations, widths 130 and 255, a 100 + 100 last layer, x cut inside a k tile (tests/mlp_cases.py)
+    (65, 40, 33, [(w, mc.random_acts(a, t), two) for t, (w, a, two) in enumerate(mc.TABLE["four-mixed"][3])]),
 ]
 
 
@@ -263,6 +266,37 @@ def test_modules_autograd_and_the_cpu_path(kind):
     for t, (y, yh, tower) in enumerate(zip(ys, ys_host, towers)):
         bound = ref.tower_forward(x, tower)[-1][1]
         assert (np.abs(_host(y).astype(np.float64) - yh.numpy()) <= (3 if module.act == "tanh" else 2) * bound).all(), (kind, t)
+
+
+class _Space:
+    def __init__(self, shape):
+        self.shape, self.dtype = tuple(shape), np.uint8
+
+
+def test_a_nan_feature_row_is_nan_on_the_device_as_on_the_cpu():
+    """ReLU hands a NaN on (torch.relu's rule, which the CPU paths follow): a diverged policy shows on the device as it does on the host."""
+    import tactile_gym_amd as tg
+    torch.manual_seed(8)
+    rng = np.random.default_rng(9)
+    B, fd, A, bad = 5, 20, 2, 3
+    feats, actions = rng.standard_normal((B, fd)).astype(f32), rng.uniform(-1, 1, (B, A)).astype(f32)
+    feats[bad, 7] = np.nan
+    image = rng.integers(0, 256, (B, 1, 64, 64)).astype(f32)
+    image[bad, 0, 20, 21] = np.nan
+    trials = [(tg.ActorCriticHeads(fd, A, dict(pi=[64, 33], vf=[64]), activation_fn=nn.ReLU), (feats,)),
+              (tg.SacActorHeads(fd, A, [64, 33]), (feats,)),
+              (tg.ContinuousCriticHeads(fd, A, [64, 33]), (feats, actions)),
+              (tg.NatureCNN(_Space((1, 64, 64)), features_dim=16, float_scale=1.0 / 255.0), (image,))]
+    for module, args in trials:
+        host, dev = module, copy.deepcopy(module).cuda()
+        with torch.no_grad():
+            out_host, out_dev = host(*[torch.from_numpy(a) for a in args]), dev(*[_cuda(a) for a in args])
+        out_host, out_dev = ([o.reshape(B, -1) for o in (out if isinstance(out, tuple) else (out,)) if o.shape[0] == B] for out in (out_host, out_dev))
+        name = type(module).__name__
+        assert len(out_host) == len(out_dev) >= 1
+        for h, d in zip(out_host, out_dev):
+            assert np.array_equal(np.isnan(_host(d)), np.isnan(h.numpy())), name
+            assert np.isnan(_host(d)[bad]).all() and not np.isnan(np.delete(_host(d), bad, axis=0)).any(), name
 
 
 class CachingPolicy:
