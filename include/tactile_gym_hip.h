@@ -826,7 +826,9 @@ int tg_conv_stem_bwd(const void* x_dev, int32_t x_is_float, int32_t channels_fir
  * [B][A] and log_prob_out [B], and for the backward pass (nullable) eps_out and sigma_out [B][A].  tg_squashed_rsample_bwd: from
  * g_actions_dev [B][A] and g_log_prob_dev [B] (each nullable: zero), the saved actions, eps, sigma and the forward's log_std_dev, with
  * w = (1 - a^2) + 1e-6f and s = g_a (1 - a^2) + g_lp 2 a (1 - a^2) / w:  dmean_out = s,  dlog_std_out = (s sigma eps - g_lp) m, both
- * [B][A] and nullable, m = 1 where log_std lies in [log_std_min, log_std_max] (inclusive, torch.clamp's rule) and 0 elsewhere.  One launch each. */
+ * [B][A] and nullable, m = 1 where log_std lies in [log_std_min, log_std_max] (inclusive, torch.clamp's rule) and 0 elsewhere.  One launch each.
+ * Non-finite values follow torch's autograd: with g_log_prob_dev, s is NaN where g_lp (sigma eps) / sigma^2 is not finite,
+ * and eps_out is NaN where mean is not finite (the noise, bit for bit, everywhere else). */
 #define TG_LOSS_PATH_AUTO 0
 #define TG_LOSS_PATH_ONE 1
 #define TG_LOSS_PATH_GRID 2

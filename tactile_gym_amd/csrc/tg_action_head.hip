@@ -71,7 +71,8 @@ __global__ __launch_bounds__(kHeadThreads) void k_action_head(HeadArgs a) {
         ls = head_clamp(ls, a.ls_min, a.ls_max);                                   // a NaN passes, as torch.clamp
         const float sigma = head_sigma(ls);
         const float eps = a.noise_in ? a.noise_in[e] : (a.deterministic ? 0.0f : head_normal(a.seed, a.counter, (uint64_t)e));
-        const float se = sigma * eps;
+        // deterministic is SB3's mode(), mean itself: no product with sigma, whose 0 inf or 0 NaN would make a NaN of a finite mean
+        const float se = (a.deterministic && !a.noise_in) ? 0.0f : sigma * eps;
         const float x = mean + se;
         if (a.noise_out) a.noise_out[e] = eps;
         if (a.gauss) a.gauss[e] = x;

@@ -113,10 +113,12 @@ __device__ __forceinline__ double chunk_pass(const PpoArgs& a, int64_t chunk, fl
         const float p2 = adv * rc;
         const float pm = p2 < p1 ? p2 : p1;           // torch.min
         const bool inside = ratio >= lo && ratio <= hi;
-        if (inside || p1 < p2) {                      // autograd: the clamp passes inside (inclusive); outside only the unclipped product, when it is the smaller
-            const float g = p1 / fB;
-            coef = -g;
-        }
+        // autograd: the clamp passes inside (inclusive); outside only the unclipped product, when it is the smaller.  torch.min hands a NaN
+        // product the gradient as well, and the zero of a blocked row still meets adv and ratio on its way back: 0 inf = NaN
+        const float g = p1 / fB;
+        if (inside || !(p1 >= p2)) coef = -g;
+        else if (p1 > p2) coef = (0.0f * fabsf(adv)) * ratio;
+        else coef = 0.0f - g;                         // equal outside the clip: adv is 0, or infinite with half the gradient
         const float v = a.values[i];
         float vp = v;
         bool vpass = true;
@@ -151,6 +153,7 @@ __device__ __forceinline__ double chunk_pass(const PpoArgs& a, int64_t chunk, fl
     slot_put(lds, 4, s_cf);
     if (a.dmean || a.dls) {
         const float ge = a.ent_coef / fB;             // the entropy's share of dlog_std: -ent_coef / B per column
+        const float lost_row = coef - coef;           // 0, or NaN for a coef that is not finite
         for (int j = 0; j < A; ++j) {
             float gl = 0.0f;
             if (valid) {
@@ -166,7 +169,11 @@ __device__ __forceinline__ double chunk_pass(const PpoArgs& a, int64_t chunk, fl
                 const float q = d * d;                // dlog_prob / dlog_std = d^2 / sigma^2 - 1
                 const float qs = q / var;
                 const float dl = qs - 1.0f;
-                const float cl = coef * dl;
+                // autograd reaches log_std on two paths, coef d^2 / sigma^2 through sigma and -coef beside it: with a coef or a sigma that
+                // is not finite they give inf - inf or 0 inf, a NaN, where the factored product would be finite or infinite.  sigma itself
+                // is asked, not its float32 square: a finite sigma whose square overflows gives the finite -coef, in torch as here
+                const float lost = lost_row + (sigma - sigma);
+                const float cl = lost == 0.0f ? coef * dl : lost;
                 gl = cl - ge;
                 if (a.dls && a.ls_stride) a.dls[e] = gl;
             }
@@ -274,7 +281,9 @@ __global__ __launch_bounds__(kLossThreads) void k_squashed_rsample(RsampleArgs a
         gsum = gsum + head_gaussian_term(d, sigma, ls);
         const float act = head_tanh(x);
         a.actions[e] = act;
-        if (a.eps_out) a.eps_out[e] = eps;
+        // saved as the backward needs it: with a mean that is not finite x - mean is NaN and autograd's gradients with it, which the
+        // backward, that never sees mean, reads off a NaN here
+        if (a.eps_out) a.eps_out[e] = mean - mean == 0.0f ? eps : mean - mean;
         if (a.sigma_out) a.sigma_out[e] = sigma;
         csum = csum + head_squash_term(act);
     }
@@ -314,6 +323,13 @@ __global__ __launch_bounds__(kLossThreads) void k_squashed_rsample_bwd(RsampleBw
             const float n3 = n2 / w;
             const float n4 = glp * n3;
             s = s + n4;
+            // the Gaussian sum's gradient is taken analytically (0 to mean): autograd sends G = g_lp d / sigma^2 to x and -G to mean, and
+            // with a G that is not finite (g_lp, eps or sigma infinite, sigma 0) their sum is NaN, not 0
+            const float se = a.sigma[e] * a.eps[e];
+            const float var = a.sigma[e] * a.sigma[e];
+            const float G = glp * (se / var);
+            const float lost = G - G;
+            if (!(lost == 0.0f)) s = lost;
         }
         if (a.dmean) a.dmean[e] = s;
         if (a.dls) {                                  // x = mean + sigma eps; the Gaussian sum's own share is -1 per column

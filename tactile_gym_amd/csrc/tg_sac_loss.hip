@@ -31,6 +31,11 @@ __device__ __forceinline__ float sac_alpha(const float* log_ent_coef, float ent_
     return log_ent_coef ? (float)exp((double)*log_ent_coef) : ent_coef;
 }
 
+// torch.min: a NaN in either operand is the minimum (fminf alone returns the other operand)
+__device__ __forceinline__ float min_keeps_nan(float a, float b) {
+    return a != a ? a : (b != b ? b : fminf(a, b));
+}
+
 struct SacCriticArgs {
     SacIn q_cur, q_next;
     SacOut dq_cur;
@@ -58,7 +63,7 @@ __global__ __launch_bounds__(kLossThreads) void k_sac_critic(SacCriticArgs a) {
             m = a.q_next.p[0][i];
 #pragma unroll
             for (int c = 1; c < kSacCritics; ++c)
-                if (c < a.n) m = fminf(m, a.q_next.p[c][i]);
+                if (c < a.n) m = min_keeps_nan(m, a.q_next.p[c][i]);
             const float t1 = alpha * a.next_log_prob[i];
             const float y = m - t1;
             const float nd = 1.0f - a.dones[i];
@@ -130,12 +135,13 @@ __global__ __launch_bounds__(kLossThreads) void k_sac_actor(SacActorArgs a) {
         if (valid) {
             const float lp = a.log_prob[i];
             float m = a.q_pi.p[0][i];
-            int k = 0;                                // torch.min(dim): the lowest index that attains the minimum takes the gradient
+            int k = 0;                                // torch.min(dim): the lowest index that attains the minimum takes the gradient;
+                                                      // a NaN is the minimum, at the lowest index that holds one
 #pragma unroll
             for (int c = 1; c < kSacCritics; ++c)
                 if (c < a.n) {
                     const float q = a.q_pi.p[c][i];
-                    if (q < m) {
+                    if (q < m || (q != q && m == m)) {
                         m = q;
                         k = c;
                     }

@@ -105,7 +105,8 @@ __global__ __launch_bounds__(kVnChunk) void k_vecnorm_merge(VnTable t, int32_t N
         double n = (double)chunk_rows(0, N), mean = p[0], m2 = p[1];
         for (int c = 1; c < C; ++c) {
             const double nc = (double)chunk_rows(c, N), delta = p[2 * c] - mean, tot = n + nc;
-            mean = mean + delta * nc / tot;
+            // a chunk mean that is not finite: np.mean's sum, inf + x = inf, where the step's inf - inf would be NaN (opposite infinities still are)
+            mean = delta - delta == 0.0 ? mean + delta * nc / tot : mean + p[2 * c];
             m2 = m2 + p[2 * c + 1] + delta * delta * n * nc / tot;
             n = tot;
         }

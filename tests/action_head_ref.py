@@ -106,14 +106,17 @@ def scale_f32(env, lo, hi):
 
 
 def device_order(mode, mean, log_std, lo, hi, log_std_min=-np.inf, log_std_max=np.inf, deterministic=False, seed=0, counter=0, noise=None,
-                 shape=None):
+                 shape=None, mistake=None):
     """What one tg_action_head call writes: dict(actions, env, gaussian, log_prob, noise) of float32 arrays (gaussian / log_prob None in the
     uniform mode).  mean [N, A]; log_std [A] or [N, A]; lo, hi [A]; noise: given in place of the draws.  shape: (N, A) of the uniform mode."""
     with np.errstate(all="ignore"):                      # infinities and NaNs pass through as they do on the device
-        return _device_order(mode, mean, log_std, lo, hi, log_std_min, log_std_max, deterministic, seed, counter, noise, shape)
+        return _device_order(mode, mean, log_std, lo, hi, log_std_min, log_std_max, deterministic, seed, counter, noise, shape, mistake)
 
 
-def _device_order(mode, mean, log_std, lo, hi, log_std_min, log_std_max, deterministic, seed, counter, noise, shape):
+DEVICE_MISTAKES = ("deterministic multiplies sigma by 0",)   # x = mean + sigma 0: NaN at sigma = inf or NaN, where SB3's mode() is mean itself
+
+
+def _device_order(mode, mean, log_std, lo, hi, log_std_min, log_std_max, deterministic, seed, counter, noise, shape, mistake=None):
     lo, hi = np.asarray(lo, dtype=_f32), np.asarray(hi, dtype=_f32)
     if mode == UNIFORM:
         N, A = shape if shape is not None else np.asarray(mean).shape
@@ -131,7 +134,10 @@ def _device_order(mode, mean, log_std, lo, hi, log_std_min, log_std_max, determi
         eps = np.zeros((N, A), _f32)
     else:
         eps = normal_draws(seed, counter, N * A).reshape(N, A)
-    x = (mean + sigma * eps).astype(_f32)
+    se = sigma * eps
+    if deterministic and noise is None and mistake != "deterministic multiplies sigma by 0":
+        se = np.zeros((N, A), _f32)                      # the mode: no product with sigma
+    x = (mean + se).astype(_f32)
     d = x - mean
     t = (d * d) / (_f32(2.0) * (sigma * sigma))
     term = ((-t - ls) - _f32(LOG_SQRT_2PI)).astype(_f32)

@@ -57,6 +57,8 @@ CHUNK = 256
 STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
 PPO_MISTAKES = ("max for min", "clamp passes when clipped", "variance over B", "1e-8 left out", "value clip when none asked", "entropy sign",
                 "entropy missing from dlog_std", "approx_kl as mean(old - new)", "clip_fraction with >=")
+DEVICE_MISTAKES = ("gate drops a NaN", "dlog_std factors the two paths")   # ppo_device_order's selects before the kernel followed autograd there
+RSAMPLE_DEVICE_MISTAKES = ("cancelled paths taken as 0",)                  # rsample_bwd_device_order's, likewise
 RSAMPLE_MISTAKES = ("mask left out", "g_lp term left out", "sigma eps left out", "epsilon inside the square")
 _f32 = np.float32
 
@@ -162,8 +164,9 @@ def tree_sum(v, B):
 
 
 def ppo_device_order(mean, log_std, values, actions, old_log_prob, advantages, returns, old_values=None, clip_range=0.2, clip_range_vf=None,
-                     ent_coef=0.0, vf_coef=0.5, normalize_advantage=True):
-    """What one tg_ppo_loss call writes: dict(stats [8], log_prob, dmean, dlog_std, dvalues) of float32 arrays."""
+                     ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, mistake=None):
+    """What one tg_ppo_loss call writes: dict(stats [8], log_prob, dmean, dlog_std, dvalues) of float32 arrays.  mistake (DEVICE_MISTAKES): the
+    selects the kernel had before it followed torch's autograd on non-finite values."""
     with np.errstate(all="ignore"):
         mean, actions = np.asarray(mean, _f32), np.asarray(actions, _f32)
         B, A = mean.shape
@@ -191,8 +194,13 @@ def ppo_device_order(mean, log_std, values, actions, old_log_prob, advantages, r
         p1 = adv * ratio
         p2 = adv * np.where(ratio < lo, lo, np.where(ratio > hi, hi, ratio)).astype(_f32)
         pm = np.where(p2 < p1, p2, p1)
-        passes = ((ratio >= lo) & (ratio <= hi)) | (p1 < p2)
-        coef = np.where(passes, -(p1 / fB), _f32(0.0)).astype(_f32)
+        inside = (ratio >= lo) & (ratio <= hi)
+        g = p1 / fB
+        if mistake == "gate drops a NaN":
+            coef = np.where(inside | (p1 < p2), -g, _f32(0.0)).astype(_f32)
+        else:                                             # chunk_pass: passes (a NaN product too), blocked, equal outside the clip
+            blocked = (_f32(0.0) * np.abs(adv)) * ratio
+            coef = np.where(inside | ~(p1 >= p2), -g, np.where(p1 > p2, blocked, _f32(0.0) - g)).astype(_f32)
         vp, vpass = values, np.ones(B, bool)
         if clip_range_vf is not None:
             cv, ov = _f32(clip_range_vf), np.asarray(old_values, _f32)
@@ -206,14 +214,31 @@ def ppo_device_order(mean, log_std, values, actions, old_log_prob, advantages, r
         pl, vl, el = _f32(-(sums[0] / B)), _f32(sums[1] / B), _f32(-(sums[2] / B))
         stats = np.array([(pl + ec * el) + vc * vl, pl, vl, el, _f32(sums[3] / B), _f32(sums[4] / B), adv_mean, adv_std], _f32)
         dmean = (coef[:, None] * (d / var)).astype(_f32)
-        dls = ((coef[:, None] * (((d * d) / var) - _f32(1.0))) - ec / fB).astype(_f32)
+        cl = coef[:, None] * (((d * d) / var) - _f32(1.0))
+        if mistake != "dlog_std factors the two paths":   # 0, or NaN for a non-finite coef or sigma (not sigma^2, which overflows first)
+            lost = (coef - coef)[:, None] + (sigma - sigma)
+            cl = np.where(lost == 0, cl, lost)
+        dls = (cl - ec / fB).astype(_f32)
         if not per_row:
             dls = tree_sum(dls, B).astype(_f32)
         return dict(stats=stats, log_prob=lp, dmean=dmean, dlog_std=dls, dvalues=dvalues)
 
 
-def rsample_bwd_device_order(g_a, g_lp, a, eps, sigma, log_std, log_std_min=-20.0, log_std_max=2.0):
-    """What one tg_squashed_rsample_bwd call writes: (dmean, dlog_std), float32 [B, A]."""
+def rsample_saved_eps(mean, eps):
+    """What tg_squashed_rsample saves as eps_out: the noise, NaN where mean is not finite (x - mean is NaN there, and autograd's gradients)."""
+    with np.errstate(all="ignore"):
+        mean, eps = np.asarray(mean, _f32), np.asarray(eps, _f32)
+        return np.where(mean - mean == 0, eps, mean - mean).astype(_f32)
+
+
+def rsample_bwd_device_order(g_a, g_lp, a, eps, sigma, log_std, log_std_min=-20.0, log_std_max=2.0, mistake=None):
+    """What one tg_squashed_rsample_bwd call writes: (dmean, dlog_std), float32 [B, A].  mistake="cancelled paths taken as 0": the kernel
+    before it gave NaN where the Gaussian sum's two gradients, G to x and -G to mean, are not finite."""
+    with np.errstate(all="ignore"):
+        return _rsample_bwd(g_a, g_lp, a, eps, sigma, log_std, log_std_min, log_std_max, mistake)
+
+
+def _rsample_bwd(g_a, g_lp, a, eps, sigma, log_std, log_std_min, log_std_max, mistake):
     a, eps, sigma = (np.asarray(x, _f32) for x in (a, eps, sigma))
     ls = np.broadcast_to(np.asarray(log_std, _f32), a.shape)
     om = _f32(1.0) - a * a
@@ -225,6 +250,9 @@ def rsample_bwd_device_order(g_a, g_lp, a, eps, sigma, log_std, log_std_min=-20.
     if g_lp is not None:
         glp = np.asarray(g_lp, _f32)[:, None]
         s = s + glp * (((_f32(2.0) * a) * om) / w)
+        if mistake != "cancelled paths taken as 0":
+            G = glp * ((sigma * eps) / (sigma * sigma))
+            s = np.where(G - G == 0, s, G - G)
     inside = (ls >= _f32(log_std_min)) & (ls <= _f32(log_std_max))
     return s.astype(_f32), np.where(inside, ((s * sigma) * eps) - glp, _f32(0.0)).astype(_f32)
 

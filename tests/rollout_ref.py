@@ -23,25 +23,32 @@ def _flags(x):
     return (np.asarray(x) != 0)
 
 
-def gae_f64(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda):
-    """(advantages, returns), float64 [T, N]: SB3's recurrence."""
-    r, v, es = (np.asarray(a, dtype=np.float64) for a in (rewards, values, episode_starts))
-    T, N = r.shape
-    lv, d = np.asarray(last_values, dtype=np.float64).reshape(N), _flags(dones).reshape(N).astype(np.float64)
-    adv = np.zeros((T, N))
-    last = np.zeros(N)
-    for t in reversed(range(T)):
-        nnt = 1.0 - (d if t == T - 1 else es[t + 1])
-        nv = lv if t == T - 1 else v[t + 1]
-        delta = r[t] + gamma * nv * nnt - v[t]
-        last = delta + gamma * gae_lambda * nnt * last
-        adv[t] = last
-    return adv, adv + v
+def gae_f64(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda, dtype=np.float64):
+    """(advantages, returns), float64 [T, N]: SB3's recurrence.  dtype=np.float32: the same lines on float32 arrays (SB3's own storage)."""
+    with np.errstate(all="ignore"):                      # infinities and NaNs go through as they do in SB3
+        r, v, es = (np.asarray(a, dtype=dtype) for a in (rewards, values, episode_starts))
+        T, N = r.shape
+        lv, d = np.asarray(last_values, dtype=dtype).reshape(N), _flags(dones).reshape(N).astype(dtype)
+        gamma, gae_lambda, one = dtype(gamma), dtype(gae_lambda), dtype(1.0)
+        adv = np.zeros((T, N), dtype)
+        last = np.zeros(N, dtype)
+        for t in reversed(range(T)):
+            nnt = one - (d if t == T - 1 else es[t + 1])
+            nv = lv if t == T - 1 else v[t + 1]
+            delta = r[t] + gamma * nv * nnt - v[t]
+            last = delta + gamma * gae_lambda * nnt * last
+            adv[t] = last
+        return adv, adv + v
 
 
 def gae_f32(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda, starts_offset=1):
     """(advantages, returns), float32 [T, N]: the device arithmetic.  starts_offset=0 is a deliberately wrong recurrence (episode_starts[t] in
     place of [t + 1]) for the test that shows the error bound is not vacuous."""
+    with np.errstate(all="ignore"):
+        return _gae_f32(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda, starts_offset)
+
+
+def _gae_f32(rewards, values, episode_starts, last_values, dones, gamma, gae_lambda, starts_offset):
     f = np.float32
     r, v, es = (np.ascontiguousarray(a, dtype=f) for a in (rewards, values, episode_starts))
     T, N = r.shape

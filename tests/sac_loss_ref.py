@@ -42,6 +42,7 @@ CRITIC_STATS = ("critic_loss", "ent_coef", "target_q_mean", "min_next_q_mean", "
 ACTOR_STATS = ("actor_loss", "ent_coef_loss", "ent_coef", "log_prob_mean", "min_q_pi_mean", "dlog_ent_coef", "unused_6", "unused_7")
 CRITIC_MISTAKES = ("max for min", "(1 - dones) left out", "entropy sign in the target", "gamma on the reward", "0.5 left out", "mse as a sum")
 ACTOR_MISTAKES = ("min passes gradient to every critic", "alpha not detached", "target_entropy sign", "ent_coef_loss not negated")
+DEVICE_MISTAKES = ("fmin drops a NaN", "min skips a later NaN")   # the *_device_order selects before the kernels followed torch.min on a NaN
 MARGIN = 1e-4          # no two critics' values this close in a row
 _f32 = np.float32
 
@@ -121,15 +122,21 @@ def _alpha32(log_ent_coef, ent_coef):
     return _f32(np.exp(np.float64(_f32(log_ent_coef)))) if log_ent_coef is not None else _f32(ent_coef)
 
 
-def sac_critic_device_order(q_cur, q_next, next_log_prob, rewards, dones, gamma, log_ent_coef=None, ent_coef=None):
-    """What one tg_sac_critic_loss call writes: dict(stats [8], target [B], dq_cur [n, B]) of float32 arrays."""
+def sac_critic_device_order(q_cur, q_next, next_log_prob, rewards, dones, gamma, log_ent_coef=None, ent_coef=None, mistake=None):
+    """What one tg_sac_critic_loss call writes: dict(stats [8], target [B], dq_cur [n, B]) of float32 arrays.  The minimum keeps a NaN, as
+    torch.min does; mistake="fmin drops a NaN" is the minimum the kernel took before (DEVICE_MISTAKES)."""
     q_cur, q_next = [np.asarray(q, _f32).reshape(-1) for q in q_cur], [np.asarray(q, _f32).reshape(-1) for q in q_next]
     nlp, rewards, dones = (np.asarray(x, _f32).reshape(-1) for x in (next_log_prob, rewards, dones))
     B, n = nlp.shape[0], len(q_cur)
     alpha, fB = _alpha32(log_ent_coef, ent_coef), _f32(B)
     m = q_next[0]
     for q in q_next[1:]:
-        m = np.fmin(m, q)
+        m = np.fmin(m, q) if mistake == "fmin drops a NaN" else np.minimum(m, q)
+    with np.errstate(all="ignore"):
+        return _critic_rest(q_cur, m, nlp, rewards, dones, gamma, alpha, fB, B, n)
+
+
+def _critic_rest(q_cur, m, nlp, rewards, dones, gamma, alpha, fB, B, n):
     y = m - alpha * nlp
     target = rewards + ((_f32(1.0) - dones) * _f32(gamma)) * y
     e = [q - target for q in q_cur]
@@ -143,16 +150,25 @@ def sac_critic_device_order(q_cur, q_next, next_log_prob, rewards, dones, gamma,
     return dict(stats=stats, target=target.astype(_f32), dq_cur=np.stack([(x / fB).astype(_f32) for x in e]))
 
 
-def sac_actor_device_order(log_prob, q_pi, log_ent_coef=None, ent_coef=None, target_entropy=None):
-    """What one tg_sac_actor_loss call writes: dict(stats [8], dlog_prob [B], dq_pi [n, B]) of float32 arrays."""
+def sac_actor_device_order(log_prob, q_pi, log_ent_coef=None, ent_coef=None, target_entropy=None, mistake=None):
+    """What one tg_sac_actor_loss call writes: dict(stats [8], dlog_prob [B], dq_pi [n, B]) of float32 arrays.  The minimum and its index are
+    torch.min(dim)'s: a NaN wins, the lowest index that holds one; mistake="min skips a later NaN" is the select the kernel had before."""
+    with np.errstate(all="ignore"):
+        return _actor_order(log_prob, q_pi, log_ent_coef, ent_coef, target_entropy, mistake)
+
+
+def _actor_order(log_prob, q_pi, log_ent_coef, ent_coef, target_entropy, mistake):
     lp = np.asarray(log_prob, _f32).reshape(-1)
     q_pi = [np.asarray(q, _f32).reshape(-1) for q in q_pi]
     B = lp.shape[0]
     alpha, fB = _alpha32(log_ent_coef, ent_coef), _f32(B)
     m, k = q_pi[0], np.zeros(B, int)
     for i, q in enumerate(q_pi[1:], 1):
-        k = np.where(q < m, i, k)
-        m = np.where(q < m, q, m)
+        take = q < m
+        if mistake != "min skips a later NaN":
+            take = take | (np.isnan(q) & ~np.isnan(m))
+        k = np.where(take, i, k)
+        m = np.where(take, q, m)
     cols = [alpha * lp - m, lp, m]
     if target_entropy is not None:
         c = lp + _f32(target_entropy)

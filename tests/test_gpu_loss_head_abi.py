@@ -3,7 +3,6 @@ counts round the wavefront, the 256-row chunk and the 4096-row switch between th
 strides, the value clip and the normalisation on and off.  Every stat and gradient against the float64 composition of tests/loss_head_ref.py
 within the bounds its docstring derives (no row left out, the input conditions asserted), the two paths bit for bit, every subset of the
 nullable outputs, the workspace to the byte, the error returns, and the exact case: the head's own sample gives ratio == 1."""
-import ctypes as C
 import itertools
 import os
 import sys
@@ -19,74 +18,11 @@ import loss_head_ref as ref  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-from device_guard import PATTERN, Guarded  # noqa: E402
+from loss_device import AUTO, GRID, INPUTS, ONE, OUTPUTS, _bits, _head, _lib, _ppo, _rsample, _rsample_bwd, _upload, f32  # noqa: E402
 
 ROWS = (1, 2, 63, 64, 65, 255, 256, 257, 1000, 4096, 4097, 5000)
 WIDTHS = (1, 2, 6, 16)
 CLIP, CLIP_VF, ENT, VF = 0.2, 0.2, 0.01, 0.5
-INPUTS = ("mean", "log_std", "values", "actions", "old_log_prob", "advantages", "returns", "old_values")
-OUTPUTS = ("stats", "log_prob", "dmean", "dlog_std", "dvalues")
-AUTO, ONE, GRID = 0, 1, 2
-f32 = np.float32
-p = lambda g: C.c_void_p(g.ptr if g is not None else None)   # noqa: E731
-
-
-def _lib():
-    from tactile_gym_amd import _capi
-    return _capi, _capi.lib()
-
-
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _upload(inp):
-    return {k: Guarded(v.nbytes, fill=v) for k, v in inp.items() if v is not None}
-
-
-def _ppo(inp, dev, kw, path=AUTO, outputs=OUTPUTS, expect_error=False, workspace_bytes=None, **over):
-    """One tg_ppo_loss call on the uploaded inputs `dev` -> {output name: host float32 array}.  over: B, A, stride, a missing input (name=None),
-    path or a scalar, for the error returns."""
-    capi, L = _lib()
-    B, A = inp["mean"].shape
-    per_row = inp["log_std"].ndim == 2
-    sizes = dict(stats=8, log_prob=B, dmean=B * A, dlog_std=B * A if per_row else A, dvalues=B)
-    outs = {k: Guarded(4 * sizes[k]) for k in outputs}
-    need = int(L.tg_ppo_loss_workspace(B, A))
-    assert need == 16 + 8 * ((B + 255) // 256) * (5 + A)
-    nbytes = need if workspace_bytes is None else workspace_bytes
-    work = Guarded(nbytes)
-    clip_vf = kw["clip_range_vf"]
-    ptr = {k: p(dev.get(k)) for k in INPUTS}
-    if clip_vf is None:
-        ptr["old_values"] = p(None)                                           # not read without the clip
-    for k in INPUTS:
-        if k in over:
-            ptr[k] = p(None)
-    rc = L.tg_ppo_loss(ptr["mean"], ptr["log_std"], over.get("stride", A if per_row else 0), ptr["values"], ptr["actions"], ptr["old_log_prob"],
-                       ptr["advantages"], ptr["returns"], ptr["old_values"], over.get("B", B), over.get("A", A),
-                       over.get("clip_range", kw["clip_range"]), -1.0 if clip_vf is None else clip_vf, kw["ent_coef"], kw["vf_coef"],
-                       1 if kw["normalize_advantage"] else 0, path, p(outs.get("stats")), p(outs.get("log_prob")), p(outs.get("dmean")),
-                       p(outs.get("dlog_std")), p(outs.get("dvalues")), p(None) if over.get("no_workspace") else p(work), nbytes, _stream())
-    torch.cuda.synchronize()
-    for g in list(dev.values()) + list(outs.values()) + [work]:
-        assert g.guards_intact()
-    for k, g in dev.items():
-        assert _bits(g.host(f32), inp[k].reshape(-1)), k                      # the inputs are unchanged
-    if expect_error:
-        assert rc != 0 and L.tg_last_error().decode().startswith("tg_ppo_loss:")
-        for k, g in outs.items():
-            assert bool((g.payload() == PATTERN).all()), k                    # nothing was written
-        assert bool((work.payload() == PATTERN).all())
-        return None
-    capi.check(rc)
-    shapes = dict(stats=(8,), log_prob=(B,), dmean=(B, A), dlog_std=(B, A) if per_row else (A,), dvalues=(B,))
-    return {k: g.host(f32).reshape(shapes[k]) for k, g in outs.items()}
 
 
 def _named(got):
@@ -186,19 +122,6 @@ def test_error_returns_write_nothing():
     assert np.isfinite(ok["stats"]).all()
 
 
-def _head(mode, mean, ls, seed, counter, clamp=(-np.inf, np.inf), noise_in=None):
-    """tg_action_head -> (actions, log_prob, noise), host float32."""
-    capi, L = _lib()
-    B, A = mean.shape
-    keep = [Guarded(mean.nbytes, fill=mean), Guarded(ls.nbytes, fill=ls)] + ([Guarded(noise_in.nbytes, fill=noise_in)] if noise_in is not None else [])
-    outs = [Guarded(4 * B * A), Guarded(4 * B), Guarded(4 * B * A)]
-    lo, hi = (C.c_float * A)(*[-1.0] * A), (C.c_float * A)(*[1.0] * A)
-    capi.check(L.tg_action_head(p(keep[0]), p(keep[1]), A if ls.ndim == 2 else 0, B, A, lo, hi, clamp[0], clamp[1], mode, 0, seed, counter,
-                                p(keep[2]) if noise_in is not None else p(None), p(outs[0]), p(None), p(None), p(outs[1]), p(outs[2]), _stream()))
-    torch.cuda.synchronize()
-    return outs[0].host(f32).reshape(B, A), outs[1].host(f32), outs[2].host(f32).reshape(B, A)
-
-
 @pytest.mark.parametrize("B,A,per_row", [(64, 2, False), (257, 6, False), (1000, 16, True), (4097, 3, False)])
 def test_the_heads_own_sample_gives_ratio_one_exactly(B, A, per_row):
     """tg_action_head's Gaussian sample and log_prob fed back as actions and old_log_prob: the log-prob chain gives the head's bits, so
@@ -224,49 +147,6 @@ def test_the_heads_own_sample_gives_ratio_one_exactly(B, A, per_row):
 
 
 # ---------------------------------------------------------------------------------------------------------------- tg_squashed_rsample
-def _rsample(mean, ls, seed=0, counter=0, noise_in=None, save=True, clamp=(-20.0, 2.0), expect_error=False, null=(), **over):
-    capi, L = _lib()
-    B, A = mean.shape
-    keep = {k: Guarded(v.nbytes, fill=v) for k, v in (("mean", mean), ("ls", ls), ("noise", noise_in)) if v is not None}
-    outs = dict(actions=Guarded(4 * B * A), log_prob=Guarded(4 * B))
-    if save:
-        outs.update(eps=Guarded(4 * B * A), sigma=Guarded(4 * B * A))
-    ptr = {k: p(None) if k in null else p(v) for k, v in dict(keep, **outs).items()}
-    rc = L.tg_squashed_rsample(ptr["mean"], ptr["ls"], over.get("stride", A if ls.ndim == 2 else 0), over.get("B", B), over.get("A", A), clamp[0],
-                               clamp[1], seed, counter, ptr.get("noise", p(None)), ptr["actions"], ptr["log_prob"], ptr.get("eps", p(None)),
-                               ptr.get("sigma", p(None)), _stream())
-    torch.cuda.synchronize()
-    for g in list(keep.values()) + list(outs.values()):
-        assert g.guards_intact()
-    if expect_error:
-        assert rc != 0 and L.tg_last_error().decode().startswith("tg_squashed_rsample:")
-        assert all(bool((g.payload() == PATTERN).all()) for g in outs.values())
-        return None
-    capi.check(rc)
-    return {k: g.host(f32).reshape((B,) if k == "log_prob" else (B, A)) for k, g in outs.items()}
-
-
-def _rsample_bwd(fwd, ls, g_a, g_lp, outputs=("dmean", "dlog_std"), clamp=(-20.0, 2.0), expect_error=False, null=(), **over):
-    capi, L = _lib()
-    B, A = fwd["actions"].shape
-    keep = {k: Guarded(v.nbytes, fill=v) for k, v in (("g_a", g_a), ("g_lp", g_lp), ("actions", fwd["actions"]), ("eps", fwd["eps"]),
-                                                      ("sigma", fwd["sigma"]), ("ls", ls)) if v is not None}
-    outs = {k: Guarded(4 * B * A) for k in outputs}
-    ptr = {k: p(None) if k in null else p(v) for k, v in keep.items()}
-    rc = L.tg_squashed_rsample_bwd(ptr.get("g_a", p(None)), ptr.get("g_lp", p(None)), ptr["actions"], ptr["eps"], ptr["sigma"], ptr["ls"],
-                                   over.get("stride", A if ls.ndim == 2 else 0), over.get("B", B), over.get("A", A), clamp[0], clamp[1],
-                                   p(outs.get("dmean")), p(outs.get("dlog_std")), _stream())
-    torch.cuda.synchronize()
-    for g in list(keep.values()) + list(outs.values()):
-        assert g.guards_intact()
-    if expect_error:
-        assert rc != 0 and L.tg_last_error().decode().startswith("tg_squashed_rsample_bwd:")
-        assert all(bool((g.payload() == PATTERN).all()) for g in outs.values())
-        return None
-    capi.check(rc)
-    return {k: g.host(f32).reshape(B, A) for k, g in outs.items()}
-
-
 @pytest.mark.parametrize("B,A", [(1, 1), (2, 2), (64, 2), (255, 6), (257, 16), (1000, 6)])
 def test_rsample_is_the_heads_squashed_mode_and_its_backward_stays_within_bounds(B, A):
     inp = ref.rsample_inputs(B, A, seed=B + A)

@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 from device_guard import PATTERN, Guarded  # noqa: E402
+from rollout_device import _bits_equal, _gae  # noqa: E402
 
 OFFSETS = (0, 4, 1)                     # address classes mod 16: vector aligned, float aligned, byte aligned
 PER_BLOCK = 1024                        # units per workgroup
@@ -254,26 +255,6 @@ def test_gather_error_returns_write_nothing():
 
 
 # ---------------------------------------------------------------------------------------------------------------- GAE
-def _bits_equal(a, b):
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-
-
-def _gae(r, v, es, lv, dones, gamma, lam, T, N):
-    capi = _capi()
-    L = capi.lib()
-    dev = [Guarded(a.nbytes, 0, fill=a) for a in (r, v, es, lv, dones)]
-    adv, ret = Guarded(T * N * 4, 0), Guarded(T * N * 4, 0)
-    rc = L.tg_rollout_gae(dev[0].ptr, dev[1].ptr, dev[2].ptr, dev[3].ptr, dev[4].ptr, capi.ROLLOUT_DONES[dones.dtype.name], adv.ptr, ret.ptr, T, N,
-                          gamma, lam, _stream())
-    torch.cuda.synchronize()
-    assert rc == 0, L.tg_last_error().decode()
-    assert adv.guards_intact() and ret.guards_intact()
-    for g, a in zip(dev, (r, v, es, lv, dones)):
-        assert g.guards_intact() and np.array_equal(g.host(np.uint8), a.reshape(-1).view(np.uint8))
-    return adv.host(np.float32).reshape(T, N), ret.host(np.float32).reshape(T, N)
-
-
 def _odd_float_flags(d, seed):
     """float32 dones with the same truth as d but other values: 0.5, -3 or 1 where set, +0.0 or -0.0 where not."""
     rng = np.random.default_rng(seed)

@@ -2,7 +2,6 @@
 wavefront and the 256-row chunk, one to four critics, both sources of alpha.  Every stat, the target and every gradient against the float64
 composition of tests/sac_loss_ref.py within the bounds its docstring derives (no row left out, the input conditions asserted), a second call
 bit for bit, every subset of the nullable outputs, the exact case worked by hand, ties, done rows, extreme coefficients and the error returns."""
-import ctypes as C
 import itertools
 import os
 import sys
@@ -17,110 +16,13 @@ import sac_loss_ref as ref  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
-from device_guard import PATTERN, Guarded  # noqa: E402
+from loss_device import GAMMA, _actor, _bits, _critic, f32  # noqa: E402
 
 ROWS = (1, 2, 63, 64, 65, 255, 256, 257, 1000, 4097)
 CRITICS = (1, 2, 3, 4)
-GAMMA, TARGET_ENTROPY = 0.95, -2.0
+TARGET_ENTROPY = -2.0
 CRITIC_KEYS = ("critic_loss", "ent_coef", "target_q_mean", "min_next_q_mean", "mse", "target", "dq_cur")
 ACTOR_KEYS = ("actor_loss", "ent_coef_loss", "ent_coef", "log_prob_mean", "min_q_pi_mean", "dlog_ent_coef", "dlog_prob", "dq_pi")
-f32 = np.float32
-p = lambda g: C.c_void_p(g.ptr if g is not None else None)   # noqa: E731
-
-
-def _lib():
-    from tactile_gym_amd import _capi
-    return _capi, _capi.lib()
-
-
-def _bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _array(guards, null=()):
-    """A host array of device pointers; null: positions passed as NULL."""
-    return (C.c_void_p * max(1, len(guards)))(*[None if (g is None or k in null) else g.ptr for k, g in enumerate(guards)])
-
-
-def _flat(inp, src):
-    """name -> float32 array for every device input of a call."""
-    out = {}
-    for k, v in inp.items():
-        if isinstance(v, list):
-            out.update({f"{k}{i}": q for i, q in enumerate(v)})
-        else:
-            out[k] = v
-    if "log_ent_coef" in src:
-        out["log_ent_coef"] = np.array([src["log_ent_coef"]], f32)
-    return out
-
-
-def _finish(L, rc, entry, flat, dev, outs, expect_error):
-    torch.cuda.synchronize()
-    for g in list(dev.values()) + list(outs.values()):
-        assert g.guards_intact()
-    for k, g in dev.items():
-        assert _bits(g.host(f32), flat[k].reshape(-1)), k                     # the inputs are unchanged
-    if expect_error:
-        assert rc != 0 and L.tg_last_error().decode().startswith(entry + ":")
-        for k, g in outs.items():
-            assert bool((g.payload() == PATTERN).all()), k                    # nothing was written
-        return True
-    return False
-
-
-def _critic(inp, src, outputs=None, expect_error=False, null=(), **over):
-    """One tg_sac_critic_loss call -> dict(stats [8], target [B], dq_cur [n, B]) of the outputs asked (dq_cur rows not asked: absent from
-    "dq" names).  outputs: a subset of ("target", "dq_cur0", ...); null: inputs or arrays passed as NULL; over: B, n."""
-    capi, L = _lib()
-    n, B = len(inp["q_cur"]), inp["rewards"].shape[0]
-    names = ("target",) + tuple(f"dq_cur{i}" for i in range(n))
-    outputs = names if outputs is None else outputs
-    flat = _flat(inp, src)
-    dev = {k: Guarded(v.nbytes, fill=v) for k, v in flat.items()}
-    outs = {"stats": Guarded(32)}
-    outs.update({k: Guarded(4 * B) for k in outputs})
-    ptr = {k: p(None) if k in null else p(g) for k, g in dev.items()}
-    q_cur = _array([dev[f"q_cur{i}"] for i in range(n)], [i for i in range(n) if f"q_cur{i}" in null])
-    q_next = _array([dev[f"q_next{i}"] for i in range(n)], [i for i in range(n) if f"q_next{i}" in null])
-    dq = _array([outs.get(f"dq_cur{i}") for i in range(n)])
-    rc = L.tg_sac_critic_loss(None if "q_cur" in null else q_cur, None if "q_next" in null else q_next, over.get("n", n), ptr["next_log_prob"],
-                              ptr["rewards"], ptr["dones"], over.get("B", B), GAMMA if "gamma" not in over else over["gamma"],
-                              ptr.get("log_ent_coef", p(None)), src.get("ent_coef", 0.0), p(None) if "stats" in null else p(outs["stats"]),
-                              p(outs.get("target")), dq if any(k.startswith("dq") for k in outputs) else None, _stream())
-    if _finish(L, rc, "tg_sac_critic_loss", flat, dev, outs, expect_error):
-        return None
-    capi.check(rc)
-    return {k: g.host(f32) for k, g in outs.items()}
-
-
-def _actor(inp, src, target_entropy=None, outputs=None, expect_error=False, null=(), **over):
-    """One tg_sac_actor_loss call -> dict(stats [8], dlog_prob [B], dq_pi0 .. [B])."""
-    capi, L = _lib()
-    n, B = len(inp["q_pi"]), inp["log_prob"].shape[0]
-    names = ("dlog_prob",) + tuple(f"dq_pi{i}" for i in range(n))
-    outputs = names if outputs is None else outputs
-    flat = _flat(inp, src)
-    dev = {k: Guarded(v.nbytes, fill=v) for k, v in flat.items()}
-    outs = {"stats": Guarded(32)}
-    outs.update({k: Guarded(4 * B) for k in outputs})
-    ptr = {k: p(None) if k in null else p(g) for k, g in dev.items()}
-    q_pi = _array([dev[f"q_pi{i}"] for i in range(n)], [i for i in range(n) if f"q_pi{i}" in null])
-    dq = _array([outs.get(f"dq_pi{i}") for i in range(n)])
-    want = over.get("want", target_entropy is not None)
-    rc = L.tg_sac_actor_loss(ptr["log_prob"], None if "q_pi" in null else q_pi, over.get("n", n), over.get("B", B), ptr.get("log_ent_coef", p(None)),
-                             src.get("ent_coef", 0.0), 0.0 if target_entropy is None else target_entropy, 1 if want else 0,
-                             p(None) if "stats" in null else p(outs["stats"]), p(outs.get("dlog_prob")),
-                             dq if any(k.startswith("dq_pi") for k in outputs) else None, _stream())
-    if _finish(L, rc, "tg_sac_actor_loss", flat, dev, outs, expect_error):
-        return None
-    capi.check(rc)
-    return {k: g.host(f32) for k, g in outs.items()}
 
 
 def _critic_named(got, n):

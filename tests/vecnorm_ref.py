@@ -29,8 +29,21 @@ def tree_sum(v):
     return (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
 
 
-def device_moments(x):
-    """(mean, variance) over axis 0 of x [n, d] in the order of k_vecnorm_partial and k_vecnorm_merge."""
+DEVICE_MISTAKES = ("merge steps from an infinite mean",)   # mean + delta nc / tot alone: inf - inf = NaN where np.mean gives inf
+
+
+def device_moments_before(x):
+    return device_moments(x, mistake=DEVICE_MISTAKES[0])
+
+
+def device_moments(x, mistake=None):
+    """(mean, variance) over axis 0 of x [n, d] in the order of k_vecnorm_partial and k_vecnorm_merge.  Where a chunk's mean or the merged
+    one is not finite the merge adds the two (inf + x = inf, as np.mean's sum; opposite infinities give NaN); mistake: the step alone."""
+    with np.errstate(all="ignore"):
+        return _device_moments(x, mistake)
+
+
+def _device_moments(x, mistake):
     x = np.asarray(x, dtype=np.float64)
     n, d = x.shape
     C = (n + CHUNK - 1) // CHUNK
@@ -47,10 +60,17 @@ def device_moments(x):
         nc = rows[c]
         delta = mean_c[c] - mean
         tot = cnt + nc
-        mean = mean + delta * nc / tot
+        step = mean + delta * nc / tot
+        mean = step if mistake else np.where(delta - delta == 0, step, mean + mean_c[c])
         m2 = m2 + m2_c[c] + delta * delta * cnt * nc / tot
         cnt = tot
     return mean, m2 / cnt
+
+
+def output_bound(y):
+    """The bound of a float32 output of normalize_obs / normalize_reward against the same float64 formula at the same float64 statistics: the
+    outputs are computed in float64 and rounded to float32 once, 2^-24 |y| (0 for an exact 0 or a clip value, which float32 holds)."""
+    return 2.0 ** -24 * np.abs(np.asarray(y, np.float64))
 
 
 class RunningMeanStd:
