@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _capi as capi
+from ._device import checked_f32, launch, ptr
 
 __all__ = ["DeviceDiagGaussian", "DeviceSquashedDiagGaussian"]
 
@@ -80,33 +81,14 @@ class _DeviceHead:
 
     def _c_head(self, mode, mean, log_std, stride, deterministic):
         """tg_action_head at (seed, counter) into the head's own tensors; mean / log_std: None in the uniform mode."""
-        p = C.c_void_p
-        uniform = mode == capi.HEAD_UNIFORM
-        if torch.cuda.current_device() != self.device.index:
-            with torch.cuda.device(self.device):
-                return self._c_head(mode, mean, log_std, stride, deterministic)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        capi.check(capi.lib().tg_action_head(p(None if uniform else mean.data_ptr()), p(None if uniform else log_std.data_ptr()), stride,
-                                             self.num_envs, self.action_dim, self._lo, self._hi, self.log_std_min, self.log_std_max, mode,
-                                             1 if deterministic else 0, self.seed, self.counter, p(None), p(self.actions.data_ptr()),
-                                             p(self.env_actions.data_ptr()), p(None if uniform else self.gaussian_actions.data_ptr()),
-                                             p(None if uniform else self.log_prob.data_ptr()), p(self.noise.data_ptr()), p(stream)))
+        own = (None, None) if mode == capi.HEAD_UNIFORM else (self.gaussian_actions, self.log_prob)
+        launch("tg_action_head", self.device, ptr(mean), ptr(log_std), stride, self.num_envs, self.action_dim, self._lo, self._hi,
+               self.log_std_min, self.log_std_max, mode, 1 if deterministic else 0, self.seed, self.counter, ptr(None), ptr(self.actions),
+               ptr(self.env_actions), ptr(own[0]), ptr(own[1]), ptr(self.noise))
 
     # ------------------------------------------------------------------ sampling
     def _checked(self, x, name, shapes):
-        if not isinstance(x, torch.Tensor):
-            raise TypeError(f"{name} must be a torch tensor, got {type(x).__name__}")
-        if x.dtype != torch.float32:
-            raise ValueError(f"{name} must be float32, got {x.dtype}")
-        if tuple(x.shape) not in shapes:
-            raise ValueError(f"{name} must have shape {' or '.join(str(s) for s in shapes)}, got {tuple(x.shape)}")
-        if not self._is_device(x):
-            raise ValueError(f"{name} must be on the ROCm device (there is no CPU path), got {x.device}")
-        if self.device is not None and x.device != self.device:
-            raise ValueError(f"{name} must be on the head's device {self.device}, got {x.device}")
-        if not x.is_contiguous():
-            raise ValueError(f"{name} must be contiguous (a copy would be a launch and a temporary of its own)")
-        return x.detach()
+        return checked_f32(x, name, shapes, self.device, "the head's device", self._is_device).detach()
 
     def sample(self, mean, log_std, deterministic=False):
         """(actions, env_actions, log_prob): float32 [N, A], [N, A], [N], the head's own tensors, valid until the next call.  mean: float32

@@ -24,6 +24,7 @@ import ctypes as C
 import torch
 
 from . import _capi as capi
+from ._device import call, check_f32_like, check_images, on_device, ptr, stream_of
 
 __all__ = ["random_translate", "RandomTranslate", "RandomAffine", "augment_images", "random_affine", "RandomWarp", "RandomRotation"]
 
@@ -37,19 +38,6 @@ def _pair(v, name):
     if len(v) != 2:
         raise ValueError(f"{name} must be a number or a pair, got {v}")
     return v
-
-
-def _check_images(x, name="x"):
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name} must be a torch tensor, got {type(x).__name__}")
-    if x.dtype not in _DTYPES:
-        raise TypeError(f"{name} must be uint8 or float32, got {x.dtype}")
-    if not x.is_cuda:
-        raise ValueError(f"{name} must be on the ROCm device (there is no CPU path), got {x.device}")
-    if x.dim() != 4:
-        raise ValueError(f"{name} must be a 4-D image batch, got shape {tuple(x.shape)}")
-    if not x.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
 
 
 def _unit(p):
@@ -67,21 +55,14 @@ def _chw(shape, channels_first):
 def _out_like(x, out):
     if out is None:
         return torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    _check_images(out, "out")
+    check_images(out, "out")
     if out.dtype != torch.float32 or out.shape != x.shape or out.device != x.device:
         raise ValueError("out must be a float32 tensor of the input's shape on its device")
     return out
 
 
 def _f32_tensor(t, name, shape, x):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError(f"{name} must be a float32 torch tensor")
-    if tuple(t.shape) != shape or t.device != x.device or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous {list(shape)} tensor on the input's device")
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None else None)
+    check_f32_like(t, name, shape, x, where="the input's device", got=False)
 
 
 def _u64(v):
@@ -90,9 +71,8 @@ def _u64(v):
 
 def _translate_call(x, out, rows, B, Cn, H, W, channels_first, translate, p, seed, counter, params, pout, stream):
     """The one place that lays out tg_random_translate_rows' arguments (random_translate, rows=None, and the device buffers' fused gathers)."""
-    capi.check(capi.lib().tg_random_translate_rows(
-        _ptr(x), _ptr(out), _DTYPES[x.dtype], int(bool(channels_first)), B, Cn, H, W, translate[0], translate[1], p, _u64(seed), _u64(counter),
-        _ptr(params), _ptr(pout), _ptr(rows), C.c_void_p(stream)))
+    call("tg_random_translate_rows", ptr(x), ptr(out), _DTYPES[x.dtype], int(bool(channels_first)), B, Cn, H, W, translate[0], translate[1], p,
+         _u64(seed), _u64(counter), ptr(params), ptr(pout), ptr(rows), C.c_void_p(stream))
 
 
 def random_translate(x, translate=(0.05, 0.05), p=0.5, seed=0, counter=0, params=None, channels_first=True, out=None, return_params=False):
@@ -101,7 +81,7 @@ def random_translate(x, translate=(0.05, 0.05), p=0.5, seed=0, counter=0, params
     translate: (ax, ay) in [0, 1], fractions of W and H; p: the probability that a sample is warped.  (seed, counter) pick the draws: element
     3 b + k of tg_sample_actions' generator.  params: an optional float32 [B, 3] device tensor of (apply, tx, ty) per sample (tx, ty in pixels)
     used instead of the draws.  return_params=True returns (out, params) with the [B, 3] values that were used."""
-    _check_images(x)
+    check_images(x)
     ax, ay = _pair(translate, "translate")
     if not (0.0 <= ax <= 1.0 and 0.0 <= ay <= 1.0):
         raise ValueError(f"translate must lie in [0, 1], got {(ax, ay)}")
@@ -109,9 +89,9 @@ def random_translate(x, translate=(0.05, 0.05), p=0.5, seed=0, counter=0, params
     if params is not None:
         _f32_tensor(params, "params", (B, 3), x)
     pout = torch.empty((B, 3), dtype=torch.float32, device=x.device) if return_params else None
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _translate_call(x, out, None, B, *_chw(x.shape[1:], channels_first), channels_first, (ax, ay), p, seed, counter, params, pout, stream)
+    with on_device(x.device):
+        _translate_call(x, out, None, B, *_chw(x.shape[1:], channels_first), channels_first, (ax, ay), p, seed, counter, params, pout,
+                        stream_of(x.device).value)
     return (out, pout) if return_params else out
 
 
@@ -123,11 +103,10 @@ class _FusedModule(torch.nn.Module):
     """A module whose call is one `_fused` launch: draws (seed, counter), advances the counter, sets `_params`."""
 
     def forward(self, x):
-        _check_images(x)
+        check_images(x)
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            self._fused(x, out, None, x.shape[0], *_chw(x.shape[1:], self.channels_first), self.channels_first,
-                        torch.cuda.current_stream(x.device).cuda_stream)
+        with on_device(x.device):
+            self._fused(x, out, None, x.shape[0], *_chw(x.shape[1:], self.channels_first), self.channels_first, stream_of(x.device).value)
         return out
 
 
@@ -209,9 +188,9 @@ def _affine_call(x, out, rows, B, Cn, H, W, channels_first, ranges, p, seed, cou
     """The one place that lays out tg_random_affine_rows' arguments (random_affine and the device buffers' fused gathers)."""
     (ax, ay), (d0, d1), (sc, has_y), sh = ranges
     s2, s3 = (sc[2], sc[3]) if has_y else (0.0, 0.0)
-    capi.check(capi.lib().tg_random_affine_rows(
-        _ptr(x), _ptr(out), _DTYPES[x.dtype], int(bool(channels_first)), B, Cn, H, W, ax, ay, d0, d1, sc[0], sc[1], s2, s3, sh[0], sh[1], sh[2],
-        sh[3], p, _u64(seed), _u64(counter), _ptr(params), _ptr(pout), _ptr(coeffs), _ptr(cout), _ptr(rows), C.c_void_p(stream)))
+    call("tg_random_affine_rows", ptr(x), ptr(out), _DTYPES[x.dtype], int(bool(channels_first)), B, Cn, H, W, ax, ay, d0, d1, sc[0], sc[1], s2,
+         s3, sh[0], sh[1], sh[2], sh[3], p, _u64(seed), _u64(counter), ptr(params), ptr(pout), ptr(coeffs), ptr(cout), ptr(rows),
+         C.c_void_p(stream))
 
 
 _centers = {}   # (H, W, device) -> float32 [1, 2] on the device: uploaded once, not per call
@@ -235,7 +214,7 @@ def random_affine(x, degrees=0.0, translate=None, scale=None, shear=None, p=0.5,
     device tensor (apply, tx, ty, angle, scale_x, scale_y, shear_x, shear_y) used instead of the draws; coeffs: an optional float32 [B, 6]
     device tensor (a00, a01, a02, a10, a11, a12) of source-coordinate coefficients used as they are (only `apply` then comes from the
     parameters).  return_params=True returns (out, params, coeffs) with the [B, 8] and [B, 6] values that were used."""
-    _check_images(x)
+    check_images(x)
     ranges = (_translate_pair(translate), _degrees_range(degrees), _scale_range(scale), _shear_range(shear))
     p, B, out = _unit(p), x.shape[0], _out_like(x, out)
     if params is not None:
@@ -244,10 +223,9 @@ def random_affine(x, degrees=0.0, translate=None, scale=None, shear=None, p=0.5,
         _f32_tensor(coeffs, "coeffs", (B, 6), x)
     pout = torch.empty((B, 8), dtype=torch.float32, device=x.device) if return_params else None
     cout = torch.empty((B, 6), dtype=torch.float32, device=x.device) if return_params else None
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
+    with on_device(x.device):
         _affine_call(x, out, None, B, *_chw(x.shape[1:], channels_first), channels_first, ranges, p, seed, counter, params, pout, coeffs, cout,
-                     stream)
+                     stream_of(x.device).value)
     return (out, pout, cout) if return_params else out
 
 

@@ -18,38 +18,16 @@ inputs (csrc/tg_loss_head.hip).
 reads it.  The gradients are the fused ones of the kernel (torch autograd's rules written out), scaled by the incoming gradient; advantages,
 returns, old values and old log-probs are data and get none.  The arithmetic is restated in tests/loss_head_ref.py.  There is no CPU path.
 """
-import ctypes as C
-
 import torch
 
 from . import _capi as capi
+from ._device import checked_f32, launch, ptr, ptrs, workspace
 
 __all__ = ["ppo_loss", "squashed_rsample", "sac_critic_loss", "sac_actor_loss", "STATS", "SAC_CRITIC_STATS", "SAC_ACTOR_STATS"]
 
 STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std")
 SAC_CRITIC_STATS = ("critic_loss", "ent_coef", "target_q_mean", "min_next_q_mean", "mse_0", "mse_1", "mse_2", "mse_3")
 SAC_ACTOR_STATS = ("actor_loss", "ent_coef_loss", "ent_coef", "log_prob_mean", "min_q_pi_mean", "dlog_ent_coef", "unused_6", "unused_7")
-
-
-def _checked(x, name, shapes, device=None):
-    """What the action heads refuse (action_head._checked); the tensor itself comes back, with its autograd history."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"{name} must be a torch tensor, got {type(x).__name__}")
-    if x.dtype != torch.float32:
-        raise ValueError(f"{name} must be float32, got {x.dtype}")
-    if tuple(x.shape) not in shapes:
-        raise ValueError(f"{name} must have shape {' or '.join(str(s) for s in shapes)}, got {tuple(x.shape)}")
-    if not x.is_cuda:
-        raise ValueError(f"{name} must be on the ROCm device (there is no CPU path), got {x.device}")
-    if device is not None and x.device != device:
-        raise ValueError(f"{name} must be on the device {device}, got {x.device}")
-    if not x.is_contiguous():
-        raise ValueError(f"{name} must be contiguous (a copy would be a launch and a temporary of its own)")
-    return x
-
-
-def _ptr(t):
-    return C.c_void_p(None if t is None else t.data_ptr())
 
 
 class _PpoLoss(torch.autograd.Function):
@@ -64,16 +42,11 @@ class _PpoLoss(torch.autograd.Function):
         dls = torch.empty_like(log_std) if need[1] else None
         dvalues = torch.empty_like(values) if need[2] else None
         grid = path == capi.LOSS_PATH_GRID or (path == capi.LOSS_PATH_AUTO and B > capi.LOSS_ONE_MAX_ROWS)
-        nbytes = capi.lib().tg_ppo_loss_workspace(B, A) if grid else 0
-        if nbytes < 0:
-            capi.check(int(nbytes))
+        nbytes = workspace("tg_ppo_loss_workspace", B, A) if grid else 0
         work = torch.empty(nbytes, dtype=torch.uint8, device=mean.device) if grid else None
-        with torch.cuda.device(mean.device):
-            stream = torch.cuda.current_stream(mean.device).cuda_stream
-            capi.check(capi.lib().tg_ppo_loss(_ptr(mean), _ptr(log_std), 0 if log_std.dim() == 1 else A, _ptr(values), _ptr(actions),
-                                              _ptr(old_log_prob), _ptr(advantages), _ptr(returns), _ptr(old_values), B, A, clip_range,
-                                              clip_range_vf, ent_coef, vf_coef, 1 if normalize_advantage else 0, path, _ptr(stats), _ptr(None),
-                                              _ptr(dmean), _ptr(dls), _ptr(dvalues), _ptr(work), nbytes, C.c_void_p(stream)))
+        launch("tg_ppo_loss", mean.device, ptr(mean), ptr(log_std), 0 if log_std.dim() == 1 else A, ptr(values), ptr(actions),
+               ptr(old_log_prob), ptr(advantages), ptr(returns), ptr(old_values), B, A, clip_range, clip_range_vf, ent_coef, vf_coef,
+               1 if normalize_advantage else 0, path, ptr(stats), ptr(None), ptr(dmean), ptr(dls), ptr(dvalues), ptr(work), nbytes)
         ctx.grads = (dmean, dls, dvalues)
         ctx.mark_non_differentiable(stats)
         return stats[0], stats
@@ -95,22 +68,22 @@ def ppo_loss(mean, log_std, values, actions, old_log_prob, advantages, returns, 
     if not isinstance(mean, torch.Tensor):
         raise TypeError(f"mean must be a torch tensor, got {type(mean).__name__}")
     B, A = (int(mean.shape[0]), int(mean.shape[1])) if mean.dim() == 2 else (-1, -1)
-    mean = _checked(mean, "mean", [(B, A)])
+    mean = checked_f32(mean, "mean", [(B, A)])
     if B < 1 or not 1 <= A <= capi.HEAD_MAX_ACT:
         raise ValueError(f"mean must be [B, A] with B >= 1 and 1 <= A <= {capi.HEAD_MAX_ACT}, got {tuple(mean.shape)}")
     dev = mean.device
-    log_std = _checked(log_std, "log_std", [(A,), (B, A)], dev)
-    values = _checked(values, "values", [(B,)], dev)
-    actions = _checked(actions, "actions", [(B, A)], dev).detach()
-    old_log_prob = _checked(old_log_prob, "old_log_prob", [(B,)], dev).detach()
-    advantages = _checked(advantages, "advantages", [(B,)], dev).detach()
-    returns = _checked(returns, "returns", [(B,)], dev).detach()
+    log_std = checked_f32(log_std, "log_std", [(A,), (B, A)], dev)
+    values = checked_f32(values, "values", [(B,)], dev)
+    actions = checked_f32(actions, "actions", [(B, A)], dev).detach()
+    old_log_prob = checked_f32(old_log_prob, "old_log_prob", [(B,)], dev).detach()
+    advantages = checked_f32(advantages, "advantages", [(B,)], dev).detach()
+    returns = checked_f32(returns, "returns", [(B,)], dev).detach()
     if clip_range_vf is not None:
         if old_values is None:
             raise ValueError("clip_range_vf needs old_values")
         if not clip_range_vf >= 0:
             raise ValueError(f"clip_range_vf must be None or >= 0, got {clip_range_vf}")
-        old_values = _checked(old_values, "old_values", [(B,)], dev).detach()
+        old_values = checked_f32(old_values, "old_values", [(B,)], dev).detach()
     else:
         old_values = None
     if not clip_range >= 0:
@@ -129,10 +102,8 @@ class _SquashedRsample(torch.autograd.Function):
         actions, log_prob = torch.empty_like(mean), torch.empty(B, dtype=torch.float32, device=mean.device)
         eps = torch.empty_like(mean) if save else None
         sigma = torch.empty_like(mean) if save else None
-        with torch.cuda.device(mean.device):
-            stream = torch.cuda.current_stream(mean.device).cuda_stream
-            capi.check(capi.lib().tg_squashed_rsample(_ptr(mean), _ptr(log_std), stride, B, A, ls_min, ls_max, seed, counter, _ptr(noise),
-                                                      _ptr(actions), _ptr(log_prob), _ptr(eps), _ptr(sigma), C.c_void_p(stream)))
+        launch("tg_squashed_rsample", mean.device, ptr(mean), ptr(log_std), stride, B, A, ls_min, ls_max, seed, counter, ptr(noise),
+               ptr(actions), ptr(log_prob), ptr(eps), ptr(sigma))
         if save:
             ctx.save_for_backward(actions, eps, sigma, log_std)
             ctx.clamp = (ls_min, ls_max)
@@ -147,11 +118,8 @@ class _SquashedRsample(torch.autograd.Function):
         need_mean, need_ls = ctx.needs_input_grad[:2]
         dmean = torch.empty_like(actions) if need_mean else None
         dls = torch.empty_like(actions) if need_ls else None
-        with torch.cuda.device(actions.device):
-            stream = torch.cuda.current_stream(actions.device).cuda_stream
-            capi.check(capi.lib().tg_squashed_rsample_bwd(_ptr(g_a), _ptr(g_lp), _ptr(actions), _ptr(eps), _ptr(sigma), _ptr(log_std),
-                                                          0 if log_std.dim() == 1 else A, B, A, ctx.clamp[0], ctx.clamp[1], _ptr(dmean), _ptr(dls),
-                                                          C.c_void_p(stream)))
+        launch("tg_squashed_rsample_bwd", actions.device, ptr(g_a), ptr(g_lp), ptr(actions), ptr(eps), ptr(sigma), ptr(log_std),
+               0 if log_std.dim() == 1 else A, B, A, ctx.clamp[0], ctx.clamp[1], ptr(dmean), ptr(dls))
         if dls is not None and log_std.dim() == 1:
             dls = dls.sum(dim=0)                      # a state-independent log_std [A] (not SAC's): the rows' sum, on torch
         return dmean, dls, None, None, None, None, None
@@ -164,21 +132,16 @@ def squashed_rsample(mean, log_std, log_std_min=-20.0, log_std_max=2.0, seed=0, 
     if not isinstance(mean, torch.Tensor):
         raise TypeError(f"mean must be a torch tensor, got {type(mean).__name__}")
     B, A = (int(mean.shape[0]), int(mean.shape[1])) if mean.dim() == 2 else (-1, -1)
-    mean = _checked(mean, "mean", [(B, A)])
+    mean = checked_f32(mean, "mean", [(B, A)])
     if B < 1 or not 1 <= A <= capi.HEAD_MAX_ACT:
         raise ValueError(f"mean must be [B, A] with B >= 1 and 1 <= A <= {capi.HEAD_MAX_ACT}, got {tuple(mean.shape)}")
-    log_std = _checked(log_std, "log_std", [(A,), (B, A)], mean.device)
+    log_std = checked_f32(log_std, "log_std", [(A,), (B, A)], mean.device)
     if noise is not None:
-        noise = _checked(noise, "noise", [(B, A)], mean.device).detach()
+        noise = checked_f32(noise, "noise", [(B, A)], mean.device).detach()
     return _SquashedRsample.apply(mean, log_std, float(log_std_min), float(log_std_max), int(seed), int(counter), noise)
 
 
 # ---------------------------------------------------------------------------------------------------------------- SAC's losses
-def _ptrs(tensors):
-    """A host array of device pointers (NULL for None): how the C entries take the critics' separate tensors."""
-    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
-
-
 def _critic_outputs(qs, name, B=None, device=None):
     """A tuple or list of 1 .. SAC_MAX_CRITICS tensors [B] or [B, 1] -> (list, B)."""
     if not isinstance(qs, (tuple, list)):
@@ -191,8 +154,8 @@ def _critic_outputs(qs, name, B=None, device=None):
         B = int(qs[0].shape[0]) if qs[0].dim() in (1, 2) else -1
         if not 1 <= B <= capi.SAC_MAX_ROWS:
             raise ValueError(f"{name}[0] must have shape [B] or [B, 1] with 1 <= B <= {capi.SAC_MAX_ROWS}, got {tuple(qs[0].shape)}")
-        device = _checked(qs[0], f"{name}[0]", [(B,), (B, 1)]).device
-    return [_checked(q, f"{name}[{i}]", [(B,), (B, 1)], device) for i, q in enumerate(qs)], B
+        device = checked_f32(qs[0], f"{name}[0]", [(B,), (B, 1)]).device
+    return [checked_f32(q, f"{name}[{i}]", [(B,), (B, 1)], device) for i, q in enumerate(qs)], B
 
 
 def _alpha_source(log_ent_coef, ent_coef, device):
@@ -201,7 +164,7 @@ def _alpha_source(log_ent_coef, ent_coef, device):
         raise ValueError("give exactly one of log_ent_coef (a device tensor) and ent_coef (a float)")
     if log_ent_coef is None:
         return None, float(ent_coef)
-    return _checked(log_ent_coef, "log_ent_coef", [(), (1,)], device), 0.0
+    return checked_f32(log_ent_coef, "log_ent_coef", [(), (1,)], device), 0.0
 
 
 class _SacCriticLoss(torch.autograd.Function):
@@ -211,10 +174,8 @@ class _SacCriticLoss(torch.autograd.Function):
         B, dev = q_cur[0].shape[0], q_cur[0].device
         stats = torch.empty(8, dtype=torch.float32, device=dev)
         grads = [torch.empty_like(q) if need else None for q, need in zip(q_cur, ctx.needs_input_grad[7 + n:])]
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            capi.check(capi.lib().tg_sac_critic_loss(_ptrs(q_cur), _ptrs(q_next), n, _ptr(next_log_prob), _ptr(rewards), _ptr(dones), B, gamma,
-                                                     _ptr(log_ent_coef), ent_coef, _ptr(stats), _ptr(None), _ptrs(grads), C.c_void_p(stream)))
+        launch("tg_sac_critic_loss", dev, ptrs(q_cur), ptrs(q_next), n, ptr(next_log_prob), ptr(rewards), ptr(dones), B, gamma,
+               ptr(log_ent_coef), ent_coef, ptr(stats), ptr(None), ptrs(grads))
         ctx.grads = grads
         ctx.mark_non_differentiable(stats)
         return stats[0], stats
@@ -239,9 +200,9 @@ def sac_critic_loss(q_cur, q_next, next_log_prob, rewards, dones, gamma, log_ent
     if len(q_next) != len(q_cur):
         raise ValueError(f"q_cur and q_next must hold the same number of tensors, got {len(q_cur)} and {len(q_next)}")
     rows = [(B,), (B, 1)]
-    next_log_prob = _checked(next_log_prob, "next_log_prob", rows, dev).detach()
-    rewards = _checked(rewards, "rewards", rows, dev).detach()
-    dones = _checked(dones, "dones", rows, dev).detach()
+    next_log_prob = checked_f32(next_log_prob, "next_log_prob", rows, dev).detach()
+    rewards = checked_f32(rewards, "rewards", rows, dev).detach()
+    dones = checked_f32(dones, "dones", rows, dev).detach()
     log_ent_coef, ent_coef = _alpha_source(log_ent_coef, ent_coef, dev)
     if log_ent_coef is not None:
         log_ent_coef = log_ent_coef.detach()
@@ -257,11 +218,8 @@ class _SacActorLoss(torch.autograd.Function):
         stats = torch.empty(8, dtype=torch.float32, device=dev)
         need = ctx.needs_input_grad
         grads = [torch.empty_like(log_prob) if need[4] else None] + [torch.empty_like(q) if nd else None for q, nd in zip(q_pi, need[5:])]
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            capi.check(capi.lib().tg_sac_actor_loss(_ptr(log_prob), _ptrs(q_pi), n, B, _ptr(log_ent_coef), ent_coef,
-                                                    target_entropy if want else 0.0, 1 if want else 0, _ptr(stats), _ptr(grads[0]),
-                                                    _ptrs(grads[1:]), C.c_void_p(stream)))
+        launch("tg_sac_actor_loss", dev, ptr(log_prob), ptrs(q_pi), n, B, ptr(log_ent_coef), ent_coef, target_entropy if want else 0.0,
+               1 if want else 0, ptr(stats), ptr(grads[0]), ptrs(grads[1:]))
         ctx.grads = grads
         ctx.dlec = stats[5].reshape(log_ent_coef.shape) if want and need[3] else None      # the launch wrote it into the stats
         ctx.mark_non_differentiable(stats)
@@ -288,7 +246,7 @@ def sac_actor_loss(log_prob, q_pi, log_ent_coef=None, ent_coef=None, target_entr
     if not isinstance(log_prob, torch.Tensor):
         raise TypeError(f"log_prob must be a torch tensor, got {type(log_prob).__name__}")
     B = int(log_prob.shape[0]) if log_prob.dim() in (1, 2) else -1
-    log_prob = _checked(log_prob, "log_prob", [(B,), (B, 1)])
+    log_prob = checked_f32(log_prob, "log_prob", [(B,), (B, 1)])
     if not 1 <= B <= capi.SAC_MAX_ROWS:
         raise ValueError(f"log_prob must have shape [B] or [B, 1] with 1 <= B <= {capi.SAC_MAX_ROWS}, got {tuple(log_prob.shape)}")
     dev = log_prob.device

@@ -16,7 +16,6 @@ backward pass are taken in a fixed order: the same bits on every run.
 Device tensors run the HIP kernels on torch's current stream.  CPU tensors take a plain-torch path of the same meaning (F.linear and torch's
 activations) that is not bit-specified: SB3 can save, load and evaluate the modules on the host.
 """
-import ctypes as C
 import math
 
 import torch
@@ -25,6 +24,7 @@ import torch.nn.functional as F
 from torch.autograd.function import once_differentiable
 
 from . import _capi as capi
+from ._device import addr, check_f32_like, launch, workspace
 
 __all__ = ["mlp_towers", "ActorCriticHeads", "SacActorHeads", "ContinuousCriticHeads"]
 
@@ -37,13 +37,6 @@ def _act_name(act):
     if isinstance(act, str) and act.lower() in capi.MLP_ACT:
         return act.lower()
     raise ValueError(f"activation {act!r}: None, 'none', 'tanh' or 'relu' are built")
-
-
-def _check_param(t, name, shape, x):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise TypeError(f"{name} must be a float32 torch tensor")
-    if tuple(t.shape) != tuple(shape) or t.device != x.device or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous {list(shape)} tensor on x's device, got {list(t.shape)} on {t.device}")
 
 
 def _check_x(x):
@@ -96,21 +89,17 @@ def _check(x, towers):
             out, out2 = int(w.shape[0]), (int(w2.shape[0]) if isinstance(w2, torch.Tensor) and w2.dim() == 2 else 0)
             if not 1 <= out or out + out2 > capi.MLP_MAX_WIDTH:
                 raise ValueError(f"tower {t} layer {l} is {out + out2} wide: widths above {capi.MLP_MAX_WIDTH} are not built")
-            _check_param(w, f"tower {t} layer {l} weight", (out, width), blocks[0])
-            _check_param(b, f"tower {t} layer {l} bias", (out,), blocks[0])
+            check_f32_like(w, f"tower {t} layer {l} weight", (out, width), blocks[0])
+            check_f32_like(b, f"tower {t} layer {l} bias", (out,), blocks[0])
             if w2 is not None:
-                _check_param(w2, f"tower {t} layer {l} weight2", (out2, width), blocks[0])
-                _check_param(b2, f"tower {t} layer {l} bias2", (out2,), blocks[0])
+                check_f32_like(w2, f"tower {t} layer {l} weight2", (out2, width), blocks[0])
+                check_f32_like(b2, f"tower {t} layer {l} bias2", (out2,), blocks[0])
                 if out2 < 1:
                     raise ValueError(f"tower {t} layer {l}: the second row block is empty")
             layers.append((w, b, _act_name(act), w2, b2))
             width = out
         spec.append(layers)
     return blocks, spec
-
-
-def _addr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def _descriptors(acts, params, hs, grads=None, dys=None):
@@ -120,15 +109,15 @@ def _descriptors(acts, params, hs, grads=None, dys=None):
     for t, tower in enumerate(acts):
         arr[t].n_layers = len(tower)
         if dys is not None:
-            arr[t].dy, arr[t].dy2 = _addr(dys[t][0]), _addr(dys[t][1])
+            arr[t].dy, arr[t].dy2 = addr(dys[t][0]), addr(dys[t][1])
         for l, act in enumerate(tower):
             ly = arr[t].layer[l]
             w, b, w2, b2 = params[t][l]
-            ly.weight, ly.bias, ly.weight2, ly.bias2 = _addr(w), _addr(b), _addr(w2), _addr(b2)
+            ly.weight, ly.bias, ly.weight2, ly.bias2 = addr(w), addr(b), addr(w2), addr(b2)
             ly.in_, ly.out, ly.out2, ly.act = w.shape[1], w.shape[0], (w2.shape[0] if w2 is not None else 0), capi.MLP_ACT[act]
-            ly.h, ly.h2 = _addr(hs[t][l][0]), _addr(hs[t][l][1])
+            ly.h, ly.h2 = addr(hs[t][l][0]), addr(hs[t][l][1])
             if grads is not None:
-                ly.dweight, ly.dbias, ly.dweight2, ly.dbias2 = (_addr(g) for g in grads[t][l])
+                ly.dweight, ly.dbias, ly.dweight2, ly.dbias2 = (addr(g) for g in grads[t][l])
     return arr
 
 
@@ -148,10 +137,7 @@ def _run_forward(x0, x1, acts, params, save_all):
     if B == 0:                                                            # nothing to launch (an empty tensor has no address to pass)
         return hs
     arr = _descriptors(acts, params, hs)
-    with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        capi.check(capi.lib().tg_mlp_forward(_addr(x0), x0.shape[1], _addr(x1), x1.shape[1] if x1 is not None else 0, B, arr, len(acts),
-                                             int(save_all), C.c_void_p(stream)))
+    launch("tg_mlp_forward", dev, addr(x0), x0.shape[1], addr(x1), x1.shape[1] if x1 is not None else 0, B, arr, len(acts), int(save_all))
     return hs
 
 
@@ -236,16 +222,11 @@ class _MlpTowers(torch.autograd.Function):
         if B == 0:
             return (None, None, None, *dx, *flat_grads)
         arr = _descriptors(acts, params, hs, grads, dys)
-        L = capi.lib()
         Ka, Kb = x0.shape[1], (x1.shape[1] if x1 is not None else 0)
-        nbytes = L.tg_mlp_backward_workspace(B, Ka, Kb, arr, len(meta))
-        if nbytes < 0:
-            capi.check(int(nbytes))
-        work = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            capi.check(L.tg_mlp_backward(_addr(x0), Ka, _addr(x1), Kb, B, arr, len(meta), _addr(dx[0]), _addr(dx[1]) if n_blocks == 2 else None,
-                                         _addr(work), int(nbytes), C.c_void_p(stream)))
+        nbytes = workspace("tg_mlp_backward_workspace", B, Ka, Kb, arr, len(meta))
+        work = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+        launch("tg_mlp_backward", dev, addr(x0), Ka, addr(x1), Kb, B, arr, len(meta), addr(dx[0]), addr(dx[1]) if n_blocks == 2 else None,
+               addr(work), nbytes)
         return (None, None, None, *dx, *flat_grads)
 
 

@@ -29,8 +29,9 @@ import numpy as np
 import torch
 
 from . import _capi as capi
-from .augment import _chw, _gather_images, _unwrap_augment
-from .rollout import DeviceRolloutBuffer, _space_shapes
+from ._device import call, launch, on_device, ptr, stream_of
+from .augment import _chw, _gather_images
+from .rollout import _DeviceBuffer, _positive_int
 from .vecnorm import DeviceVecNormalize
 
 __all__ = ["DeviceReplayBuffer", "ReplayBufferSamples"]
@@ -40,45 +41,20 @@ ReplayBufferSamples = collections.namedtuple("ReplayBufferSamples", ["observatio
 _M64 = 0xFFFFFFFFFFFFFFFF
 
 
-class DeviceReplayBuffer:
+class DeviceReplayBuffer(_DeviceBuffer):
     """stable_baselines3's ReplayBuffer / DictReplayBuffer in device memory (constructor arguments in SB3's positional order).  channels_first:
     the layout of the image keys, as in DeviceRolloutBuffer; seed: of sample()'s counter-based draw."""
 
     def __init__(self, buffer_size, observation_space, action_space, device="cuda", n_envs=1, optimize_memory_usage=False,
                  handle_timeout_termination=True, channels_first=None, seed=0):
-        if isinstance(buffer_size, bool) or int(buffer_size) != buffer_size or int(buffer_size) < 1:
-            raise ValueError(f"buffer_size must be a positive integer, got {buffer_size!r}")
-        if isinstance(n_envs, bool) or int(n_envs) != n_envs or int(n_envs) < 1:
-            raise ValueError(f"n_envs must be a positive integer, got {n_envs!r}")
         if optimize_memory_usage:
             raise NotImplementedError("optimize_memory_usage=True is not built (SB3's DictReplayBuffer refuses it as well)")
-        self.n_envs = int(n_envs)
+        super().__init__(buffer_size, observation_space, action_space, device, n_envs, channels_first)
         self.buffer_size = max(int(buffer_size) // self.n_envs, 1)          # SB3: the ring's length in steps
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ValueError(f"device must be the ROCm device (there is no CPU path), got {self.device}")
         self.optimize_memory_usage = False
         self.handle_timeout_termination = bool(handle_timeout_termination)
-        self.observation_space, self.action_space = observation_space, action_space
-        self._obs_spec = _space_shapes(observation_space, "observation_space")
-        self._dict_obs = None not in self._obs_spec
-        act = _space_shapes(action_space, "action_space")
-        if None not in act or act[None][1] != torch.float32 or len(act[None][0]) != 1:
-            raise TypeError(f"action_space must be a float32 Box of one dimension, got {action_space!r}")
-        self.action_dim = act[None][0][0]
         if 2 * len(self._obs_spec) + 4 > capi.ROLLOUT_MAX_ARRAYS:
             raise ValueError(f"observation_space has {len(self._obs_spec)} keys, at most {(capi.ROLLOUT_MAX_ARRAYS - 4) // 2} are built")
-        self._image_keys = [k for k, (shape, dt) in self._obs_spec.items() if dt == torch.uint8 and len(shape) == 3]
-        if channels_first is not None and not isinstance(channels_first, (bool, np.bool_)):
-            raise ValueError(f"channels_first={channels_first!r}: True, False or None")
-        self._channels_first = {}
-        for k in self._image_keys:
-            shape = self._obs_spec[k][0]
-            cf = bool(np.argmin(shape) == 0) if channels_first is None else bool(channels_first)
-            c, h, w = shape if cf else (shape[2], shape[0], shape[1])
-            if h < 2 or w < 2:
-                raise ValueError(f"observation_space key {k!r}: image keys need H, W >= 2, got shape {shape} (channels_first={cf})")
-            self._channels_first[k] = cf
         T, N = self.buffer_size, self.n_envs
         if T >= 1 << 31 or N >= 1 << 31:
             raise ValueError(f"buffer_size // n_envs = {T} and n_envs = {N} must be below 2^31")
@@ -112,30 +88,11 @@ class DeviceReplayBuffer:
         buf._venv = venv
         return buf
 
-    def _alloc(self, shape, dtype):
-        return torch.zeros(shape, dtype=dtype, device=self.device)
-
-    _input, _place, _on_device, _device_index = (DeviceRolloutBuffer._input, DeviceRolloutBuffer._place, DeviceRolloutBuffer._on_device,
-                                                 DeviceRolloutBuffer._device_index)
-
-    def size(self):
-        return self.buffer_size if self.full else self.pos
-
     def reset(self):
         """Empty the ring (the storage keeps its contents) and forget a pending carry; the draw counter moves on."""
         self.pos, self.full, self._carry = 0, False, False
 
     # ------------------------------------------------------------------ add
-    def _obs_inputs(self, obs, name):
-        N = self.n_envs
-        if self._dict_obs:
-            if not isinstance(obs, dict) or set(obs) != set(self._obs_spec):
-                raise ValueError(f"{name} must be a dict with the keys {sorted(self._obs_spec)}, got "
-                                 f"{sorted(obs) if isinstance(obs, dict) else type(obs).__name__}")
-            return [self._input(obs[k], f"{name}[{k!r}]", (N,) + shape, (dt,)) for k, (shape, dt) in self._obs_spec.items()]
-        shape, dt = self._obs_spec[None]
-        return [self._input(obs, name, (N,) + shape, (dt,))]
-
     def _transition_inputs(self, next_obs, action, reward, done, infos, terminal_obs, timeouts):
         """Every argument of add() / add_next() after `obs`, checked and then placed: (next_obs list, terminal list or None, action, reward,
         done as uint8, timeouts, select or None)."""
@@ -171,11 +128,7 @@ class DeviceReplayBuffer:
             flag = s.dtype == torch.uint8 and d.dtype == torch.float32       # done / timeout flags as uint8
             kind_tab[i] = capi.ROLLOUT_FLAG_U8 if flag else capi.ROLLOUT_COPY
             bytes_tab[i] = s.numel() * s.element_size() // N
-        dev = self._device_index()
-        with self._on_device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            capi.check(capi.lib().tg_replay_add(len(arrays), src_tab, alt_tab, dst_tab, bytes_tab, kind_tab, N,
-                                                C.c_void_p(select.data_ptr() if select is not None else None), C.c_void_p(stream)))
+        launch("tg_replay_add", self._device_index(), len(arrays), src_tab, alt_tab, dst_tab, bytes_tab, kind_tab, N, ptr(select))
 
     def _advance(self):
         self.pos += 1
@@ -246,7 +199,7 @@ class DeviceReplayBuffer:
         src[2 * K + 2], row_bytes[2 * K + 2], kinds[2 * K + 2] = rd[1].data_ptr(), 1, capi.ROLLOUT_FLAG_U8
         src[2 * K + 3], row_bytes[2 * K + 3], kinds[2 * K + 3] = self._no_timeouts.data_ptr(), 4, capi.ROLLOUT_COPY   # this env never truncates
         self._env_tab = dict(n=n, K=K, src=src, alt=alt, dst=(C.c_void_p * n)(), row_bytes=row_bytes, kinds=kinds, dst_base=dst_base,
-                             slot_bytes=slot_bytes, select=C.c_void_p(rd[1].data_ptr() if term is not None else None),
+                             slot_bytes=slot_bytes, select=ptr(rd[1] if term is not None else None),
                              target=getattr(venv, "_obs_sel", 0), keep=(obs, term, rd))
 
     def add_from_env(self, actions):
@@ -271,10 +224,7 @@ class DeviceReplayBuffer:
         for j in range(tab["n"]):
             dst[j] = base[j] + (q if K <= j < 2 * K else p) * slot[j]
         tab["src"][2 * K] = actions.data_ptr()
-        with self._on_device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            capi.check(capi.lib().tg_replay_add(tab["n"], tab["src"], tab["alt"], dst, tab["row_bytes"], tab["kinds"], self.n_envs, tab["select"],
-                                                C.c_void_p(stream)))
+        launch("tg_replay_add", dev, tab["n"], tab["src"], tab["alt"], dst, tab["row_bytes"], tab["kinds"], self.n_envs, tab["select"])
         self._advance()
 
     # ------------------------------------------------------------------ sample
@@ -300,28 +250,21 @@ class DeviceReplayBuffer:
         and next_observations and the rewards in one more launch (image keys and `augment` are not touched by it)."""
         if env is not None and not isinstance(env, DeviceVecNormalize):
             raise NotImplementedError(f"sample(env=...): only a tactile_gym_amd DeviceVecNormalize is built, got {type(env).__name__}")
-        if isinstance(batch_size, bool) or int(batch_size) != batch_size or int(batch_size) < 1:
-            raise ValueError(f"batch_size must be a positive integer, got {batch_size!r}")
-        module = _unwrap_augment(augment) if augment is not None else None
-        if out_dtype not in (torch.float32, torch.uint8):
-            raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
-        if module is not None and out_dtype != torch.float32:
-            raise ValueError("out_dtype must be torch.float32 with augment (the augmentation writes float32)")
+        B = _positive_int(batch_size, "batch_size")
+        module = self._image_options(augment, out_dtype)
         M, first = self._slot_range()
-        B, T, N = int(batch_size), self.buffer_size, self.n_envs
+        T, N = self.buffer_size, self.n_envs
         dev = self._device_index()
-        L = capi.lib()
         obs, nxt, plain = {}, {}, []              # plain: (pair [2, T, N, ...], destination [2 B, ...]) of the one k_rollout_gather launch
         whole = {}                                # their destinations by key: what sample(env=) normalises
-        with self._on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with on_device(dev):
+            stream = stream_of(dev)
             rows = torch.empty((2 * B,), dtype=torch.int64, device=dev)
             actions = torch.empty((B, self.action_dim), dtype=torch.float32, device=dev)
             rewards, dones = torch.empty((B, 1), dtype=torch.float32, device=dev), torch.empty((B, 1), dtype=torch.float32, device=dev)
-            capi.check(L.tg_replay_draw(B, M, first, T, N, C.c_uint64(self.seed & _M64), C.c_uint64(self.counter & _M64),
-                                        C.c_void_p(self.actions.data_ptr()), self.action_dim, C.c_void_p(self.rewards.data_ptr()),
-                                        C.c_void_p(self.dones.data_ptr()), C.c_void_p(self.timeouts.data_ptr()), T * N, C.c_void_p(rows.data_ptr()),
-                                        C.c_void_p(actions.data_ptr()), C.c_void_p(rewards.data_ptr()), C.c_void_p(dones.data_ptr()), stream))
+            call("tg_replay_draw", B, M, first, T, N, C.c_uint64(self.seed & _M64), C.c_uint64(self.counter & _M64), ptr(self.actions),
+                 self.action_dim, ptr(self.rewards), ptr(self.dones), ptr(self.timeouts), T * N, ptr(rows), ptr(actions), ptr(rewards),
+                 ptr(dones), stream)
             self.counter += 1
             for k, (shape, dt) in self._obs_spec.items():
                 src = self._pair[k]
@@ -335,11 +278,7 @@ class DeviceReplayBuffer:
                     whole[k] = out
                 obs[k], nxt[k] = out[:B], out[B:]
             if plain:
-                n = len(plain)
-                src_tab, dst_tab, bytes_tab = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int64 * n)()
-                for i, (s, d) in enumerate(plain):
-                    src_tab[i], dst_tab[i], bytes_tab[i] = s.data_ptr(), d.data_ptr(), s[0, 0, 0].numel() * s.element_size()
-                capi.check(L.tg_rollout_gather(n, src_tab, dst_tab, bytes_tab, C.c_void_p(rows.data_ptr()), 2 * B, stream))
+                self._gather_plain(plain, rows, stream)
             if env is not None:                                # after the gather: both halves of every vector key and the rewards, in place
                 env._normalize_sample(whole, rewards)
         if not self._dict_obs:

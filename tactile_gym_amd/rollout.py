@@ -25,13 +25,13 @@ sample) come out of get() as float32 with values 0 ... 255, the convention of ta
 compute_returns_and_advantage is restated bit for bit in tests/rollout_ref.py.  There is no CPU path: a CPU device raises.
 """
 import collections
-import contextlib
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _capi as capi
+from ._device import call, launch, on_device, ptr, stream_of
 from .augment import _chw, _gather_images, _unwrap_augment
 
 __all__ = ["DeviceRolloutBuffer", "RolloutBufferSamples", "flat_rows"]
@@ -65,21 +65,23 @@ def _space_shapes(space, name):
     return out
 
 
-class DeviceRolloutBuffer:
-    """stable_baselines3's RolloutBuffer / DictRolloutBuffer in device memory (constructor arguments in SB3's positional order).  channels_first:
-    the layout of the image keys ([C, H, W] or [H, W, C] per sample), needed by get(augment=...); None applies SB3's rule
-    (is_image_space_channels_first: the smallest of the three dimensions comes first)."""
+def _positive_int(v, name, tail=""):
+    if isinstance(v, bool) or int(v) != v or int(v) < 1:
+        raise ValueError(f"{name} must be a positive integer{tail}, got {v!r}")
+    return int(v)
 
-    def __init__(self, buffer_size, observation_space, action_space, device="cuda", gae_lambda=1.0, gamma=0.99, n_envs=1, channels_first=None):
-        if isinstance(buffer_size, bool) or int(buffer_size) != buffer_size or int(buffer_size) < 1:
-            raise ValueError(f"buffer_size must be a positive integer, got {buffer_size!r}")
-        if isinstance(n_envs, bool) or int(n_envs) != n_envs or int(n_envs) < 1:
-            raise ValueError(f"n_envs must be a positive integer, got {n_envs!r}")
-        self.buffer_size, self.n_envs = int(buffer_size), int(n_envs)
+
+class _DeviceBuffer:
+    """What DeviceRolloutBuffer and DeviceReplayBuffer share: the constructor's checks up to the image keys' layout table, the checks of what
+    add() and get() / sample() are handed, and the tg_rollout_gather launch.  A subclass sets `buffer_size` (in steps), checks its own
+    ROLLOUT_MAX_ARRAYS budget and allocates."""
+
+    def __init__(self, buffer_size, observation_space, action_space, device, n_envs, channels_first):
+        _positive_int(buffer_size, "buffer_size")
+        self.n_envs = _positive_int(n_envs, "n_envs")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError(f"device must be the ROCm device (there is no CPU path), got {self.device}")
-        self.gae_lambda, self.gamma = float(gae_lambda), float(gamma)
         self.observation_space, self.action_space = observation_space, action_space
         self._obs_spec = _space_shapes(observation_space, "observation_space")
         self._dict_obs = None not in self._obs_spec
@@ -87,8 +89,6 @@ class DeviceRolloutBuffer:
         if None not in act or act[None][1] != torch.float32 or len(act[None][0]) != 1:
             raise TypeError(f"action_space must be a float32 Box of one dimension, got {action_space!r}")
         self.action_dim = act[None][0][0]
-        if len(self._obs_spec) + 5 > capi.ROLLOUT_MAX_ARRAYS:
-            raise ValueError(f"observation_space has {len(self._obs_spec)} keys, at most {capi.ROLLOUT_MAX_ARRAYS - 5} are built")
         self._image_keys = [k for k, (shape, dt) in self._obs_spec.items() if dt == torch.uint8 and len(shape) == 3]
         if channels_first is not None and not isinstance(channels_first, (bool, np.bool_)):
             raise ValueError(f"channels_first={channels_first!r}: True, False or None")
@@ -100,35 +100,19 @@ class DeviceRolloutBuffer:
             if h < 2 or w < 2:
                 raise ValueError(f"observation_space key {k!r}: image keys need H, W >= 2, got shape {shape} (channels_first={cf})")
             self._channels_first[k] = cf
-        T, N = self.buffer_size, self.n_envs
-        self._obs = {k: self._alloc((T, N) + shape, dt) for k, (shape, dt) in self._obs_spec.items()}
-        self.observations = self._obs if self._dict_obs else self._obs[None]
-        self.actions = self._alloc((T, N, self.action_dim), torch.float32)
-        for name in ("rewards", "episode_starts", "values", "log_probs", "advantages", "returns"):
-            setattr(self, name, self._alloc((T, N), torch.float32))
-        self._add_dst = list(self._obs.values()) + [self.actions, self.rewards, self.episode_starts, self.values, self.log_probs]
-        self._add_slot_bytes = [t[0].numel() * t.element_size() for t in self._add_dst]
-        n = len(self._add_dst)
-        self._tab = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int64 * n)(), (C.c_int32 * n)()
-        self.pos, self.full = 0, False
-
-    @classmethod
-    def for_env(cls, venv, n_steps, gamma=0.99, gae_lambda=1.0):
-        """The buffer of a TactileVecEnv: its spaces, num_envs, device and image layout."""
-        return cls(n_steps, venv.observation_space, venv.action_space, device=torch.device("cuda", venv._cfg.device), gae_lambda=gae_lambda,
-                   gamma=gamma, n_envs=venv.num_envs, channels_first=bool(venv.channels_first))
 
     def _alloc(self, shape, dtype):
         return torch.zeros(shape, dtype=dtype, device=self.device)
 
-    def reset(self):
-        """Start a new rollout.  The storage keeps its contents (every slot is rewritten before the buffer is full again)."""
-        self.pos, self.full = 0, False
-
     def size(self):
         return self.buffer_size if self.full else self.pos
 
-    # ------------------------------------------------------------------ add
+    def _device_index(self):
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        return self.device
+
+    # ------------------------------------------------------------------ what add() is handed
     def _input(self, x, name, shape, dtypes):
         """`x` checked as a contiguous tensor of `shape` and one of `dtypes`: (tensor, name, whether it came from numpy and still has to be
         uploaded).  _place() does the device half, after every argument of a call has passed this one."""
@@ -164,28 +148,79 @@ class DeviceRolloutBuffer:
             raise ValueError(f"{name} must be on the buffer's device ({self.device}; there is no CPU path), got {x.device}")
         return x
 
-    def _on_device(self, dev):
-        """torch.cuda.device(dev), or nothing when it is the current device already (the context manager costs more than the launch)."""
-        return contextlib.nullcontext() if torch.cuda.current_device() == dev.index else torch.cuda.device(dev)
+    def _obs_inputs(self, obs, name):
+        """_input over an observation: every key of a Dict space (the dict's keys checked first), or the one tensor of a Box."""
+        N = self.n_envs
+        if self._dict_obs:
+            if not isinstance(obs, dict) or set(obs) != set(self._obs_spec):
+                raise ValueError(f"{name} must be a dict with the keys {sorted(self._obs_spec)}, got "
+                                 f"{sorted(obs) if isinstance(obs, dict) else type(obs).__name__}")
+            return [self._input(obs[k], f"{name}[{k!r}]", (N,) + shape, (dt,)) for k, (shape, dt) in self._obs_spec.items()]
+        shape, dt = self._obs_spec[None]
+        return [self._input(obs, name, (N,) + shape, (dt,))]
 
-    def _device_index(self):
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        return self.device
+    # ------------------------------------------------------------------ what get() / sample() are handed, and their plain gather
+    @staticmethod
+    def _image_options(augment, out_dtype):
+        """The module of `augment` (None for None) after the checks of out_dtype and of the two together."""
+        module = _unwrap_augment(augment) if augment is not None else None
+        if out_dtype not in (torch.float32, torch.uint8):
+            raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
+        if module is not None and out_dtype != torch.float32:
+            raise ValueError("out_dtype must be torch.float32 with augment (the augmentation writes float32)")
+        return module
 
+    @staticmethod
+    def _gather_plain(plain, rows, stream):
+        """One k_rollout_gather launch on `stream`: for every (source, destination [B, ...]) of `plain`, destination[b] = the source's storage
+        row rows[b] (a row is one destination sample: the source's leading dimensions are the row index)."""
+        n, B = len(plain), rows.numel()
+        src_tab, dst_tab, bytes_tab = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int64 * n)()
+        for i, (s, d) in enumerate(plain):
+            src_tab[i], dst_tab[i], bytes_tab[i] = s.data_ptr(), d.data_ptr(), d.numel() // B * d.element_size()
+        call("tg_rollout_gather", n, src_tab, dst_tab, bytes_tab, ptr(rows), B, stream)
+
+
+class DeviceRolloutBuffer(_DeviceBuffer):
+    """stable_baselines3's RolloutBuffer / DictRolloutBuffer in device memory (constructor arguments in SB3's positional order).  channels_first:
+    the layout of the image keys ([C, H, W] or [H, W, C] per sample), needed by get(augment=...); None applies SB3's rule
+    (is_image_space_channels_first: the smallest of the three dimensions comes first)."""
+
+    def __init__(self, buffer_size, observation_space, action_space, device="cuda", gae_lambda=1.0, gamma=0.99, n_envs=1, channels_first=None):
+        super().__init__(buffer_size, observation_space, action_space, device, n_envs, channels_first)
+        self.buffer_size = int(buffer_size)
+        self.gae_lambda, self.gamma = float(gae_lambda), float(gamma)
+        if len(self._obs_spec) + 5 > capi.ROLLOUT_MAX_ARRAYS:
+            raise ValueError(f"observation_space has {len(self._obs_spec)} keys, at most {capi.ROLLOUT_MAX_ARRAYS - 5} are built")
+        T, N = self.buffer_size, self.n_envs
+        self._obs = {k: self._alloc((T, N) + shape, dt) for k, (shape, dt) in self._obs_spec.items()}
+        self.observations = self._obs if self._dict_obs else self._obs[None]
+        self.actions = self._alloc((T, N, self.action_dim), torch.float32)
+        for name in ("rewards", "episode_starts", "values", "log_probs", "advantages", "returns"):
+            setattr(self, name, self._alloc((T, N), torch.float32))
+        self._add_dst = list(self._obs.values()) + [self.actions, self.rewards, self.episode_starts, self.values, self.log_probs]
+        self._add_slot_bytes = [t[0].numel() * t.element_size() for t in self._add_dst]
+        n = len(self._add_dst)
+        self._tab = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int64 * n)(), (C.c_int32 * n)()
+        self.pos, self.full = 0, False
+
+    @classmethod
+    def for_env(cls, venv, n_steps, gamma=0.99, gae_lambda=1.0):
+        """The buffer of a TactileVecEnv: its spaces, num_envs, device and image layout."""
+        return cls(n_steps, venv.observation_space, venv.action_space, device=torch.device("cuda", venv._cfg.device), gae_lambda=gae_lambda,
+                   gamma=gamma, n_envs=venv.num_envs, channels_first=bool(venv.channels_first))
+
+    def reset(self):
+        """Start a new rollout.  The storage keeps its contents (every slot is rewritten before the buffer is full again)."""
+        self.pos, self.full = 0, False
+
+    # ------------------------------------------------------------------ add
     def add(self, obs, action, reward, episode_start, value, log_prob):
         """Write slot `pos` and advance it: one launch on torch's current stream when every argument is a device tensor.  The inputs are only read."""
         if self.full:
             raise RuntimeError(f"add to a full rollout buffer (buffer_size={self.buffer_size}): call reset() first")
         N = self.n_envs
-        if self._dict_obs:
-            if not isinstance(obs, dict) or set(obs) != set(self._obs_spec):
-                raise ValueError(f"obs must be a dict with the keys {sorted(self._obs_spec)}, got "
-                                 f"{sorted(obs) if isinstance(obs, dict) else type(obs).__name__}")
-            srcs = [self._input(obs[k], f"obs[{k!r}]", (N,) + shape, (dt,)) for k, (shape, dt) in self._obs_spec.items()]
-        else:
-            shape, dt = self._obs_spec[None]
-            srcs = [self._input(obs, "obs", (N,) + shape, (dt,))]
+        srcs = self._obs_inputs(obs, "obs")
         srcs.append(self._input(action, "action", (N, self.action_dim), (torch.float32,)))
         srcs.append(self._input(reward, "reward", (N,), (torch.float32,)))
         srcs.append(self._input(episode_start, "episode_start", (N,), (torch.float32, torch.uint8, torch.bool)))
@@ -200,10 +235,7 @@ class DeviceRolloutBuffer:
             flag = s.dtype == torch.uint8 and d.dtype == torch.float32           # the episode starts as the env's uint8 done flags
             kind_tab[i] = capi.ROLLOUT_FLAG_U8 if flag else capi.ROLLOUT_COPY
             bytes_tab[i] = s.numel() * s.element_size()
-        dev = self._device_index()
-        with self._on_device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            capi.check(capi.lib().tg_rollout_add(len(srcs), src_tab, dst_tab, bytes_tab, kind_tab, C.c_void_p(stream)))
+        launch("tg_rollout_add", self._device_index(), len(srcs), src_tab, dst_tab, bytes_tab, kind_tab)
         self.pos += 1
         if self.pos == self.buffer_size:
             self.full = True
@@ -218,14 +250,9 @@ class DeviceRolloutBuffer:
         lv, dn = self._place(lv), self._place(dn)
         if dn.dtype == torch.bool:
             dn = dn.view(torch.uint8)
-        dev = self._device_index()
-        with self._on_device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            capi.check(capi.lib().tg_rollout_gae(
-                C.c_void_p(self.rewards.data_ptr()), C.c_void_p(self.values.data_ptr()), C.c_void_p(self.episode_starts.data_ptr()),
-                C.c_void_p(lv.data_ptr()), C.c_void_p(dn.data_ptr()), capi.ROLLOUT_DONES["uint8" if dn.dtype == torch.uint8 else "float32"],
-                C.c_void_p(self.advantages.data_ptr()), C.c_void_p(self.returns.data_ptr()), self.buffer_size, N, self.gamma, self.gae_lambda,
-                C.c_void_p(stream)))
+        launch("tg_rollout_gae", self._device_index(), ptr(self.rewards), ptr(self.values), ptr(self.episode_starts), ptr(lv), ptr(dn),
+               capi.ROLLOUT_DONES["uint8" if dn.dtype == torch.uint8 else "float32"], ptr(self.advantages), ptr(self.returns), self.buffer_size,
+               N, self.gamma, self.gae_lambda)
 
     # ------------------------------------------------------------------ get
     def get(self, batch_size=None, augment=None, indices=None, out_dtype=torch.float32, generator=None):
@@ -236,17 +263,10 @@ class DeviceRolloutBuffer:
         minibatch being one call of the module (its counter advances, `_params` is set); out_dtype=torch.uint8 without augment keeps them uint8."""
         if not self.full:
             raise RuntimeError(f"get() needs a full rollout buffer: {self.pos} of {self.buffer_size} steps added")
-        module = _unwrap_augment(augment) if augment is not None else None
-        if out_dtype not in (torch.float32, torch.uint8):
-            raise TypeError(f"out_dtype must be torch.float32 or torch.uint8, got {out_dtype}")
-        if module is not None and out_dtype != torch.float32:
-            raise ValueError("out_dtype must be torch.float32 with augment (the augmentation writes float32)")
+        module = self._image_options(augment, out_dtype)
         T, N = self.buffer_size, self.n_envs
         total = T * N
-        if batch_size is None:
-            batch_size = total
-        if isinstance(batch_size, bool) or int(batch_size) != batch_size or int(batch_size) < 1:
-            raise ValueError(f"batch_size must be a positive integer or None, got {batch_size!r}")
+        batch_size = _positive_int(total if batch_size is None else batch_size, "batch_size", " or None")
         if indices is not None:
             if isinstance(indices, np.ndarray):
                 indices = torch.from_numpy(indices)
@@ -258,7 +278,7 @@ class DeviceRolloutBuffer:
         else:
             indices = torch.randperm(total, device=self._device_index(), generator=generator)
         rows = flat_rows(indices, T, N).contiguous()
-        return self._batches(rows, int(batch_size), module, out_dtype)
+        return self._batches(rows, batch_size, module, out_dtype)
 
     def _batches(self, rows, batch_size, module, out_dtype):
         for start in range(0, rows.numel(), batch_size):
@@ -267,10 +287,9 @@ class DeviceRolloutBuffer:
     def _gather(self, rows, module, out_dtype):
         B = rows.numel()
         dev = self._device_index()
-        L = capi.lib()
         obs, plain = {}, []                       # plain: (source [T, N, ...], destination [B, ...]) of the one k_rollout_gather launch
-        with self._on_device(dev):
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with on_device(dev):
+            stream = stream_of(dev)
             for k, (shape, dt) in self._obs_spec.items():
                 src = self._obs[k]
                 if k in self._image_keys and out_dtype == torch.float32:
@@ -286,9 +305,5 @@ class DeviceRolloutBuffer:
                 out = torch.empty((B,) + tuple(src.shape[2:]), dtype=torch.float32, device=dev)
                 plain.append((src, out))
                 fields.append(out)
-            n = len(plain)
-            src_tab, dst_tab, bytes_tab = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int64 * n)()
-            for i, (s, d) in enumerate(plain):
-                src_tab[i], dst_tab[i], bytes_tab[i] = s.data_ptr(), d.data_ptr(), s[0, 0].numel() * s.element_size()
-            capi.check(L.tg_rollout_gather(n, src_tab, dst_tab, bytes_tab, C.c_void_p(rows.data_ptr()), B, stream))
+            self._gather_plain(plain, rows, stream)
         return RolloutBufferSamples(obs if self._dict_obs else obs[None], *fields)

@@ -19,14 +19,13 @@ What reaches the module, and the scale that goes with it:
 Device tensors run the HIP kernels on torch's current stream.  CPU tensors take a plain-torch path of the same meaning (F.conv2d on
 x.float() * scale, then relu) that is not bit-specified: SB3 can save, load and evaluate the module on the host.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _capi as capi
+from ._device import check_f32_like, check_images, launch, ptr, workspace
 from .vec_env import _optional_base
 
 __all__ = ["conv_stem", "ConvStem", "NatureCNN"]
@@ -36,15 +35,8 @@ _FeaturesBase = _optional_base("stable_baselines3.common.torch_layers", "BaseFea
 
 
 def _check_stem(x, weight, bias, channels_first):
-    """(Cn, H, W) of the batch x after augment._check_images' checks (a CPU tensor is allowed here) and the parameters' own."""
-    if not isinstance(x, torch.Tensor):
-        raise TypeError(f"x must be a torch tensor, got {type(x).__name__}")
-    if x.dtype not in (torch.uint8, torch.float32):
-        raise TypeError(f"x must be uint8 or float32, got {x.dtype}")
-    if x.dim() != 4:
-        raise ValueError(f"x must be a 4-D image batch, got shape {tuple(x.shape)}")
-    if not x.is_contiguous():
-        raise ValueError("x must be contiguous")
+    """(Cn, H, W) of the batch x after _device.check_images' checks (a CPU tensor is allowed here), its own, and the parameters'."""
+    check_images(x, allow_cpu=True)
     if x.requires_grad:
         raise ValueError("x requires a gradient: the conv stem treats its input as data and computes none")
     Cn, H, W = tuple(x.shape[1:]) if channels_first else (x.shape[3], x.shape[1], x.shape[2])
@@ -53,19 +45,12 @@ def _check_stem(x, weight, bias, channels_first):
     if H < capi.STEM_KERNEL or W < capi.STEM_KERNEL:
         raise ValueError(f"x is {H} x {W}: the 8 x 8 kernel needs H, W >= 8")
     for t, name, shape in ((weight, "weight", (capi.STEM_OUT, Cn, capi.STEM_KERNEL, capi.STEM_KERNEL)), (bias, "bias", (capi.STEM_OUT,))):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-            raise TypeError(f"{name} must be a float32 torch tensor")
-        if tuple(t.shape) != shape or t.device != x.device or not t.is_contiguous():
-            raise ValueError(f"{name} must be a contiguous {list(shape)} tensor on x's device, got {list(t.shape)} on {t.device}")
+        check_f32_like(t, name, shape, x)
     return Cn, H, W
 
 
 def _out_hw(H, W):
     return (H - capi.STEM_KERNEL) // capi.STEM_STRIDE + 1, (W - capi.STEM_KERNEL) // capi.STEM_STRIDE + 1
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
 
 
 class _ConvStem(torch.autograd.Function):
@@ -74,10 +59,8 @@ class _ConvStem(torch.autograd.Function):
         B = x.shape[0]
         Cn, H, W = tuple(x.shape[1:]) if channels_first else (x.shape[3], x.shape[1], x.shape[2])
         y = torch.empty((B, capi.STEM_OUT) + _out_hw(H, W), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            capi.check(capi.lib().tg_conv_stem(_ptr(x), int(x.dtype == torch.float32), int(channels_first), B, Cn, H, W, _ptr(weight.detach()),
-                                               _ptr(bias.detach()), scale, _ptr(y), C.c_void_p(stream)))
+        launch("tg_conv_stem", x.device, ptr(x), int(x.dtype == torch.float32), int(channels_first), B, Cn, H, W, ptr(weight.detach()),
+               ptr(bias.detach()), scale, ptr(y))
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:          # under no_grad, or with frozen parameters, nothing is kept
             ctx.save_for_backward(x, y)
             ctx.stem = (bool(channels_first), scale, Cn, H, W)
@@ -94,15 +77,10 @@ class _ConvStem(torch.autograd.Function):
         alloc = torch.empty if B else torch.zeros                         # B = 0 launches nothing: the gradients are zero
         dweight = alloc((capi.STEM_OUT, Cn, capi.STEM_KERNEL, capi.STEM_KERNEL), dtype=torch.float32, device=x.device)
         dbias = alloc((capi.STEM_OUT,), dtype=torch.float32, device=x.device)
-        L = capi.lib()
-        nbytes = L.tg_conv_stem_bwd_workspace(B, Cn, H, W)
-        if nbytes < 0:
-            capi.check(int(nbytes))
-        work = torch.empty((max(int(nbytes), 1),), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            capi.check(L.tg_conv_stem_bwd(_ptr(x), int(x.dtype == torch.float32), int(channels_first), B, Cn, H, W, _ptr(y), _ptr(dy), scale,
-                                          _ptr(dweight), _ptr(dbias), _ptr(work), int(nbytes), C.c_void_p(stream)))
+        nbytes = workspace("tg_conv_stem_bwd_workspace", B, Cn, H, W)
+        work = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=x.device)
+        launch("tg_conv_stem_bwd", x.device, ptr(x), int(x.dtype == torch.float32), int(channels_first), B, Cn, H, W, ptr(y), ptr(dy), scale,
+               ptr(dweight), ptr(dbias), ptr(work), nbytes)
         return None, dweight, dbias, None, None
 
 

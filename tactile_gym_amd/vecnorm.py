@@ -23,6 +23,7 @@ import torch
 
 from . import _capi as capi
 from . import spaces
+from ._device import launch, ptr
 
 __all__ = ["DeviceVecNormalize", "DeviceRunningMeanStd"]
 
@@ -101,21 +102,15 @@ class DeviceVecNormalize:
         self._tab = (C.c_void_p * n)(), (C.c_void_p * n)(), (C.c_int32 * n)(*widths), (C.c_void_p * n)(*[r.block.data_ptr() for r in self.obs_rms.values()])
 
     # ------------------------------------------------------------------ the two C entries (tests replace these two methods)
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _c_update(self, arrays, with_returns):
         """tg_vecnorm_update: `arrays`, one [N, d] float32 tensor per normalised key (or none of them); with_returns: the returns recurrence
         with the env's reward buffer and the update of ret_rms."""
         x_tab, _, w_tab, s_tab = self._tab
         for i, x in enumerate(arrays):
             x_tab[i] = x.data_ptr()
-        p = C.c_void_p
-        capi.check(capi.lib().tg_vecnorm_update(len(arrays), x_tab, w_tab, s_tab, self.num_envs,
-                                                p(self.returns.data_ptr() if with_returns else None),
-                                                p(self._rd[0].data_ptr() if with_returns else None), self.gamma,
-                                                p(self.ret_rms.block.data_ptr() if with_returns else None), p(self._scratch.data_ptr()),
-                                                self._stream()))
+        ret = (self.returns, self._rd[0], self.ret_rms.block) if with_returns else (None, None, None)
+        launch("tg_vecnorm_update", self.device, len(arrays), x_tab, w_tab, s_tab, self.num_envs, ptr(ret[0]), ptr(ret[1]), self.gamma,
+               ptr(ret[2]), ptr(self._scratch))
 
     def _c_apply(self, pairs, rows, rewards=None, rewards_out=None, reset=None):
         """tg_vecnorm_apply: `pairs`, one (x, out) of [rows, d] float32 tensors per normalised key (or none); rewards -> rewards_out (any equal
@@ -123,14 +118,10 @@ class DeviceVecNormalize:
         x_tab, o_tab, w_tab, s_tab = self._tab
         for i, (x, o) in enumerate(pairs):
             x_tab[i], o_tab[i] = x.data_ptr(), o.data_ptr()
-        p = C.c_void_p
-        capi.check(capi.lib().tg_vecnorm_apply(len(pairs), x_tab, o_tab, w_tab, s_tab, rows, self.clip_obs, self.epsilon,
-                                               p(rewards.data_ptr() if rewards is not None else None),
-                                               p(rewards_out.data_ptr() if rewards is not None else None),
-                                               rewards.numel() if rewards is not None else 0, p(self.ret_rms.block.data_ptr()), self.clip_reward,
-                                               p(self.returns.data_ptr() if reset else None),
-                                               p(self._rd[1].data_ptr() if reset == "done" else None), self.num_envs if reset else 0,
-                                               self._stream()))
+        launch("tg_vecnorm_apply", self.device, len(pairs), x_tab, o_tab, w_tab, s_tab, rows, self.clip_obs, self.epsilon, ptr(rewards),
+               ptr(rewards_out if rewards is not None else None), rewards.numel() if rewards is not None else 0, ptr(self.ret_rms.block),
+               self.clip_reward, ptr(self.returns if reset else None), ptr(self._rd[1] if reset == "done" else None),
+               self.num_envs if reset else 0)
 
     # ------------------------------------------------------------------ VecEnv surface
     def __getattr__(self, name):           # everything else is the env's (frame_stack, channels_first, sample_actions, _cfg ...)

@@ -211,3 +211,113 @@ def test_env_visuotactile_keys_through_augment_images():
         _steps(v, 1, seed=2, reset=False)
     finally:
         v.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- every family's stream argument
+def _cuda(values, dtype=np.float32, grad=False):
+    t = torch.from_numpy(np.asarray(values, dtype=dtype)).cuda()
+    return t.requires_grad_() if grad else t
+
+
+def _family_calls(tg):
+    """[(name, call)]: one wrapper of each family that launches through tactile_gym_amd._device at the smallest shape its
+    kernel accepts.  A call makes its inputs from fixed values, seeds and counters on the current stream and returns the tensors it produced."""
+    from tactile_gym_amd import spaces
+    rng = lambda: np.random.default_rng(7)  # noqa: E731
+    act = spaces.Box(low=-1.0, high=1.0, shape=(1,), dtype=np.float32)
+    obs_space = spaces.Dict({"tactile": spaces.Box(low=0, high=255, shape=(1, 8, 8), dtype=np.uint8),
+                             "oracle": spaces.Box(low=-1.0, high=1.0, shape=(3,), dtype=np.float32)})
+
+    def obs(seed):
+        r = np.random.default_rng(seed)
+        return {"tactile": _cuda(r.integers(0, 256, (1, 1, 8, 8)), np.uint8), "oracle": _cuda(r.uniform(-1, 1, (1, 3)))}
+
+    def ppo():                                                                   # B = 2, A = 1
+        mean, log_std, values = _cuda([[0.1], [-0.2]], grad=True), _cuda([-0.5], grad=True), _cuda([0.3, 0.1], grad=True)
+        loss, stats = tg.ppo_loss(mean, log_std, values, _cuda([[0.2], [-0.4]]), _cuda([-0.9, -1.1]), _cuda([1.0, -0.5]), _cuda([0.4, 0.2]))
+        loss.backward()
+        return [stats, mean.grad, log_std.grad, values.grad]
+
+    def sac_critic():                                                            # B = 1, one critic
+        q = _cuda([0.3], grad=True)
+        loss, stats = tg.sac_critic_loss([q], [_cuda([0.5])], _cuda([-1.2]), _cuda([0.7]), _cuda([0.0]), 0.99, ent_coef=0.2)
+        loss.backward()
+        return [stats, q.grad]
+
+    def stem():                                                                  # 1 x 1 x 8 x 8: one output pixel per channel
+        r = rng()
+        x = _cuda(r.integers(0, 256, (1, 1, 8, 8)), np.uint8)
+        w, b = _cuda(r.standard_normal((32, 1, 8, 8)) * 0.1, grad=True), _cuda(r.standard_normal(32) * 0.1, grad=True)
+        y = tg.conv_stem(x, w, b)
+        y.sum().backward()
+        return [y, w.grad, b.grad]
+
+    def tower():                                                                 # B = 1, one 1 -> 1 layer
+        x, w, b = _cuda([[0.5]], grad=True), _cuda([[-0.7]], grad=True), _cuda([0.2], grad=True)
+        y, = tg.mlp_towers(x, [[(w, b, "tanh")]])
+        y.sum().backward()
+        return [y, x.grad, w.grad, b.grad]
+
+    def head():                                                                  # N = 1
+        h = tg.DeviceDiagGaussian(act, seed=3, num_envs=1, device="cuda")
+        h.counter = 5
+        return [t.clone() for t in h.sample(_cuda([[0.1]]), _cuda([-0.3]))] + [h.noise.clone()]
+
+    def rollout():                                                               # T = 1, N = 1
+        buf = tg.DeviceRolloutBuffer(1, obs_space, act, "cuda", gae_lambda=0.9, gamma=0.95, n_envs=1)
+        buf.add(obs(1), _cuda([[0.2]]), _cuda([0.5]), _cuda([1.0]), _cuda([0.3]), _cuda([-0.8]))
+        buf.compute_returns_and_advantage(_cuda([0.6]), _cuda([0], np.uint8))
+        return list(buf.observations.values()) + [buf.actions, buf.rewards, buf.episode_starts, buf.values, buf.log_probs, buf.advantages,
+                                                   buf.returns]
+
+    def replay():                                                                # one slot; sample(1): the draw, the image key, the vector key
+        buf = tg.DeviceReplayBuffer(1, obs_space, act, "cuda", n_envs=1, seed=5)
+        buf.counter = 9
+        buf.add(obs(2), obs(3), _cuda([[0.2]]), _cuda([0.5]), _cuda([1], np.uint8))
+        s = buf.sample(1)
+        return list(s.observations.values()) + list(s.next_observations.values()) + [s.actions, s.dones, s.rewards]
+
+    return [("ppo_loss", ppo), ("sac_critic_loss", sac_critic), ("conv_stem", stem), ("mlp_towers", tower), ("DeviceDiagGaussian.sample", head),
+            ("DeviceRolloutBuffer", rollout), ("DeviceReplayBuffer", replay)]
+
+
+def _vecnorm_step(tg, venv):
+    """reset + one step of a DeviceVecNormalize over `venv` on the current stream: what it handed out and its statistics."""
+    vn = tg.DeviceVecNormalize(venv, gamma=0.95)
+    vn.reset()
+    obs, rewards, _, _ = vn.step(np.array([[0.1, -0.2], [-0.05, 0.25]], np.float32))
+    return [obs["oracle"].clone(), torch.from_numpy(rewards), vn.returns.clone(), vn.ret_rms.block.clone(), vn.obs_rms["oracle"].block.clone()]
+
+
+def test_every_wrapper_family_launches_on_the_current_stream():
+    """One wrapper of each family under torch.cuda.stream(side), then side.synchronize() ONLY: every result equals, bit for bit, the same call
+    made on the default stream from the same values, seeds and counters.  The default stream is kept busy meanwhile and the results are read
+    on the side stream, so a wrapper that launched on another stream than torch's current one is read before it ran."""
+    import tactile_gym_amd as tg
+    modes = dict(EDGE, observation_mode="oracle")
+    envs = [tg.make_vec("edge_follow-v0", num_envs=2, max_steps=6, image_size=[64, 64], env_modes=modes, seed=4, obs_mode="torch") for _ in range(2)]
+    try:
+        calls = _family_calls(tg)
+        want = {name: call() for name, call in calls}
+        want["DeviceVecNormalize.step"] = _vecnorm_step(tg, envs[0])
+        torch.cuda.synchronize()
+        want = {name: [t.detach().cpu().numpy() for t in ts] for name, ts in want.items()}
+        busy, out = torch.rand((8192, 8192), device="cuda"), torch.empty((8192, 8192), device="cuda")
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        for _ in range(24):                                                      # the default stream is busy for the whole side section: a launch
+            torch.mm(busy, busy, out=out)                                        # that went there by mistake has not run when its result is read
+        with torch.cuda.stream(side):
+            got = {name: call() for name, call in calls}
+            got["DeviceVecNormalize.step"] = _vecnorm_step(tg, envs[1])
+            side.synchronize()
+            got = {name: [t.detach().cpu().numpy() for t in ts] for name, ts in got.items()}     # read on the side stream as well
+        for name, ts in got.items():
+            assert len(ts) == len(want[name]) and len(ts) >= 2, name
+            for i, (g, w) in enumerate(zip(ts, want[name])):
+                assert g.dtype == w.dtype and g.shape == w.shape and g.tobytes() == w.tobytes(), (name, i, g, w)
+                assert np.isfinite(g.astype(np.float64)).all(), (name, i, g)
+    finally:
+        torch.cuda.synchronize()
+        for v in envs:
+            v.close()
