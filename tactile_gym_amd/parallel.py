@@ -26,6 +26,7 @@ import ctypes as C
 import os
 
 from . import _capi as capi
+from .vec_env import _DevArray
 
 TILE_MAGIC = 0x54475431
 TILE_REC = 272
@@ -69,11 +70,6 @@ def torch_unpack_tiles(torch, src, tmpl, n, H, W, dst):
     dst.copy_(tiles.reshape(n, TH, TW, 16, 16).permute(0, 1, 3, 2, 4).reshape(n, H * W))
 
 
-class _DevArray:
-    def __init__(self, ptr, nbytes):
-        self.__cuda_array_interface__ = {"shape": (int(nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
-
-
 class _IpcSlots:
     """Rank 0's receive slots and the flags beside them, shared with the peers by IPC handle.  Layout of the allocation:
     [flags: 4096 B | slot 0: world x msg | slot 1: world x msg]; flags (uint32, one per 64 bytes): ready[slot][rank] at word
@@ -112,7 +108,7 @@ class _IpcSlots:
                 except Exception as e:  # noqa: BLE001
                     self.failed, self.base = e, C.c_void_p()
         self.err = torch.zeros(1, dtype=torch.int32, device=device)       # timeouts of this rank's waits (bit = flag lane)
-        self.local = torch.as_tensor(_DevArray(self.base.value, total), device=device) if (self.owner and self.failed is None) else None
+        self.local = torch.as_tensor(_DevArray(self.base.value, (total,), "|u1"), device=device) if (self.owner and self.failed is None) else None
 
     uncached = None                                   # rank 0: whether the receive slots are uncached device memory (None elsewhere)
     fixed_stream = None                               # a pipelined shard pins its stream: no per-call lookup (ShardedVecEnv sets it)
@@ -804,10 +800,9 @@ class TorchShard:
     def tile_template(self):
         """uint8 [H*W] device tensor: the image of the untouched sensor (zero inside, the pasted ring outside) tiles are compared with."""
         if not hasattr(self, "_tmpl"):
-            import torch
             p = C.c_void_p()
             capi.check(self.venv._L.tg_get_tile_template(self.venv._ctx, C.byref(p)))
-            self._tmpl = torch.as_tensor(_DevArray(p.value, self.venv.H * self.venv.W), device=self.venv.tactile_torch().device)
+            self._tmpl = self.venv._view(("tile_template", 0, False), p.value, (self.venv.H * self.venv.W,), "|u1")
         return self._tmpl
 
     def pack_tiles(self, dst_ptr, counters, tail=None, tail_offset=0):

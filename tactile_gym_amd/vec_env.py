@@ -89,6 +89,17 @@ class TactileVecEnv(_VecEnvBase):
     duck type otherwise)."""
 
     metadata = {"render.modes": ["rgb_array"]}
+    _IMAGE_KEYS = ("tactile", "visual")              # uint8 [N, H, W, C]; every other key is a float32 vector [N, dim]
+
+    # State that later calls set; __init__ gives every other attribute its first value.
+    _UNBOUND = object()              # _bound_stream before the first bind: that bind leaves no stream, so it neither drains nor counts as a rebind
+    _bound_stream = _UNBOUND         # the HIP stream the library was last put on (None: set_stream(None) returned it to following torch's)
+    _obs_sel = 0                     # the render target the next steps / resets draw into (select_obs_target)
+    _tile_download = None            # host_tiles.TileDownload while set_obs_transfer("tiles") holds
+    _obs_ring_i = -1                 # the buffer of _obs_ring the last copy_obs=False batch landed in
+    _held = None                     # the CUDA action tensor of a step in flight, kept alive until step_wait
+    _wf = None                       # pb_math.WorkFrame, built by the first _workframe()
+    _device = None                   # torch.device of the context's card, made by the first _torch_device()
 
     def __init__(self, cfg, robot, sensor_desc, mesh_desc, observation_mode="tactile", obs_mode="numpy", seed=None, act_dim=None,
                  oracle_dim=10, feature_dim=0, copy_obs=True, scene_spec=None, guard_spec=None, frame_stack=1, channels_first=False):
@@ -134,19 +145,22 @@ class TactileVecEnv(_VecEnvBase):
         self.ndof = robot.ndof
         self.act_dim = act_dim if act_dim is not None else {0: 2, 1: 3, 2: 3, 3: 4}[cfg.movement_mode]
         self.action_space = spaces.Box(low=cfg.min_action, high=cfg.max_action, shape=(self.act_dim,), dtype=np.float32)
-        obs_spaces = {}
-        if "oracle" in observation_mode:
-            obs_spaces["oracle"] = spaces.Box(low=-np.inf, high=np.inf, shape=(oracle_dim,), dtype=np.float32)
-            capi.check(self._L.tg_enable_oracle_obs(self._ctx))   # written by every step / reset; the step's own copy is the terminal observation
-        if "tactile" in observation_mode:
-            obs_spaces["tactile"] = spaces.Box(low=0, high=255, shape=(self.H, self.W, 1), dtype=np.uint8)
-        if self._visual:
-            obs_spaces["visual"] = spaces.Box(low=0, high=255, shape=(self.H, self.W, 3), dtype=np.uint8)   # rgb_image_size = image_size
-            self._set_scene(every_step=True)
-        if "feature" in observation_mode:
-            obs_spaces["extended_feature"] = spaces.Box(low=-np.inf, high=np.inf, shape=(feature_dim,), dtype=np.float32)
+        # the key table: the observation's keys in the order every dict handed out has them, and each key's last axis (image channels, vector length;
+        # rgb_image_size = image_size).  The spaces, the hand-out (_fetch) and the stacks' shapes (_stack_shape) all read these two.
+        self._keys = [k for k, on in (("oracle", "oracle" in observation_mode), ("tactile", "tactile" in observation_mode), ("visual", self._visual),
+                                      ("extended_feature", "feature" in observation_mode)) if on]
+        self._width = {"oracle": oracle_dim, "tactile": 1, "visual": 3, "extended_feature": feature_dim}
+        # the keys handed out from a device stack (tg_get_obs_stack).  channels_first with n = 1: the visual key only; the tactile image [N, H, W, 1]
+        # is the observation buffer itself seen as [N, 1, H, W], the vectors are the plain observations
+        self._stacked = frozenset(k for k in self._keys if self.frame_stack > 1 or (k == "visual" and self.channels_first))
         self.feature_dim, self._oracle_dim = feature_dim, oracle_dim
-        self.observation_space = spaces.stacked(spaces.Dict(obs_spaces), self.frame_stack)
+        if "oracle" in self._keys:
+            capi.check(self._L.tg_enable_oracle_obs(self._ctx))   # written by every step / reset; the step's own copy is the terminal observation
+        if self._visual:
+            self._set_scene(every_step=True)
+        self.observation_space = spaces.stacked(spaces.Dict({
+            k: (spaces.Box(low=0, high=255, shape=(self.H, self.W, self._width[k]), dtype=np.uint8) if k in self._IMAGE_KEYS else
+                spaces.Box(low=-np.inf, high=np.inf, shape=(self._width[k],), dtype=np.float32)) for k in self._keys}), self.frame_stack)
         if self.channels_first:
             self.observation_space = spaces.transposed(self.observation_space)
         if _VecEnvBase is not object:     # SB3's constructor records num_envs / spaces (and render_mode in recent versions)
@@ -157,10 +171,9 @@ class TactileVecEnv(_VecEnvBase):
         self._actions = np.zeros((self.num_envs, self.act_dim), dtype=np.float32)
         self._reward = np.zeros(self.num_envs, dtype=np.float32)
         self._done = np.zeros(self.num_envs, dtype=np.uint8)
-        self._obs_host = np.zeros((self.num_envs, self.H, self.W, 1), dtype=np.uint8)
-        self._term_host = None
+        self._obs_ring = [np.zeros((self.num_envs, self.H, self.W, 1), dtype=np.uint8) for _ in range(4)]   # copy_obs=False (pages untouched until written)
         self._closed = False
-        self._views = {}
+        self._views = {}                            # (name, render target, terminal) -> the zero-copy tensor(s) handed out under that name (_view)
         self._t_start = time.time()                 # Monitor's t_start (info["episode"]["t"])
         self._lazy_info, self._monitor = True, None
         self._obs_guard, self._guard_sum = False, {}
@@ -196,37 +209,49 @@ class TactileVecEnv(_VecEnvBase):
         if mask is not None:
             m = np.ascontiguousarray(mask, dtype=np.uint8)
             assert m.shape == (self.num_envs,)
-        self._bind_torch_stream()
+        self._begin_enqueue(check=False)            # a reset has never checked the buffer it draws into
         capi.check(self._L.tg_reset(self._ctx, m.ctypes.data_as(C.POINTER(C.c_uint8)) if m is not None else None))
         capi.check(self._L.tg_sync(self._ctx))
         if self._obs_guard:
             self._guard_after_step()
         return self._observation()
 
-    def _bind_torch_stream(self):
-        """obs_mode="torch": the zero-copy observation / reward / done tensors and CUDA action tensors are produced and consumed on
-        torch's CURRENT stream, so the library is put on that stream before work is enqueued (tg_set_stream is a pointer swap: every
-        step's launches go on whichever stream is bound).  Ordering between the policy's kernels and the env's is then the stream's own: no event,
-        no host wait, and correct under non-default or per-thread torch streams as well."""
-        if self.obs_mode != "torch" or self._pinned_stream:
-            return
-        import torch
-        ptr = torch.cuda.current_stream(torch.device("cuda", self._cfg.device)).cuda_stream
-        if getattr(self, "_bound_stream", None) != ptr:
-            if hasattr(self, "_bound_stream"):
-                capi.check(self._L.tg_sync(self._ctx))     # drain the stream being left before work goes to another one
-                self._rebinds += 1
-                if self._rebinds == 8:                     # every switch costs a host sync of the stream being left
-                    warnings.warn("TactileVecEnv (obs_mode='torch') has been moved between torch streams 8 times: drive an env from ONE stream "
-                                  "(or pin it with set_stream); each switch drains the stream being left", RuntimeWarning, stacklevel=3)
-            capi.check(self._L.tg_set_stream(self._ctx, C.c_void_p(ptr)))
-            self._bound_stream = ptr
+    def _torch_device(self):
+        """The device of every tensor handed out and of the stream followed: the one place that names it."""
+        if self._device is None:
+            import torch
+            self._device = torch.device("cuda", self._cfg.device)
+        return self._device
+
+    def _begin_enqueue(self, check=True):
+        """What reset / step_async / step_random_async do before they enqueue their work (its counterpart afterwards is _guard_after_step under the
+        same flag; both stay off the unguarded path, which is host bound: no call per step that the work itself does not need).
+        obs_mode="torch": the zero-copy observation / reward / done tensors and CUDA action tensors are produced and consumed on torch's CURRENT
+        stream, so the library is put on that stream first (tg_set_stream is a pointer swap: every step's launches go on whichever stream is
+        bound).  Ordering between the policy's kernels and the env's is then the stream's own: no event, no host wait, and correct under non-default
+        or per-thread torch streams as well.  Under set_obs_guard (`check`) the buffer about to be drawn into must still hold what the library last
+        drew there."""
+        if self.obs_mode == "torch" and not self._pinned_stream:
+            import torch
+            ptr = torch.cuda.current_stream(self._device or self._torch_device()).cuda_stream
+            if self._bound_stream != ptr:
+                self._follow_stream(ptr)
+        if check and self._obs_guard:
+            self._guard_before_step()
+
+    def _follow_stream(self, ptr):
+        if self._bound_stream is not self._UNBOUND:
+            capi.check(self._L.tg_sync(self._ctx))     # drain the stream being left before work goes to another one
+            self._rebinds += 1
+            if self._rebinds == 8:                     # every switch costs a host sync of the stream being left
+                warnings.warn("TactileVecEnv (obs_mode='torch') has been moved between torch streams 8 times: drive an env from ONE stream "
+                              "(or pin it with set_stream); each switch drains the stream being left", RuntimeWarning, stacklevel=4)
+        capi.check(self._L.tg_set_stream(self._ctx, C.c_void_p(ptr)))
+        self._bound_stream = ptr
 
     def step_async(self, actions):
         """actions: numpy float32 [N, act_dim], or a torch CUDA tensor (read in place on the current torch stream)."""
-        self._bind_torch_stream()
-        if self._obs_guard:
-            self._guard_before_step()
+        self._begin_enqueue()
         if hasattr(actions, "data_ptr") and getattr(actions, "is_cuda", False):
             assert actions.dtype.is_floating_point and actions.element_size() == 4 and actions.is_contiguous()
             assert tuple(actions.shape) == (self.num_envs, self.act_dim)
@@ -254,21 +279,20 @@ class TactileVecEnv(_VecEnvBase):
         torch = __import__("torch")
         t = self.tactile_torch()
         total = int(t.reshape(-1).view(torch.int64).sum().item())
-        if self._layout_on():                       # the stacks handed out alias the library's buffers as well
-            for key in filter(self._device_stacked, self._stack_keys()):
-                total += int(self._stack_torch(key).reshape(-1).view(torch.int32).to(torch.int64).sum().item())
+        for key in sorted(self._stacked):           # the stacks handed out alias the library's buffers as well
+            total += int(self._stack_torch(key).reshape(-1).view(torch.int32).to(torch.int64).sum().item())
         return total
 
     def _guard_before_step(self):
-        sel = getattr(self, "_obs_sel", 0)          # the target this step draws into: its buffer must still hold what the library last drew there
-        if self._obs_guard and self.obs_mode == "torch" and sel in self._guard_sum and self._guard_checksum() != self._guard_sum[sel]:
+        sel = self._obs_sel                         # the target this step draws into: its buffer must still hold what the library last drew there
+        if self.obs_mode == "torch" and sel in self._guard_sum and self._guard_checksum() != self._guard_sum[sel]:
             raise RuntimeError("the tactile observation tensor handed out by the last step / reset was modified in place: obs_mode='torch' tensors "
                                "alias the library's buffer, of which only the changed 16 x 16 blocks are rewritten per step (DESIGN.md 4.2).  Copy "
                                "before augmenting in place, or run with TG_RASTER_REWRITE_ALL=1")
 
     def _guard_after_step(self):
-        if self._obs_guard and self.obs_mode == "torch":
-            self._guard_sum[getattr(self, "_obs_sel", 0)] = self._guard_checksum()
+        if self.obs_mode == "torch":
+            self._guard_sum[self._obs_sel] = self._guard_checksum()
 
     def set_monitor(self, monitor_dir, env_id=None):
         """What `make_vec_env(..., monitor_dir=d)` asks for (sb3_helpers/rl_utils.py:22, 59; read back by stable_baselines3's load_results, which
@@ -303,38 +327,35 @@ class TactileVecEnv(_VecEnvBase):
         """One step of a random-action rollout, `step(action_space.sample())` for the whole batch, with the policy inside the step: the uniform draw (draw k =
         sample_actions(seed, k)) is made by the step kernel itself (or by the step's first launch) and the draw counter lives on the device (tg_step_random).  restart: the next draw
         is first_draw + 1.  The actions used are `actions_torch()`."""
-        self._bind_torch_stream()
-        if self._obs_guard:
-            self._guard_before_step()
+        self._begin_enqueue()
         capi.check(self._L.tg_step_random(self._ctx, C.c_uint64(seed), C.c_uint64(first_draw), 1 if restart else 0))
         if self._obs_guard:
             self._guard_after_step()
 
     def actions_torch(self):
         """The context's own action buffer as a float32 [N, act_dim] device tensor (what step_random_async drew)."""
-        if "act" not in self._views:
-            import torch
+        view = self._views.get(("actions", 0, False))
+        if view is None:
             p = C.c_void_p()
             capi.check(self._L.tg_get_actions(self._ctx, C.byref(p)))
-            self._views["act"] = torch.as_tensor(_DevArray(p.value, (self.num_envs, self.act_dim), "<f4"), device=f"cuda:{self._cfg.device}")
-        return self._views["act"]
+            view = self._view(("actions", 0, False), p.value, (self.num_envs, self.act_dim), "<f4")
+        return view
 
     def step_wait(self):
-        td = getattr(self, "_tile_download", None)
-        if td is not None and "tactile" in self.observation_mode and self.obs_mode != "torch":
-            # tile download: the observation fetch brings reward / done along under its one synchronisation
+        # tile download: the observation fetch comes first and brings reward / done (and the finished envs' rows) along under its one
+        # synchronisation; otherwise tg_get_reward_done is the synchronising call and the observation follows it
+        td = self._tile_download
+        rides = td is not None and "tactile" in self._keys and self.obs_mode != "torch"
+        if rides:
             td.rd_fresh = False
             obs = self._observation()
-            if td.rd_fresh:
-                np.copyto(self._reward, td.rew_host); np.copyto(self._done, td.done_host)
-            else:
-                capi.check(self._L.tg_get_reward_done(self._ctx, self._reward.ctypes.data_as(C.POINTER(C.c_float)),
-                                                      self._done.ctypes.data_as(C.POINTER(C.c_uint8))))
-            self._held = None
+        if rides and td.rd_fresh:
+            np.copyto(self._reward, td.rew_host); np.copyto(self._done, td.done_host)
         else:
             capi.check(self._L.tg_get_reward_done(self._ctx, self._reward.ctypes.data_as(C.POINTER(C.c_float)),
                                                   self._done.ctypes.data_as(C.POINTER(C.c_uint8))))
-            self._held = None
+        self._held = None
+        if not rides:
             obs = self._observation()
         dones = self._done.astype(bool)
         # SB3 reads infos[i].get(...) / "key" in infos[i]; only the envs that finished carry anything.  lazy_info (default): the others share ONE
@@ -343,7 +364,7 @@ class TactileVecEnv(_VecEnvBase):
         infos = [_EMPTY_INFO] * self.num_envs if self._lazy_info else [{} for _ in range(self.num_envs)]
         # tile download (round 6): the finished envs' ids, episode statistics and terminal images came along with the observation fetch
         # (host_tiles.TileDownload.done_rows; tg_pack_done_rows) - no further round trip to the device in this step
-        dr = td.done_rows if (td is not None and td.rd_fresh and "tactile" in self.observation_mode and self.obs_mode != "torch") else None
+        dr = td.done_rows if rides and td.rd_fresh else None
         if dr is not None and not np.array_equal(dr[0], np.nonzero(dones)[0]):
             dr = None                                 # (cannot happen: the same done flags; the copies below are always right)
         if dones.any():
@@ -385,7 +406,7 @@ class TactileVecEnv(_VecEnvBase):
             self._closed = True
             if self._monitor is not None:
                 self._monitor.close()
-            if getattr(self, "_tile_download", None) is not None:
+            if self._tile_download is not None:
                 self._tile_download.close()
                 self._tile_download = None
             self._L.tg_destroy(self._ctx)
@@ -455,6 +476,15 @@ class TactileVecEnv(_VecEnvBase):
         capi.check(self._L.tg_set_stream(self._ctx, C.c_void_p(hip_stream_ptr)))
         self._bound_stream = hip_stream_ptr
 
+    def _view(self, key, ptr, shape, typestr):
+        """The zero-copy hand-out `key` = (name, render target, terminal): a torch tensor on the env's device that aliases the memory at `ptr`,
+        made here and nowhere else, and kept in _views.  An accessor looks its key up there first and comes here once, so every later call
+        returns this same object.  The library's buffers never move in a context's life; a caller's render targets can (set_obs_targets), which
+        is why the target is part of every key."""
+        import torch
+        view = self._views[key] = torch.as_tensor(_DevArray(ptr, shape, typestr), device=self._torch_device())
+        return view
+
     def tactile_device_ptr(self, terminal=False):
         p = C.c_void_p()
         fn = self._L.tg_get_terminal_obs if terminal else self._L.tg_get_obs_tactile
@@ -468,56 +498,52 @@ class TactileVecEnv(_VecEnvBase):
         arr = (C.c_void_p * max(len(dev_ptrs), 1))(*[C.c_void_p(int(p)) for p in dev_ptrs])
         capi.check(self._L.tg_set_obs_targets(self._ctx, len(dev_ptrs), arr))
         self._obs_sel = 0
-        for k in [k for k in self._views if isinstance(k, tuple) and k[0] == "obs" and k[1] != 0]:
-            del self._views[k]
+        for key in [key for key in self._views if key[1] != 0]:     # views of the targets just forgotten
+            del self._views[key]
 
     def select_obs_target(self, index):
-        if index != getattr(self, "_obs_sel", 0):
+        if index != self._obs_sel:
             capi.check(self._L.tg_select_obs_target(self._ctx, int(index)))
             self._obs_sel = int(index)
 
     def tactile_torch(self, terminal=False):
         """Zero-copy torch.uint8 [N,H,W,1] view of the device observation buffer (of the selected render target)."""
-        key = "term" if terminal else ("obs", getattr(self, "_obs_sel", 0))
-        if key not in self._views:   # the library's buffers never move: build each aliasing tensor once
-            import torch
-            arr = _DevArray(self.tactile_device_ptr(terminal), (self.num_envs, self.H, self.W, 1), "|u1")
-            self._views[key] = torch.as_tensor(arr, device=f"cuda:{self._cfg.device}")
-        return self._views[key]
+        key = ("tactile", 0 if terminal else self._obs_sel, terminal)      # (the terminal buffer is the context's own whichever target is selected)
+        view = self._views.get(key)
+        if view is None:
+            view = self._view(key, self.tactile_device_ptr(terminal), (self.num_envs, self.H, self.W, 1), "|u1")
+        return view
 
     def reward_done_torch(self):
-        if "rd" not in self._views:
-            import torch
+        rd = self._views.get(("reward_done", 0, False))
+        if rd is None:
             r, d = C.c_void_p(), C.c_void_p()
             capi.check(self._L.tg_get_reward_done_dev(self._ctx, C.byref(r), C.byref(d)))
-            dev = f"cuda:{self._cfg.device}"
-            self._views["rd"] = (torch.as_tensor(_DevArray(r.value, (self.num_envs,), "<f4"), device=dev),
-                                 torch.as_tensor(_DevArray(d.value, (self.num_envs,), "|u1"), device=dev))
-        return self._views["rd"]
+            rd = self._views["reward_done", 0, False] = (self._view(("reward", 0, False), r.value, (self.num_envs,), "<f4"),
+                                                         self._view(("done", 0, False), d.value, (self.num_envs,), "|u1"))
+        return rd
 
     def packed_torch(self):
         """Zero-copy torch.uint8 view of the whole per-step output block [obs | pad | reward f32 | done u8 | pad | feature f32[N][12]],
         the reward offset and the feature offset (-1: this env has no extended_feature)."""
-        if "packed" not in self._views:
-            import torch
+        packed = self._views.get(("packed", 0, False))
+        if packed is None:
             p, ob, tot, fo, fd = C.c_void_p(), C.c_int64(), C.c_int64(), C.c_int64(), C.c_int32()
             capi.check(self._L.tg_get_packed_outputs(self._ctx, C.byref(p), C.byref(ob), C.byref(tot)))
             capi.check(self._L.tg_get_packed_feature(self._ctx, C.byref(fo), C.byref(fd)))
-            self._views["packed"] = (torch.as_tensor(_DevArray(p.value, (tot.value,), "|u1"), device=f"cuda:{self._cfg.device}"), ob.value, fo.value)
-        return self._views["packed"]
+            packed = self._views["packed", 0, False] = (self._view(("packed_block", 0, False), p.value, (tot.value,), "|u1"), ob.value, fo.value)
+        return packed
 
     def tactile_numpy(self, terminal=False):
         """Host copy of the observation batch.  copy_obs=True: a new array per call.  copy_obs=False: the device -> host copy lands in
         one of four rotating host buffers (an extra 16.8 MB `.copy()` per step costs more than the PCIe transfer itself): the array stays
         untouched for the next three steps."""
-        if not terminal and getattr(self, "_tile_download", None) is not None:
+        if not terminal and self._tile_download is not None:
             return self._tile_download.fetch()
         if terminal or self.copy_obs:
-            buf = np.empty_like(self._obs_host)
+            buf = np.empty_like(self._obs_ring[0])
         else:
-            self._obs_ring_i = (getattr(self, "_obs_ring_i", -1) + 1) % 4
-            if not hasattr(self, "_obs_ring"):
-                self._obs_ring = [self._obs_host] + [np.zeros_like(self._obs_host) for _ in range(3)]
+            self._obs_ring_i = (self._obs_ring_i + 1) % 4
             buf = self._obs_ring[self._obs_ring_i]
         capi.check(self._L.tg_copy_obs_tactile(self._ctx, buf.ctypes.data_as(C.POINTER(C.c_uint8)), int(terminal)))
         return buf
@@ -527,33 +553,28 @@ class TactileVecEnv(_VecEnvBase):
         that differ from the untouched sensor's image, rebuilt on the host (host_tiles.py; lossless; needs torch and lib/libtg_host.so);
         the batch handed out is then one of five ring buffers, untouched for the next three steps (as with copy_obs=False).  Terminal
         observations always take the full copy."""
-        old = getattr(self, "_tile_download", None)
-        if old is not None:
-            old.close()
-        if how == "full":
-            self._tile_download = None
-        elif how == "tiles" and self.frame_stack > 1:
-            self._tile_download = None
+        if self._tile_download is not None:
+            self._tile_download.close()
+        self._tile_download = None                  # what a refusal below leaves behind
+        if how == "tiles" and self.frame_stack > 1:
             raise ValueError(f"obs_transfer 'tiles' with frame_stack={self.frame_stack}: the tile download carries single frames; use 'full'")
-        elif how == "tiles" and self.channels_first and self._visual:
-            self._tile_download = None
+        if how == "tiles" and self.channels_first and self._visual:
             raise ValueError("obs_transfer 'tiles' with channels_first and a visual key: the tile download carries the tactile image only; use 'full'")
-        elif how == "tiles":
+        if how == "tiles":
             from .host_tiles import TileDownload
             self._tile_download = TileDownload(self)
-        else:
+        elif how != "full":
             raise ValueError(f"obs_transfer {how!r}: 'full' or 'tiles'")
         return self
 
     def visual_torch(self, terminal=False):
         """Zero-copy torch.uint8 [N, H, W, 3] view of the device-resident scene-camera images."""
-        key = ("vis", bool(terminal))
-        if key not in self._views:
-            import torch
+        view = self._views.get(("visual", 0, terminal))
+        if view is None:
             p = C.c_void_p()
             capi.check(self._L.tg_get_obs_visual(self._ctx, C.byref(p), int(terminal)))
-            self._views[key] = torch.as_tensor(_DevArray(p.value, (self.num_envs, self.H, self.W, 3), "|u1"), device=f"cuda:{self._cfg.device}")
-        return self._views[key]
+            view = self._view(("visual", 0, terminal), p.value, (self.num_envs, self.H, self.W, 3), "|u1")
+        return view
 
     def visual_numpy(self, terminal=False):
         buf = np.empty((self.num_envs, self.H, self.W, 3), dtype=np.uint8)
@@ -561,46 +582,26 @@ class TactileVecEnv(_VecEnvBase):
         return buf
 
     # ------------------------------------------------------------------ frame stack (tg_set_frame_stack)
-    def _layout_on(self):
-        return self.frame_stack > 1 or self.channels_first
-
-    def _device_stacked(self, key):
-        """Whether `key` is handed out from a device stack (tg_get_obs_stack).  channels_first with n = 1: the visual key only; the tactile
-        image [N, H, W, 1] is the observation buffer itself seen as [N, 1, H, W], the vectors are the plain observations."""
-        return self.frame_stack > 1 or (key == "visual" and self.channels_first)
-
-    def _stack_keys(self):
-        keys = []
-        if "oracle" in self.observation_mode:
-            keys.append("oracle")
-        if "tactile" in self.observation_mode:
-            keys.append("tactile")
-        if self._visual:
-            keys.append("visual")
-        if "feature" in self.observation_mode:
-            keys.append("extended_feature")
-        return keys
-
     def _stack_shape(self, key, rows):
-        if key in ("tactile", "visual"):
-            c = (3 if key == "visual" else 1) * self.frame_stack
+        c = self._width[key] * self.frame_stack
+        if key in self._IMAGE_KEYS:
             return ((rows, c, self.H, self.W) if self.channels_first else (rows, self.H, self.W, c)), np.uint8, "|u1"
-        dim = self._oracle_dim if key == "oracle" else self.feature_dim
-        return (rows, dim * self.frame_stack), np.float32, "<f4"
+        return (rows, c), np.float32, "<f4"
 
     def _stack_torch(self, key, terminal=False):
         """Zero-copy torch view of the device stack of `key` (read-only contract as tactile_torch)."""
-        vk = ("stack", key, bool(terminal))
-        if vk not in self._views:
-            import torch
+        vk = ("stack_" + key, 0, terminal)
+        view = self._views.get(vk)
+        if view is None:
             shape, _, typestr = self._stack_shape(key, self.num_envs)
-            if shape[-1] == 0:
-                self._views[vk] = torch.zeros(shape, dtype=torch.float32, device=f"cuda:{self._cfg.device}")
+            if shape[-1] == 0:                      # a zero-width key has no stack on the device
+                import torch
+                view = self._views[vk] = torch.zeros(shape, dtype=torch.float32, device=self._torch_device())
             else:
                 p = C.c_void_p()
                 capi.check(self._L.tg_get_obs_stack(self._ctx, capi.OBS_STACK_KEY[key], int(terminal), C.byref(p)))
-                self._views[vk] = torch.as_tensor(_DevArray(p.value, shape, typestr), device=f"cuda:{self._cfg.device}")
-        return self._views[vk]
+                view = self._view(vk, p.value, shape, typestr)
+        return view
 
     def _stack_numpy(self, key, terminal=False, idx=None):
         """Host copy of the stack of `key`: the whole batch, or (idx) the rows of those envs only (tg_copy_obs_stack_rows)."""
@@ -616,45 +617,54 @@ class TactileVecEnv(_VecEnvBase):
                                                       out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def _layout_obs(self, key, terminal=False):
-        """One key of the observation (or terminal observation) batch with a frame stack or channels first."""
+    # ------------------------------------------------------------------ the hand-out
+    def _fetch(self, key, terminal=False, idx=None, tactile_rows=None):
+        """One key of the observation (terminal: of the observation before the auto-reset), as it is handed out: a zero-copy tensor in obs_mode
+        "torch", a host copy otherwise.  idx (host copies only): the rows of those envs alone, in arrays made for this call; tactile_rows: the
+        tactile rows of `idx` where the tile download has brought them along.  The source is the key's device stack, or its plain buffer - which
+        for the tactile key under channels_first with n = 1 is reinterpreted: [N, H, W, 1] and [N, 1, H, W] are the same bytes."""
         torch_mode = self.obs_mode == "torch"
-        if self._device_stacked(key):
-            return self._stack_torch(key, terminal) if torch_mode else self._stack_numpy(key, terminal)
-        if key == "tactile":                        # channels first, n = 1: [N, H, W, 1] and [N, 1, H, W] are the same bytes
-            if torch_mode:
-                vk = ("cf1", bool(terminal))
-                if vk not in self._views:
-                    self._views[vk] = self.tactile_torch(terminal).view(self.num_envs, 1, self.H, self.W)
-                return self._views[vk]
-            return self.tactile_numpy(terminal).reshape(self.num_envs, 1, self.H, self.W)
+        if key in self._stacked:
+            return self._stack_torch(key, terminal) if torch_mode else self._stack_numpy(key, terminal, idx)
+        cf1 = key == "tactile" and self.channels_first
+        if idx is not None and key in self._IMAGE_KEYS:      # only the finished envs' images cross PCIe
+            rows = tactile_rows if key == "tactile" and tactile_rows is not None else self._image_rows(idx, key == "visual", terminal)
+            return np.ascontiguousarray(rows).reshape(len(idx), 1, self.H, self.W) if cf1 else rows
+        if idx is not None:                                  # the small per-env vectors: rows of the whole-batch copy
+            return np.array(self._fetch(key, terminal)[idx])
         if key == "oracle":
             return self.oracle_terminal() if terminal else self.oracle_obs()
+        if cf1 and not torch_mode:
+            return self.tactile_numpy(terminal).reshape(self.num_envs, 1, self.H, self.W)
+        if cf1:
+            vk = ("tactile_cf", 0 if terminal else self._obs_sel, terminal)
+            view = self._views.get(vk)
+            return view if view is not None else self._view(vk, self.tactile_device_ptr(terminal), (self.num_envs, 1, self.H, self.W), "|u1")
+        if key == "tactile":
+            return self.tactile_torch(terminal) if torch_mode else self.tactile_numpy(terminal)
+        if key == "visual":
+            return self.visual_torch(terminal) if torch_mode else self.visual_numpy(terminal)
         return self.feature_torch(terminal) if torch_mode else self.feature_numpy(terminal)
 
     def _observation(self):
-        if self._layout_on():
-            return {k: self._layout_obs(k) for k in self._stack_keys()}
-        obs = {}
-        if "oracle" in self.observation_mode:
-            obs["oracle"] = self.oracle_obs()
-        if "tactile" in self.observation_mode:
-            obs["tactile"] = self.tactile_torch() if self.obs_mode == "torch" else self.tactile_numpy()
-        if self._visual:
-            obs["visual"] = self.visual_torch() if self.obs_mode == "torch" else self.visual_numpy()
-        if "feature" in self.observation_mode:
-            obs["extended_feature"] = self.feature_torch() if self.obs_mode == "torch" else self.feature_numpy()
-        return obs
+        return {k: self._fetch(k) for k in self._keys}
+
+    def _terminal_observation(self):
+        return {k: self._fetch(k, terminal=True) for k in self._keys}
+
+    def _terminal_rows(self, idx, tactile_rows=None):
+        """The terminal observation of the envs `idx` only (numpy)."""
+        return {k: self._fetch(k, True, idx, tactile_rows) for k in self._keys}
 
     def oracle_terminal(self):
         """The oracle vectors of the last step before the auto-reset (rows valid where done); observation_mode "oracle" only."""
         if self.obs_mode == "torch":
-            if "oracle_term" not in self._views:
-                import torch
+            view = self._views.get(("oracle", 0, True))
+            if view is None:
                 p = C.c_void_p()
                 capi.check(self._L.tg_get_obs_oracle_terminal(self._ctx, C.byref(p)))
-                self._views["oracle_term"] = torch.as_tensor(_DevArray(p.value, (self.num_envs, self._oracle_dim), "<f4"), device=f"cuda:{self._cfg.device}")
-            return self._views["oracle_term"]
+                view = self._view(("oracle", 0, True), p.value, (self.num_envs, self._oracle_dim), "<f4")
+            return view
         buf = np.empty((self.num_envs, self._oracle_dim), dtype=np.float32)
         capi.check(self._L.tg_copy_obs_oracle_terminal(self._ctx, buf.ctypes.data_as(C.POINTER(C.c_float))))
         return buf
@@ -668,60 +678,14 @@ class TactileVecEnv(_VecEnvBase):
                                             out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out
 
-    def _terminal_rows(self, idx, tactile_rows=None):
-        """The terminal observation of the envs `idx` only (numpy): images by tg_copy_obs_rows (or `tactile_rows`, what the tile download brought along),
-        the small per-env vectors from their whole-batch copies.  With a frame stack: the finished envs' terminal stacks."""
-        if self._layout_on():
-            obs = {}
-            for k in self._stack_keys():
-                if self._device_stacked(k):
-                    obs[k] = self._stack_numpy(k, terminal=True, idx=idx)
-                elif k == "tactile":
-                    rows = tactile_rows if tactile_rows is not None else self._image_rows(idx, False)
-                    obs[k] = np.ascontiguousarray(rows).reshape(len(idx), 1, self.H, self.W)
-                elif k == "oracle":
-                    obs[k] = np.array(self.oracle_terminal()[idx])
-                else:
-                    obs[k] = np.array(self.feature_numpy(True)[idx])
-            return obs
-        obs = {}
-        if "oracle" in self.observation_mode:
-            obs["oracle"] = np.array(self.oracle_terminal()[idx])
-        if "tactile" in self.observation_mode:
-            obs["tactile"] = tactile_rows if tactile_rows is not None else self._image_rows(idx, False)
-        if self._visual:
-            obs["visual"] = self._image_rows(idx, True)
-        if "feature" in self.observation_mode:
-            obs["extended_feature"] = np.array(self.feature_numpy(True)[idx])
-        return obs
-
-    def _terminal_observation(self):
-        if self._layout_on():
-            return {k: self._layout_obs(k, terminal=True) for k in self._stack_keys()}
-        obs = {}
-        if "oracle" in self.observation_mode:
-            obs["oracle"] = self.oracle_terminal()
-        if "tactile" in self.observation_mode:
-            obs["tactile"] = self.tactile_torch(True) if self.obs_mode == "torch" else self.tactile_numpy(True)
-        if self._visual:
-            obs["visual"] = self.visual_torch(True) if self.obs_mode == "torch" else self.visual_numpy(True)
-        if "feature" in self.observation_mode:
-            obs["extended_feature"] = self.feature_torch(True) if self.obs_mode == "torch" else self.feature_numpy(True)
-        return obs
-
-    def _feature_ptr(self, terminal):
-        p, dim = C.c_void_p(), C.c_int32()
-        capi.check(self._L.tg_get_obs_feature(self._ctx, C.byref(p), C.byref(dim), int(terminal)))
-        return p.value, dim.value
-
     def feature_torch(self, terminal=False):
         """Zero-copy torch.float32 [N, feature_dim] view of the device-resident extended_feature observation."""
-        key = ("feat", bool(terminal))
-        if key not in self._views:
-            import torch
-            ptr, dim = self._feature_ptr(terminal)
-            self._views[key] = torch.as_tensor(_DevArray(ptr, (self.num_envs, dim), "<f4"), device=torch.device("cuda", self._cfg.device))
-        return self._views[key]
+        view = self._views.get(("extended_feature", 0, terminal))
+        if view is None:
+            p, dim = C.c_void_p(), C.c_int32()
+            capi.check(self._L.tg_get_obs_feature(self._ctx, C.byref(p), C.byref(dim), int(terminal)))
+            view = self._view(("extended_feature", 0, terminal), p.value, (self.num_envs, dim.value), "<f4")
+        return view
 
     def feature_numpy(self, terminal=False):
         if self.feature_dim == 0:
@@ -735,14 +699,10 @@ class TactileVecEnv(_VecEnvBase):
         a zero-copy torch view in obs_mode "torch" (valid until the next call), an owned numpy array otherwise.  The env classes'
         oracle_obs_host() is the same vector from a state read-back (kept as a cross-check)."""
         if self.obs_mode == "torch":
-            if "oracle" not in self._views:
-                import torch
-                p, d = C.c_void_p(), C.c_int32()
-                capi.check(self._L.tg_get_obs_oracle(self._ctx, C.byref(p), C.byref(d)))
-                self._views["oracle"] = torch.as_tensor(_DevArray(p.value, (self.num_envs, d.value), "<f4"), device=f"cuda:{self._cfg.device}")
-            else:
-                capi.check(self._L.tg_get_obs_oracle(self._ctx, C.byref(C.c_void_p()), None))
-            return self._views["oracle"]
+            p, d = C.c_void_p(), C.c_int32()
+            capi.check(self._L.tg_get_obs_oracle(self._ctx, C.byref(p), C.byref(d)))     # every call: the entry recomputes the vectors on the device
+            view = self._views.get(("oracle", 0, False))
+            return view if view is not None else self._view(("oracle", 0, False), p.value, (self.num_envs, d.value), "<f4")
         buf = np.empty((self.num_envs, self._oracle_dim), dtype=np.float32)
         capi.check(self._L.tg_copy_obs_oracle(self._ctx, buf.ctypes.data_as(C.POINTER(C.c_float))))
         return buf
@@ -752,7 +712,7 @@ class TactileVecEnv(_VecEnvBase):
 
     def _workframe(self):
         from .pb_math import WorkFrame
-        if not hasattr(self, "_wf"):
+        if self._wf is None:
             self._wf = WorkFrame([self._cfg.workframe_pos[k] for k in range(3)], [self._cfg.workframe_rpy[k] for k in range(3)])
         return self._wf
 
