@@ -1,4 +1,7 @@
-// tg_api.hip — env-step / reset kernels and the C ABI of libtactile_gym_hip.so (see include/tactile_gym_hip.h).
+// tg_api.hip — env-step / reset kernels and the C ABI of libtactile_gym_hip.so (see include/tactile_gym_hip.h): configuration, creation,
+// the step / reset launches, the scene camera and the interior payload.  The rest of the ABI shares tg_ctx.hpp: tg_api_obs.hip (where every
+// observation buffer lives: the tg_get_* / tg_copy_* entries, render targets, frame stack and layout), tg_api_state.hip (the read side:
+// state, statistics, profiling, the broadphase guard), tg_api_ops.hip (the torch-facing device ops).
 //
 // Per-env state lives in HBM as struct-of-arrays with the env index minor ([field][num_envs], doubles), so a
 // wavefront of 64 consecutive envs reads or writes one 512-byte contiguous run per field: the whole dynamic state
@@ -295,16 +298,7 @@ static const BankDev* bank_dev(const tg_ctx* c) { return c->bank_mode != 0 ? (co
 // The launch functions below stand in the order draws, resets, bank refill, steps: the compiler lays the kernels out in tg_api's code object in
 // the order in which this file first names them, and the step kernels at other addresses measured 0.25 - 0.4 % slower in device-bound rollouts
 // (profiles/step_dispatch_refactor.txt, section 4).  tools/dev/compare_device_code.py against the previous build shows a changed layout.
-static int oracle_dim(const tg_ctx* c) {
-    switch (c->cfg.env_kind) {
-        case TG_ENV_EDGE_FOLLOW: return 10;
-        case TG_ENV_SURFACE_FOLLOW_AUTO: return 20;
-        case TG_ENV_OBJECT_BALANCE: return 26;
-        case TG_ENV_OBJECT_PUSH: return 30;
-        default: return 34;
-    }
-}
-static void oracle_draw(tg_ctx* c, float* dst) {
+void oracle_draw(tg_ctx* c, float* dst) {   // (tg_ctx.hpp: tg_api_obs.hip draws through it and names no kernel itself)
     dispatch(c, [&](auto p) { launch_env(c, k_oracle_obs<typename decltype(p)::T, decltype(p)::TOPO>, 0, oracle_dim(c), dst); });
 }
 // get_visual_obs for the whole batch (or the masked envs; save_prev keeps their previous image as the terminal observation)
@@ -601,49 +595,10 @@ static void bank_refill(tg_ctx* c) {
 
 using namespace tg;
 
-// The frame stack's update after a step (flag = st.done) or a reset (flag = the reset mask, null: every env); tg_stack.hip.  Reads the finished
-// observation buffers of that step / reset, so it is the last launch of the sequence.
-static int feature_dim(const tg_ctx* c) { return c->cfg.env_kind == TG_ENV_OBJECT_ROLL ? 3 : c->cfg.env_kind == TG_ENV_SURFACE_FOLLOW_AUTO ? 6 : 12; }
-static bool stack_rewrite_all() {
-    static const bool on = [] { const char* e = getenv("TG_STACK_REWRITE_ALL"); return e && e[0] == '1'; }();   // read once per process
-    return on;
-}
-static int stack_update(tg_ctx* c, int mode, const uint8_t* flag) {
-    if (c->stack_n <= 1 && !c->d_vstack) return 0;
-    StackArgs a;
-    a.num_envs = c->cfg.num_envs; a.H = c->H; a.W = c->W; a.n = c->stack_n; a.mode = mode; a.rewrite_all = stack_rewrite_all() ? 1 : 0;
-    a.flag = flag;
-    const bool term = mode == kStackStep && c->cfg.auto_reset;
-    a.frame = c->d_obs; a.term_frame = c->d_term; a.tmpl = c->d_tile_tmpl; a.stack = c->d_stack; a.rec = c->d_stack_rec;
-    a.term_stack = term ? c->d_stack_term : nullptr;
-    for (int k = 0; k < 2; ++k) {
-        if (!c->d_stack_vec[k]) continue;
-        StackVec& v = a.vec[k];
-        v.dim = c->stack_vec_dim[k];
-        v.pitch = k == 0 ? v.dim : 12;
-        v.src = k == 0 ? c->d_oracle : c->st.feature;
-        v.term = k == 0 ? c->d_oracle_term : c->st.term_feature;
-        v.stack = c->d_stack_vec[k];
-        v.term_stack = term ? c->d_stack_vec_term[k] : nullptr;
-    }
-    if (!c->d_vstack && !c->obs_cf) {
-        if (launch_frame_stack(a, c->stream) != 0) return fail(-2, "frame stack launch failed");
-        return 0;
-    }
-    if (c->stack_n <= 1) a.frame = nullptr;     // channels first, n = 1: the tactile buffer is its own stack
-    VisStack v;
-    if (c->d_vstack) {
-        v.frame = c->d_vis; v.term_frame = c->d_vis_term; v.stack = c->d_vstack; v.term_stack = term ? c->d_vstack_term : nullptr;
-        v.H = c->scene.H; v.W = c->scene.W;
-    }
-    if (launch_obs_stack(a, v, c->obs_cf, c->stream) != 0) return fail(-2, "observation stack launch failed");
-    return 0;
-}
-
 // ------------------------------------------------------------------------------------------------ tg_create, step by step
 // create_impl runs the functions below in order.  Everything the host can hold against a configuration is said by check_config, before the
 // device is touched; every later step allocates through dev_alloc / dev_upload (tg_ctx.hpp) and, on an error, simply returns: tg_create's guard
-// destroys the context, and the context's list frees whatever had been made.  None of them names a kernel (the note above oracle_dim).
+// destroys the context, and the context's list frees whatever had been made.  None of them names a kernel (the note above oracle_draw).
 struct HostConsts { std::vector<uint8_t> robot, env; int act_dim = 0; };   // DevRobot<T> / EnvConst<T> in the configuration's physics_dtype, as bytes
 
 static int check_config(const tg_config* cfg, const tg_robot* robot, const tg_sensor* sensor, const tg_mesh* stim, HostConsts& hc) {
@@ -1262,32 +1217,6 @@ int tg_step_random(tg_ctx* c, uint64_t seed, uint64_t first_draw, int32_t restar
     return 0;
 }
 
-int tg_set_obs_targets(tg_ctx* c, int32_t count, void* const* dev_ptrs) {
-    if (!c || count < 0 || count > 2 || (count > 0 && !dev_ptrs)) return fail(-1, "tg_set_obs_targets: bad argument");
-    for (int k = 0; k < count; ++k) if (!dev_ptrs[k]) return fail(-1, "tg_set_obs_targets: NULL target");   // (every argument is checked before anything is changed)
-    if (count > 0 && c->stack_n > 1) return fail(-1, "tg_set_obs_targets: a context with a frame stack (tg_set_frame_stack n > 1) draws into its own buffer only");
-    if (count > 0 && c->obs_cf) return fail(-1, "tg_set_obs_targets: a context with channels-first observations (tg_set_obs_layout 1) draws into its own buffer only");
-    TG_ENTER(c);
-    TG_HIP(hipStreamSynchronize(c->stream));
-    c->obs_sel = 0;
-    const size_t regions = (c->rp.W % 128 == 0 && c->rp.H % 128 == 0) ? (size_t)(c->rp.W / 128) * (c->rp.H / 128) : 0;
-    for (int k = 0; k < 2; ++k) {
-        c->obs_ext[k] = k < count ? (uint8_t*)dev_ptrs[k] : nullptr;
-        if (k < count && c->rp.drawn != nullptr && regions == 0) return fail(-3, "tg_set_obs_targets: a changed-block record without 128-pixel regions (internal)");
-        if (k < count && c->rp.drawn != nullptr) {   // a changed-block record of its own: nothing in that buffer is known to hold the untouched-sensor image
-            const size_t bytes = (size_t)c->cfg.num_envs * regions * 8;
-            if (!c->drawn_ext[k] && dev_alloc(c, c->drawn_ext[k], bytes, kNoFill)) return -2;
-            TG_HIP(hipMemset(c->drawn_ext[k], 0xFF, bytes));
-        }
-    }
-    return 0;
-}
-int tg_select_obs_target(tg_ctx* c, int32_t index) {
-    if (!c || index < 0 || index > 2 || (index > 0 && c->obs_ext[index - 1] == nullptr)) return fail(-1, "tg_select_obs_target: no such target");
-    c->obs_sel = index;
-    return 0;
-}
-
 int tg_get_tile_template(tg_ctx* c, void** p) {
     if (!c || !p) return fail(-1, "NULL argument");
     *p = c->d_tile_tmpl;
@@ -1312,51 +1241,6 @@ int tg_unpack_interior(tg_ctx* c, const void* src_dev, int32_t n_images, void* d
     hipLaunchKernelGGL(k_unpack_interior, dim3((HW / 4 + 255) / 256, n_images), dim3(256), 0, c->stream, (const uint32_t*)src_dev, c->d_int_rank,
                        (const uint32_t*)c->d_nodef_gray, K, HW, n_images, (uint32_t*)dst_dev);
     TG_HIP(hipGetLastError());
-    return 0;
-}
-// the observation_mode "oracle" vectors [n][34], allocated on first use (zeroed)
-static int need_oracle(tg_ctx* c, float*& buf) { return buf ? 0 : dev_alloc(c, buf, (size_t)c->cfg.num_envs * 34 * sizeof(float)); }
-int tg_enable_oracle_obs(tg_ctx* c) {
-    if (!c) return fail(-1, "NULL ctx");
-    if (c->stack_n > 1 && !c->oracle_every_step) return fail(-1, "tg_enable_oracle_obs: call it before tg_set_frame_stack");
-    TG_ENTER(c);
-    for (float* buf : {c->d_oracle, c->d_oracle_term})    // enabled again: the rows start from zero
-        if (buf) TG_HIP(hipMemset(buf, 0, (size_t)c->cfg.num_envs * 34 * sizeof(float)));
-    if (need_oracle(c, c->d_oracle) || need_oracle(c, c->d_oracle_term)) return -2;
-    c->oracle_every_step = true;
-    return 0;
-}
-int tg_get_obs_oracle_terminal(tg_ctx* c, void** p) {
-    if (!c || !p) return fail(-1, "NULL argument");
-    if (!c->oracle_every_step) return fail(-1, "tg_get_obs_oracle_terminal: needs tg_enable_oracle_obs");
-    *p = c->d_oracle_term;
-    return 0;
-}
-int tg_copy_obs_oracle_terminal(tg_ctx* c, float* dst) {
-    if (!c || !dst) return fail(-1, "NULL argument");
-    TG_ENTER(c);
-    if (!c->oracle_every_step) return fail(-1, "tg_copy_obs_oracle_terminal: needs tg_enable_oracle_obs");
-    TG_HIP(hipMemcpyAsync(dst, c->d_oracle_term, (size_t)c->cfg.num_envs * oracle_dim(c) * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    TG_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-}
-int tg_get_obs_oracle(tg_ctx* c, void** p, int32_t* dim) {
-    if (!c || !p) return fail(-1, "NULL argument");
-    TG_ENTER(c);
-    const int d = oracle_dim(c);
-    if (int rc = need_oracle(c, c->d_oracle)) return rc;
-    if (!c->oracle_every_step) oracle_draw(c, c->d_oracle);     // (enabled: tg_step / tg_reset have already written it)
-    TG_HIP(hipGetLastError());
-    *p = c->d_oracle;
-    if (dim) *dim = d;
-    return 0;
-}
-int tg_copy_obs_oracle(tg_ctx* c, float* dst) {
-    if (!c || !dst) return fail(-1, "NULL argument");
-    void* p = nullptr; int32_t d = 0;
-    if (int rc = tg_get_obs_oracle(c, &p, &d)) return rc;
-    TG_HIP(hipMemcpyAsync(dst, p, (size_t)c->cfg.num_envs * d * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    TG_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
 
@@ -1472,22 +1356,6 @@ int tg_render_scene(tg_ctx* c) {
     return 0;
 }
 
-int tg_get_obs_visual(tg_ctx* c, void** p, int32_t terminal) {
-    if (!c || !p) return fail(-1, "NULL argument");
-    if (!c->scene_on) return fail(-1, "tg_get_obs_visual: no scene (tg_set_scene)");
-    *p = terminal ? c->d_vis_term : c->d_vis;
-    return 0;
-}
-
-int tg_copy_obs_visual(tg_ctx* c, uint8_t* dst, int32_t terminal) {
-    if (!c || !dst) return fail(-1, "NULL argument");
-    TG_ENTER(c);
-    if (!c->scene_on) return fail(-1, "tg_copy_obs_visual: no scene (tg_set_scene)");
-    TG_HIP(hipMemcpyAsync(dst, terminal ? c->d_vis_term : c->d_vis, (size_t)c->cfg.num_envs * c->scene.W * c->scene.H * 3, hipMemcpyDeviceToHost, c->stream));
-    TG_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 int tg_sync(tg_ctx* c) {
     if (!c) return fail(-1, "NULL ctx");
     TG_ENTER(c);
@@ -1504,28 +1372,6 @@ int tg_sync(tg_ctx* c) {
     return 0;
 }
 
-int tg_get_obs_tactile(tg_ctx* c, void** p) { if (!c || !p) return fail(-1, "NULL argument"); *p = obs_buf(c); return 0; }
-int tg_get_terminal_obs(tg_ctx* c, void** p) { if (!c || !p) return fail(-1, "NULL argument"); *p = c->d_term; return 0; }
-int tg_get_reward_done_dev(tg_ctx* c, void** r, void** d) {
-    if (!c) return fail(-1, "NULL ctx");
-    if (r) *r = c->st.reward;
-    if (d) *d = c->st.done;
-    return 0;
-}
-int tg_get_packed_outputs(tg_ctx* c, void** p, int64_t* obs_bytes, int64_t* total_bytes) {
-    if (!c || !p) return fail(-1, "NULL argument");
-    *p = c->d_obs;
-    if (obs_bytes) *obs_bytes = (int64_t)c->packed_obs_bytes;
-    if (total_bytes) *total_bytes = (int64_t)c->packed_bytes;
-    return 0;
-}
-int tg_get_packed_feature(tg_ctx* c, int64_t* feature_off, int32_t* dim) {
-    if (!c || !feature_off) return fail(-1, "NULL argument");
-    const bool has = env_has_feature(c->cfg.env_kind);
-    *feature_off = has ? (int64_t)c->packed_feature_off : -1;
-    if (dim) *dim = has ? 12 : 0;
-    return 0;
-}
 int tg_sample_actions(tg_ctx* c, uint64_t seed, uint64_t counter, float* dev_actions) {
     if (!c || !dev_actions) return fail(-1, "tg_sample_actions: NULL argument");
     const int total = c->cfg.num_envs * c->act_dim;
@@ -1540,173 +1386,4 @@ int tg_sample_actions(tg_ctx* c, uint64_t seed, uint64_t counter, float* dev_act
     TG_HIP(hipGetLastError());
     return 0;
 }
-int tg_get_obs_feature(tg_ctx* c, void** p, int32_t* dim, int32_t terminal) {
-    if (!c || !p) return fail(-1, "NULL argument");
-    if (!env_has_feature(c->cfg.env_kind))
-        return fail(-1, "tg_get_obs_feature: this env has no extended_feature observation");
-    *p = terminal ? c->st.term_feature : c->st.feature;
-    if (dim) *dim = 12;
-    return 0;
-}
-int tg_copy_obs_feature(tg_ctx* c, float* dst, int32_t terminal) {
-    if (!c || !dst) return fail(-1, "NULL argument");
-    TG_ENTER(c);
-    if (!env_has_feature(c->cfg.env_kind))
-        return fail(-1, "tg_copy_obs_feature: this env has no extended_feature observation");
-    TG_HIP(hipMemcpyAsync(dst, terminal ? c->st.term_feature : c->st.feature, (size_t)c->cfg.num_envs * 12 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    TG_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-}
-int tg_get_reward_done(tg_ctx* c, float* reward, uint8_t* done) {
-    if (!c) return fail(-1, "NULL ctx");
-    TG_ENTER(c);
-    const int n = c->cfg.num_envs;
-    if (reward) TG_HIP(hipMemcpyAsync(reward, c->st.reward, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    if (done) TG_HIP(hipMemcpyAsync(done, c->st.done, (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    TG_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-}
-int tg_copy_obs_tactile(tg_ctx* c, uint8_t* dst, int32_t terminal) {
-    if (!c || !dst) return fail(-1, "NULL argument");
-    TG_ENTER(c);
-    TG_HIP(hipMemcpyAsync(dst, terminal ? c->d_term : obs_buf(c), (size_t)c->cfg.num_envs * c->H * c->W, hipMemcpyDeviceToHost, c->stream));
-    TG_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
-int tg_copy_obs_rows(tg_ctx* c, int32_t visual, int32_t terminal, const int32_t* env_ids, int32_t count, uint8_t* dst) {
-    if (!c || count < 0 || (count > 0 && (!env_ids || !dst))) return fail(-1, "tg_copy_obs_rows: bad argument");
-    TG_ENTER(c);
-    if (visual && !c->scene_on) return fail(-1, "tg_copy_obs_rows: no scene (tg_set_scene)");
-    const size_t img = visual ? (size_t)c->scene.W * c->scene.H * 3 : (size_t)c->H * c->W;
-    const uint8_t* src = visual ? (terminal ? c->d_vis_term : c->d_vis) : (terminal ? c->d_term : obs_buf(c));
-    for (int32_t k = 0; k < count; ++k)
-        if (env_ids[k] < 0 || env_ids[k] >= c->cfg.num_envs) return fail(-1, "tg_copy_obs_rows: env id out of range");
-    // through a pinned staging block (64 images at a time): a device -> pageable copy of 16 KB is a staged, blocking copy of its own each time
-    constexpr int kChunk = 64;
-    if (c->h_rows_bytes < img * kChunk) {
-        if (c->h_rows) { (void)hipHostFree(c->h_rows); c->h_rows = nullptr; c->h_rows_bytes = 0; }
-        TG_HIP(hipHostMalloc((void**)&c->h_rows, img * kChunk, hipHostMallocDefault));
-        c->h_rows_bytes = img * kChunk;
-    }
-    for (int32_t k0 = 0; k0 < count; k0 += kChunk) {
-        const int32_t m = count - k0 < kChunk ? count - k0 : kChunk;
-        for (int32_t k = 0; k < m; ++k)
-            TG_HIP(hipMemcpyAsync(c->h_rows + (size_t)k * img, src + (size_t)env_ids[k0 + k] * img, img, hipMemcpyDeviceToHost, c->stream));
-        TG_HIP(hipStreamSynchronize(c->stream));
-        memcpy(dst + (size_t)k0 * img, c->h_rows, (size_t)m * img);
-    }
-    return 0;
-}
-
-// ---- frame stack (VecFrameStack on the device; tg_stack.hip) ----
-static void free_stack(tg_ctx* c) {
-    dev_release(c, c->d_stack); dev_release(c, c->d_stack_term); dev_release(c, c->d_stack_rec); dev_release(c, c->d_vstack); dev_release(c, c->d_vstack_term);
-    for (int k = 0; k < 2; ++k) { dev_release(c, c->d_stack_vec[k]); dev_release(c, c->d_stack_vec_term[k]); }
-    c->stack_vec_dim[0] = c->stack_vec_dim[1] = 0;
-    c->stack_n = 1;
-}
-// (Re)allocates every stack for n frames in layout cf, all zero.
-static int alloc_stacks(tg_ctx* c, int n, int cf) {
-    if (c->scene_every_step && (n > 1 || cf) && c->scene.W % 16) return fail(-1, "stacked scene images need a width that is a multiple of 16");
-    TG_HIP(hipStreamSynchronize(c->stream));
-    free_stack(c);
-    c->obs_cf = cf;
-    const size_t envs = (size_t)c->cfg.num_envs;
-    if (n > 1) {
-        const size_t img = envs * c->H * c->W * n, rec = envs * (c->H / 16) * (c->W / 16);   // (the same bytes in either layout)
-        if (dev_alloc(c, c->d_stack, img) || dev_alloc(c, c->d_stack_term, img) || dev_alloc(c, c->d_stack_rec, rec)) return -2;   // rec 0: no slot holds the template, the first update writes every block
-        c->stack_vec_dim[0] = c->oracle_every_step ? oracle_dim(c) : 0;
-        c->stack_vec_dim[1] = env_has_feature(c->cfg.env_kind) ? feature_dim(c) : 0;
-        for (int k = 0; k < 2; ++k) {
-            if (!c->stack_vec_dim[k]) continue;
-            const size_t b = envs * c->stack_vec_dim[k] * n * sizeof(float);
-            if (dev_alloc(c, c->d_stack_vec[k], b) || dev_alloc(c, c->d_stack_vec_term[k], b)) return -2;
-        }
-        c->stack_n = n;
-    }
-    if (c->scene_every_step && (n > 1 || cf)) {      // the visual observation modes
-        const size_t b = envs * c->scene.H * c->scene.W * 3 * n;
-        if (dev_alloc(c, c->d_vstack, b) || dev_alloc(c, c->d_vstack_term, b)) return -2;
-    }
-    TG_HIP(hipDeviceSynchronize());
-    return 0;
-}
-int tg_set_frame_stack(tg_ctx* c, int32_t n) {
-    if (!c) return fail(-1, "NULL ctx");
-    if (n < 1 || n > kStackMax) return fail(-1, "tg_set_frame_stack: n must be in [1, 8]");
-    if (n > 1 && (c->obs_ext[0] || c->obs_ext[1])) return fail(-1, "tg_set_frame_stack: not with render targets of the caller (tg_set_obs_targets: sharded runs)");
-    TG_ENTER(c);
-    return alloc_stacks(c, n, c->obs_cf);
-}
-int tg_set_obs_layout(tg_ctx* c, int32_t channels_first) {
-    if (!c) return fail(-1, "NULL ctx");
-    if (channels_first != 0 && channels_first != 1) return fail(-1, "tg_set_obs_layout: channels_first must be 0 or 1");
-    if (channels_first && (c->obs_ext[0] || c->obs_ext[1])) return fail(-1, "tg_set_obs_layout: not with render targets of the caller (tg_set_obs_targets: sharded runs)");
-    TG_ENTER(c);
-    return alloc_stacks(c, c->stack_n, channels_first);
-}
-int tg_get_obs_layout(tg_ctx* c, int32_t* channels_first) {
-    if (!c || !channels_first) return fail(-1, "NULL argument");
-    *channels_first = c->obs_cf;
-    return 0;
-}
-int tg_get_frame_stack(tg_ctx* c, int32_t* n) {
-    if (!c || !n) return fail(-1, "NULL argument");
-    *n = c->stack_n;
-    return 0;
-}
-// key TG_OBS_KEY_*: (device pointer, bytes per env row) of the current or terminal stack
-static int stack_buffer(tg_ctx* c, int32_t key, int32_t terminal, void** p, size_t* row) {
-    if (key == TG_OBS_KEY_VISUAL) {
-        if (!c->d_vstack) return fail(-1, "no visual stack (a scene drawn every step, with tg_set_frame_stack n > 1 or tg_set_obs_layout 1)");
-        *p = terminal ? c->d_vstack_term : c->d_vstack;
-        *row = (size_t)c->scene.H * c->scene.W * 3 * c->stack_n;
-        return 0;
-    }
-    if (key == TG_OBS_KEY_TACTILE && c->stack_n <= 1 && c->obs_cf) {   // [n][H][W] is [n][1][H][W]: the observation buffers themselves
-        *p = terminal ? c->d_term : c->d_obs;
-        *row = (size_t)c->H * c->W;
-        return 0;
-    }
-    if (c->stack_n <= 1) return fail(-1, "no frame stack (tg_set_frame_stack n > 1)");
-    if (key == TG_OBS_KEY_TACTILE) {
-        *p = terminal ? c->d_stack_term : c->d_stack;
-        *row = (size_t)c->H * c->W * c->stack_n;
-        return 0;
-    }
-    const int k = key == TG_OBS_KEY_ORACLE ? 0 : key == TG_OBS_KEY_FEATURE ? 1 : -1;
-    if (k < 0) return fail(-1, "unknown observation key");
-    if (!c->d_stack_vec[k]) return fail(-1, k == 0 ? "no stacked oracle observation (tg_enable_oracle_obs before tg_set_frame_stack)" : "this env has no extended_feature observation");
-    *p = terminal ? c->d_stack_vec_term[k] : c->d_stack_vec[k];
-    *row = (size_t)c->stack_vec_dim[k] * c->stack_n * sizeof(float);
-    return 0;
-}
-int tg_get_obs_stack(tg_ctx* c, int32_t key, int32_t terminal, void** p) {
-    if (!c || !p) return fail(-1, "NULL argument");
-    size_t row = 0;
-    return stack_buffer(c, key, terminal, p, &row);
-}
-int tg_copy_obs_stack(tg_ctx* c, int32_t key, int32_t terminal, void* dst) {
-    if (!c || !dst) return fail(-1, "NULL argument");
-    TG_ENTER(c);
-    void* p = nullptr; size_t row = 0;
-    if (int rc = stack_buffer(c, key, terminal, &p, &row)) return rc;
-    TG_HIP(hipMemcpyAsync(dst, p, row * c->cfg.num_envs, hipMemcpyDeviceToHost, c->stream));
-    TG_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-}
-int tg_copy_obs_stack_rows(tg_ctx* c, int32_t key, int32_t terminal, const int32_t* env_ids, int32_t count, void* dst) {
-    if (!c || count < 0 || (count > 0 && (!env_ids || !dst))) return fail(-1, "tg_copy_obs_stack_rows: bad argument");
-    TG_ENTER(c);
-    void* p = nullptr; size_t row = 0;
-    if (int rc = stack_buffer(c, key, terminal, &p, &row)) return rc;
-    for (int32_t k = 0; k < count; ++k)
-        if (env_ids[k] < 0 || env_ids[k] >= c->cfg.num_envs) return fail(-1, "tg_copy_obs_stack_rows: env id out of range");
-    for (int32_t k = 0; k < count; ++k)     // (a finished env's row: a few per step)
-        TG_HIP(hipMemcpyAsync((uint8_t*)dst + (size_t)k * row, (const uint8_t*)p + (size_t)env_ids[k] * row, row, hipMemcpyDeviceToHost, c->stream));
-    TG_HIP(hipStreamSynchronize(c->stream));
-    return 0;
-}
-
 }  // extern "C"

@@ -267,7 +267,7 @@ struct tg_ctx {
     tg::State bk{};                    // the bank view: st's layout, the reset-written arrays in allocations of the bank's own
     tg::BankAux aux{};
     int bank_mode = 0;                 // 0 off, 1 refills on bank_stream every bank_every steps, 2 as 1 and waited for (tests)
-    uint8_t* h_rows = nullptr;         // tg_copy_obs_rows: pinned staging block
+    uint8_t* h_rows = nullptr;         // tg_copy_obs_rows, tg_copy_obs_stack_rows (copy_rows, tg_api_obs.hip): pinned staging block
     size_t h_rows_bytes = 0;
     int bank_every = 8;
     static constexpr int kBankRing = 16, kBankLag = 8;    // bank_refill: markers on the step stream, one per visit; the host stays <= kBankLag visits ahead
@@ -413,7 +413,18 @@ static int need_device() {
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(-3, "no HIP device visible — no CPU fallback");
     return 0;
 }
+static inline int oracle_dim(const tg_ctx* c) {              // floats per env of the observation_mode "oracle" vector
+    switch (c->cfg.env_kind) {
+        case TG_ENV_EDGE_FOLLOW: return 10;
+        case TG_ENV_SURFACE_FOLLOW_AUTO: return 20;
+        case TG_ENV_OBJECT_BALANCE: return 26;
+        case TG_ENV_OBJECT_PUSH: return 30;
+        default: return 34;
+    }
+}
 bool use_fused_step(const tg_ctx* c);                        // tg_api.hip
+void oracle_draw(tg_ctx* c, float* dst);                     // tg_api.hip: every env's oracle vector into dst [n][oracle_dim], on the context's stream
+int stack_update(tg_ctx* c, int mode, const uint8_t* flag);  // tg_api_obs.hip: the last launch of tg_step, tg_step_random and tg_reset
 }  // namespace tg
 
 // Every entry point that touches the device first makes the context's device current: the caller may have switched devices
