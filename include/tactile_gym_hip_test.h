@@ -3,8 +3,8 @@
  *
  * TEST INFRASTRUCTURE, not part of the boundary a maintainer binds (that is tactile_gym_hip.h / libtactile_gym_hip.so): built by
  * csrc/build.sh next to the product library from the same device headers, loaded only by tests/ (tactile_gym_amd._capi.test_lib()).
- * Translation units: tg_narrow_test.hip, tg_selftest.hip, tg_render_test.hip, tg_scene_test.hip and tg_stack_test.hip, the last three linked
- * with the product's own tg_raster.o, tg_scene.o and tg_stack.o.
+ * Translation units: tg_narrow_test.hip, tg_selftest.hip, tg_physics_test.hip, tg_render_test.hip, tg_scene_test.hip and tg_stack_test.hip, the
+ * last three linked with the product's own tg_raster.o, tg_scene.o and tg_stack.o.
  * Every function returns 0 on success, -1 bad argument, -2 no HIP device / allocation failed, -3 launch failed (tg_selftest_stack: the
  * launcher's own value).
  */
@@ -157,6 +157,24 @@ typedef struct tg_stack_test {
     const uint8_t* flag;
 } tg_stack_test;
 int tg_selftest_stack(const tg_stack_test* t, void* stream);
+/* The device helpers of csrc/tg_physics.hpp (and rot_error of csrc/tg_kernels.hpp) one by one (csrc/tg_physics_test.hip), for T = double
+ * (dtype 0) or float (dtype 1).  Case i is in [i][in_w], converted to T in the kernel, and runs in lane i % 64 of the one-wavefront workgroup
+ * i / 64: THE CALLER DECIDES WHICH CASES SHARE A WAVEFRONT, and with it the outcome of the helpers' __any / __all votes; n is a multiple of 64
+ * (pad with copies of a case: no idle lane votes).  out [i][out_w]; an integer result is the last column.  Quaternions x, y, z, w; matrices
+ * row-major.  op: in -> out
+ *    0 quat_from_euler  r, p, y -> q            1 euler_from_quat  q -> r, p, y        2 mat_from_quat  q -> R[9]       3 quat_from_mat  R[9] -> q
+ *    4 quat_mul  a, b -> q                      5 axis_angle  axis[3], angle -> R[9]   6 rot_error  Rt[9], R[9] -> e[3] 7 plane_space  n[3] -> t1[3], t2[3]
+ *    8 trsqrt  x -> y      9 trcp  x -> y      10 tsqrt_fast  x -> y                  11 inverse(S3)  xx, xy, xz, yy, yz, zz -> the same of the inverse
+ *   12 friction_clamp  s1, s2, limit, cone (0: pyramid) -> s1, s2                      13 sincos_small  x -> sin, cos
+ *   14 trig_init + k x (q += dq; trig_advance), N = 6:  k (0..24), q[6], dq[24][6] -> s[6], c[6], q[6]
+ *   15 k x integrate_rotation:  k (0..240), R[9], w[3], dt -> R[9]
+ *   16 solve_pivoted<T,6>  A[6][6], b[6] -> x[6]       17 solve_pivoted<T,8>  A[8][8], b[8] -> x[8]       18 pinv_apply<T,8>  J[6][8], b[6] -> x[8]
+ *   19 pgs_unclamped  20 pgs_unclamped_blocks  21 pgs_clamped  22 pgs_threshold, N = 6;  23 - 26 the same, N = 8:
+ *      Minv[N][N], rimp[N], jdi[N], iters, maximp, res_thr -> dv[N], the function's integer result (pgs_clamped: 0)
+ * The loop counts (k, iters) stand around a wave vote and must be equal in the 64 lanes of a wavefront.  -1, nothing launched: unknown op or
+ * dtype, a NULL pointer, n no positive multiple of 64, widths other than the op's, a loop count that is out of range or differs inside a
+ * wavefront. */
+int tg_selftest_physics(int32_t op, int32_t dtype, int32_t n, int32_t in_w, const double* in, int32_t out_w, double* out);
 /* The message of the last failing call of this library on the calling thread. */
 const char* tg_selftest_last_error(void);
 

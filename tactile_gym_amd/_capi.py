@@ -387,6 +387,7 @@ TEST_SYMBOLS = {
                                          C.POINTER(C.c_int32), _fp, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "tg_selftest_scene": (C.c_int, [C.POINTER(TgSceneTest), C.c_int32, _fp, _u8p, _u8p, _u8p]),
     "tg_selftest_stack": (C.c_int, [C.POINTER(TgStackTest), C.c_void_p]),
+    "tg_selftest_physics": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp]),
     "tg_selftest_last_error": (C.c_char_p, []),
 }
 # raster kernel ids of tg_selftest_render (TG_RK_*)
