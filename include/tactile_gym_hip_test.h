@@ -3,8 +3,8 @@
  *
  * TEST INFRASTRUCTURE, not part of the boundary a maintainer binds (that is tactile_gym_hip.h / libtactile_gym_hip.so): built by
  * csrc/build.sh next to the product library from the same device headers, loaded only by tests/ (tactile_gym_amd._capi.test_lib()).
- * Translation units: tg_narrow_test.hip, tg_selftest.hip, tg_physics_test.hip, tg_render_test.hip, tg_scene_test.hip and tg_stack_test.hip, the
- * last three linked with the product's own tg_raster.o, tg_scene.o and tg_stack.o.
+ * Translation units: tg_narrow_test.hip, tg_selftest.hip, tg_physics_test.hip, tg_state_test.hip, tg_render_test.hip, tg_scene_test.hip and
+ * tg_stack_test.hip, the last three linked with the product's own tg_raster.o, tg_scene.o and tg_stack.o.
  * Every function returns 0 on success, -1 bad argument, -2 no HIP device / allocation failed, -3 launch failed (tg_selftest_stack: the
  * launcher's own value).
  */
@@ -175,6 +175,27 @@ int tg_selftest_stack(const tg_stack_test* t, void* stream);
  * dtype, a NULL pointer, n no positive multiple of 64, widths other than the op's, a loop count that is out of range or differs inside a
  * wavefront. */
 int tg_selftest_physics(int32_t op, int32_t dtype, int32_t n, int32_t in_w, const double* in, int32_t out_w, double* out);
+/* Writes arm and free-object states into a context of the product library (csrc/tg_state_test.hip), so that a test can start the step kernels
+ * of object_push / object_roll / object_balance anywhere and not only at the reset pose (the product's own joint-state setter refuses envs with
+ * a free object).  Every pointer is optional; the arrays are AoS [num_envs][k] doubles: mask [n] bytes (NULL: every env; an env whose byte is
+ * 0 keeps all it holds), q, qd [n][ndof], body_pos [3], body_rot [9] row-major, body_linvel [3], body_angvel [3] (the cube, the marble, the
+ * pole / round plate, the spinning plate's spool), ball_pos, ball_linvel, ball_angvel [3] (ball_on_plate), dish_state [18] = position,
+ * rotation, linear and angular velocity (spinning_plate), goal_id [n] int32 (object_push, 0 .. traj_n_points; traj_n_points = past the last).
+ * For the masked envs the given fields are transposed into the context's SoA state and what a teleport clears is cleared: the solver licence,
+ * the pending one-shot force / torque of the last reset (with the ball's torque), the count of the cached contact manifold (tip - cube, dish -
+ * spool), the contact pairs of the last tick.  The RNG, step count, trajectory, mass / radius, embed distance, gravity and episode return stay.
+ * The context's stream is synchronised; nothing is rendered and no observation refreshed - the next step recomputes all it reports from the
+ * state.  -1 and NOTHING WRITTEN: a NULL argument, a field the env kind does not have, a non-finite value, a rotation further than 1e-9 from
+ * orthonormal (or with a negative determinant), a goal_id out of range.  -2: a HIP call failed. */
+typedef struct tg_body_state_test {
+    const uint8_t* mask;
+    const double *q, *qd;
+    const double *body_pos, *body_rot, *body_linvel, *body_angvel;
+    const double *ball_pos, *ball_linvel, *ball_angvel;
+    const double* dish_state;
+    const int32_t* goal_id;
+} tg_body_state_test;
+int tg_selftest_set_body_state(tg_ctx* ctx, const tg_body_state_test* state);
 /* The message of the last failing call of this library on the calling thread. */
 const char* tg_selftest_last_error(void);
 

@@ -358,6 +358,11 @@ class TgStackTest(C.Structure):      # tg_stack_test
                 + [("vis_H", C.c_int32), ("vis_W", C.c_int32), ("flag", C.c_void_p)])
 
 
+class TgBodyStateTest(C.Structure):  # tg_body_state_test: host arrays, AoS [num_envs][k]; every pointer optional
+    _fields_ = ([("mask", _u8p)] + [(k, _dp) for k in ("q", "qd", "body_pos", "body_rot", "body_linvel", "body_angvel", "ball_pos", "ball_linvel",
+                                                       "ball_angvel", "dish_state")] + [("goal_id", C.POINTER(C.c_int32))])
+
+
 # libtactile_gym_hip_test.so (include/tactile_gym_hip_test.h): device self-tests, test infrastructure - tests/ are the only callers
 TEST_LIB_PATH = os.path.join(os.path.dirname(LIB_PATH), "libtactile_gym_hip_test.so")
 TEST_SYMBOLS = {
@@ -388,6 +393,7 @@ TEST_SYMBOLS = {
     "tg_selftest_scene": (C.c_int, [C.POINTER(TgSceneTest), C.c_int32, _fp, _u8p, _u8p, _u8p]),
     "tg_selftest_stack": (C.c_int, [C.POINTER(TgStackTest), C.c_void_p]),
     "tg_selftest_physics": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp]),
+    "tg_selftest_set_body_state": (C.c_int, [_ctx, C.POINTER(TgBodyStateTest)]),
     "tg_selftest_last_error": (C.c_char_p, []),
 }
 # raster kernel ids of tg_selftest_render (TG_RK_*)
