@@ -797,6 +797,43 @@ int tg_conv_stem_bwd(const void* x_dev, int32_t x_is_float, int32_t channels_fir
                      const float* y_dev, const float* dy_dev, float scale, float* dweight_dev, float* dbias_dev, void* workspace_dev,
                      int64_t workspace_bytes, void* hip_stream);
 
+/* ---- device NatureCNN tail: conv2, conv3 and the linear layer as one kernel family ----------------------------------------------
+ * A valid (unpadded) strided convolution with bias and ReLU.  Context free; the launches go to hip_stream, nothing is allocated or
+ * synchronised.  x_dev: float32 [B][Cin][H][W], contiguous; weight_dev: float32 [Cout][Cin][KH][KW] (torch's layout); bias_dev: float32 [Cout];
+ * y_dev: float32 [B][Cout][OH][OW], OH = (H - KH) / stride + 1, OW = (W - KW) / stride + 1 (floor).  NatureCNN's Conv2d(32, 64, 4, 2) and
+ * Conv2d(64, 64, 3, 1) are instances; Flatten + Linear(64 h w, F) is the instance Cin = 64, H = KH = h, W = KW = w, Cout = F, stride 1
+ * (OH = OW = 1, K = 64 h w): nn.Linear's [F][64 h w] weight is that kernel, flattened.  Per output element, with k = (c KH + ky) KW + kx and
+ * K = Cin KH KW:
+ *     acc = 0;  for k = 0 .. K-1 ascending: acc = fmaf(x_k, w[co][k], acc);  z = acc + b[co];  y = z > 0 ? z : (z != z ? z : 0)
+ * in float32, bit for bit: ONE chain for every shape (K is not cut into segments), so an element's arithmetic order is a function of the
+ * layer's shape alone - never of B, of the row's index or of where its tile falls.  ONE launch.
+ *
+ * The backward call (at most THREE launches: partials, reduction, dx): with g = dy where y > 0 and 0 elsewhere (y_dev: the forward's output),
+ *     dbias[co] = sum_m g[m][co],   dweight[co][k] = sum_m g[m][co] x[m][k],   m = (b OH + oy) OW + ox
+ * split over workgroups into partials in workspace_dev (the caller's, at least tg_conv_relu_bwd_workspace(...) bytes; overwritten) and reduced
+ * in a fixed order without atomics: the same inputs give the same bits on every run.  The number of partials grows with M = B OH OW:
+ * P = max(1, min(ceil(M / 256), 64, 2^25 / (Cout K))), the workspace is 4 P (Cout K + 4 Cout) bytes.  And
+ *     dx[b][c][iy][ix] = one chain over j = (co KH + ky) KW + kx ascending of g[b][co][oy][ox] w[co][c][ky][kx],
+ *     oy = (iy - ky) / stride, ox = (ix - kx) / stride;  a term whose division is inexact or whose (oy, ox) is outside the output is fed as
+ *     0 w or skipped (the same bits for finite w), so input rows and columns that no output reads get 0.
+ * dx_dev may be NULL: then no dx kernel is launched (frozen upstream layers).  dweight_dev [Cout][Cin][KH][KW], dbias_dev [Cout] and dx_dev
+ * [B][Cin][H][W] are overwritten.  B = 0 does nothing.  Errors, each without a launch: a NULL pointer (but dx_dev), Cin outside
+ * [1, TG_CONV_MAX_CIN], Cout no multiple of TG_CONV_COUT_STEP or above TG_CONV_MAX_COUT, KH or KW outside [1, TG_CONV_MAX_KERNEL] or larger
+ * than H or W, stride outside [1, TG_CONV_MAX_STRIDE], an odd K (the MFMA takes two k per instruction), B < 0, B H W above TG_CONV_MAX_POSITIONS
+ * (one launch), a workspace that is too small (the size query returns the negative code). */
+#define TG_CONV_MAX_CIN 64
+#define TG_CONV_COUT_STEP 32
+#define TG_CONV_MAX_COUT 512
+#define TG_CONV_MAX_KERNEL 16
+#define TG_CONV_MAX_STRIDE 4
+#define TG_CONV_MAX_POSITIONS 536870880
+int tg_conv_relu(const float* x_dev, int64_t B, int32_t Cin, int32_t H, int32_t W, const float* weight_dev, const float* bias_dev, int32_t Cout,
+                 int32_t KH, int32_t KW, int32_t stride, float* y_dev, void* hip_stream);
+int64_t tg_conv_relu_bwd_workspace(int64_t B, int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t KH, int32_t KW, int32_t stride);
+int tg_conv_relu_bwd(const float* x_dev, int64_t B, int32_t Cin, int32_t H, int32_t W, const float* weight_dev, const float* y_dev,
+                     const float* dy_dev, int32_t Cout, int32_t KH, int32_t KW, int32_t stride, float* dweight_dev, float* dbias_dev,
+                     float* dx_dev, void* workspace_dev, int64_t workspace_bytes, void* hip_stream);
+
 /* ---- device loss heads: what stable_baselines3 does between the network's output and the scalar loss ---------------------------
  * Context free; the launches go to hip_stream, nothing is allocated or synchronised.  Float32 arithmetic with one rounding per operation; exp,
  * tanh and log are evaluated in double on the float32 argument and rounded once.  Every sum over rows is taken in double and rounded to float32

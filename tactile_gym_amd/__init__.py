@@ -26,6 +26,7 @@ loudly when the HIP library or a GPU is missing.
     critic_stats, actor_stats, n_updates = tg.train.sac_train(actor, critic, critic_target, actor_opt, critic_opt, rb, head, 1, 64, 0.95, 0.005, log_ent_coef=log_ent_coef, ent_coef_optimizer=ent_opt, target_entropy=-A)   # SAC.train over the device pieces
     heads = tg.ActorCriticHeads(features_dim, A, dict(pi=[256, 256], vf=[256, 256])); policy = lambda obs: heads(extractor(obs))   # SB3's MlpExtractor, action_net and value_net in one launch (tg.mlp; imports torch); tg.SacActorHeads, tg.ContinuousCriticHeads: SAC's
     CustomCombinedExtractor(observation_space, cnn_base=tg.NatureCNN)   # SB3's NatureCNN, its first layer one launch on the uint8 images (tg.torch_layers; imports torch)
+    CustomCombinedExtractor(observation_space, cnn_base=functools.partial(tg.NatureCNN, device_tail=True))   # and conv2, conv3 and the linear layer in HIP too: a row's features have one arithmetic order whatever the batch (tg.conv_relu, tg.linear_relu)
 """
 from . import rl_envs  # noqa: F401  (registers the env ids)
 from .registry import make, make_vec, register, registered_ids  # noqa: F401
@@ -53,7 +54,7 @@ def __getattr__(name):
     if name in ("ppo_loss", "sac_critic_loss", "sac_actor_loss"):
         import importlib
         return getattr(importlib.import_module(".loss_head", __name__), name)
-    if name in ("NatureCNN", "ConvStem", "conv_stem"):
+    if name in ("NatureCNN", "ConvStem", "conv_stem", "ConvRelu", "LinearRelu", "conv_relu", "linear_relu"):
         import importlib
         return getattr(importlib.import_module(".torch_layers", __name__), name)
     if name in ("mlp_towers", "ActorCriticHeads", "SacActorHeads", "ContinuousCriticHeads"):

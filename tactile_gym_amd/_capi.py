@@ -38,6 +38,7 @@ HEAD_GAUSSIAN, HEAD_SQUASHED, HEAD_UNIFORM, HEAD_MAX_ACT = 0, 1, 2, 16   # TG_HE
 LOSS_PATH_AUTO, LOSS_PATH_ONE, LOSS_PATH_GRID, LOSS_ONE_MAX_ROWS = 0, 1, 2, 4096   # TG_LOSS_* (tg_ppo_loss)
 SAC_MAX_CRITICS, SAC_MAX_ROWS = 4, 65536   # TG_SAC_* (tg_sac_critic_loss, tg_sac_actor_loss)
 STEM_KERNEL, STEM_STRIDE, STEM_OUT, STEM_MAX_CIN = 8, 4, 32, 12   # TG_STEM_* (tg_conv_stem, tg_conv_stem_bwd)
+CONV_MAX_CIN, CONV_COUT_STEP, CONV_MAX_COUT, CONV_MAX_KERNEL, CONV_MAX_STRIDE, CONV_MAX_POSITIONS = 64, 32, 512, 16, 4, 536870880   # TG_CONV_* (tg_conv_relu, tg_conv_relu_bwd)
 MLP_MAX_TOWERS, MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_IN, MLP_MAX_ROWS = 4, 4, 256, 1024, 2147483616   # TG_MLP_* (tg_mlp_forward, tg_mlp_backward)
 MLP_ACT = {"none": 0, "tanh": 1, "relu": 2}   # TG_MLP_ACT_*
 OBS_STACK_KEY = dict(OBS_KEY, visual=3)   # + TG_OBS_KEY_VISUAL (ABI v16: the scene camera's images)
@@ -271,6 +272,11 @@ SYMBOLS = {
     "tg_conv_stem_bwd_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "tg_conv_stem_bwd": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "tg_conv_relu": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                               C.c_int32, C.c_void_p, C.c_void_p]),
+    "tg_conv_relu_bwd_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tg_conv_relu_bwd": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "tg_mlp_forward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(TgMlpTower), C.c_int32, C.c_int32, C.c_void_p]),
     "tg_mlp_backward_workspace": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.POINTER(TgMlpTower), C.c_int32]),
     "tg_mlp_backward": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.POINTER(TgMlpTower), C.c_int32, C.c_void_p, C.c_void_p,

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds libtactile_gym_hip.so (the product) and libtactile_gym_hip_test.so (device self-tests, loaded by tests/ only) for gfx950 (MI355X) in-tree.  hipcc cross-compiles without a GPU.
-#   tg_raster.hip, tg_scene.hip, tg_noise.hip, tg_augment.hip (the RAD translate augmentation, bit-exact specification: DESIGN.md 4.8; tg_augment_core.h holds what it shares with tg_affine.hip) and tg_rollout.hip (the device rollout buffer, bit-exact GAE: DESIGN.md 4.9), tg_replay.hip (the device replay buffer: DESIGN.md 4.10), tg_affine.hip (the general affine augmentation, bit-exact warp: DESIGN.md 4.11), tg_vecnorm.hip (the device VecNormalize, bit-exact float64 statistics: DESIGN.md 4.12), tg_action_head.hip (the device action heads, one rounding per float32 operation: DESIGN.md 4.13), tg_conv_stem.hip (the device conv stem on the f32 MFMA, one k-ordered fmaf chain per output: DESIGN.md 4.14), tg_loss_head.hip (the device loss heads, one rounding per float32 operation and double row sums in a fixed order; tg_head_core.h holds what it shares with tg_action_head.hip: DESIGN.md 4.15), tg_sac_loss.hip (SAC's device losses, the same rules; tg_loss_core.h holds the chunk sum it shares with tg_loss_head.hip: DESIGN.md 4.16), tg_mlp.hip (the device MLP towers on the f32 MFMA - SB3's policy, value and critic heads, one k-ordered fmaf chain per output: DESIGN.md 4.17) are compiled with -ffp-contract=off (bit-exact raster specification);
+#   tg_raster.hip, tg_scene.hip, tg_noise.hip, tg_augment.hip (the RAD translate augmentation, bit-exact specification: DESIGN.md 4.8; tg_augment_core.h holds what it shares with tg_affine.hip) and tg_rollout.hip (the device rollout buffer, bit-exact GAE: DESIGN.md 4.9), tg_replay.hip (the device replay buffer: DESIGN.md 4.10), tg_affine.hip (the general affine augmentation, bit-exact warp: DESIGN.md 4.11), tg_vecnorm.hip (the device VecNormalize, bit-exact float64 statistics: DESIGN.md 4.12), tg_action_head.hip (the device action heads, one rounding per float32 operation: DESIGN.md 4.13), tg_conv_stem.hip (the device conv stem on the f32 MFMA, one k-ordered fmaf chain per output: DESIGN.md 4.14), tg_loss_head.hip (the device loss heads, one rounding per float32 operation and double row sums in a fixed order; tg_head_core.h holds what it shares with tg_action_head.hip: DESIGN.md 4.15), tg_sac_loss.hip (SAC's device losses, the same rules; tg_loss_core.h holds the chunk sum it shares with tg_loss_head.hip: DESIGN.md 4.16), tg_mlp.hip (the device MLP towers on the f32 MFMA - SB3's policy, value and critic heads, one k-ordered fmaf chain per output: DESIGN.md 4.17), tg_conv.hip (the device NatureCNN tail - conv2, conv3 and the linear layer as one convolution family on the f32 MFMA, one k-ordered fmaf chain per output: DESIGN.md 4.21) are compiled with -ffp-contract=off (bit-exact raster specification);
 #   tg_api.hip (configuration, creation, step / reset launches; + tg_api_obs.hip - the observation entries, no kernel of its own -, tg_api_state.hip, tg_api_ops.hip: the rest of the C ABI, sharing tg_ctx.hpp), tg_contact_wave.hip (wave-per-env contact solver) and tg_exchange.hip (multi-GPU payloads, integer only), tg_stack.hip (the frame stack, byte moves only) with the default contraction (FMA); tg_narrow_test.hip (GJK / EPA self-test) switches contraction off by pragma; tg_stack_test.hip (the test entry of the frame-stack launchers, no kernel of its own) needs no flag; tg_physics_test.hip (the test entry of tg_physics.hpp's helpers) keeps FMA, as tg_api.hip compiles them; tg_state_test.hip (the test entry that writes object states into a context, no kernel of its own) needs no flag; tg_fused.hip (step + render in one launch) keeps FMA for the physics and
 #   takes the raster from tg_raster_dev.hpp, whose pragma switches contraction off for everything after it.
 set -euo pipefail
@@ -50,8 +50,9 @@ cc tg_mlp -ffp-contract=off & p27=$!
 cc tg_api_obs & p28=$!
 cc tg_physics_test & p29=$!
 cc tg_state_test & p30=$!
-wait $p1; wait $p2; wait $p3; wait $p4; wait $p5; wait $p6; wait $p7; wait $p8; wait $p9; wait $p10; wait $p11; wait $p12; wait $p13; wait $p14; wait $p15; wait $p16; wait $p17; wait $p18; wait $p19; wait $p20; wait $p21; wait $p22; wait $p23; wait $p24; wait $p25; wait $p26; wait $p27; wait $p28; wait $p29; wait $p30    # each wait returns its job's status: a failed translation unit fails the build (set -e)
-$HIPCC --offload-arch=gfx950 -shared -fPIC "$OUT/tg_raster.o" "$OUT/tg_noise.o" "$OUT/tg_api.o" "$OUT/tg_contact_wave.o" "$OUT/tg_scene.o" "$OUT/tg_exchange.o" "$OUT/tg_fused.o" "$OUT/tg_broadphase.o" "$OUT/tg_api_state.o" "$OUT/tg_api_ops.o" "$OUT/tg_spin.o" "$OUT/tg_stack.o" "$OUT/tg_augment.o" "$OUT/tg_rollout.o" "$OUT/tg_replay.o" "$OUT/tg_affine.o" "$OUT/tg_vecnorm.o" "$OUT/tg_action_head.o" "$OUT/tg_conv_stem.o" "$OUT/tg_loss_head.o" "$OUT/tg_sac_loss.o" "$OUT/tg_mlp.o" "$OUT/tg_api_obs.o" -o "$OUT/libtactile_gym_hip.so"
+cc tg_conv -ffp-contract=off & p31=$!
+wait $p1; wait $p2; wait $p3; wait $p4; wait $p5; wait $p6; wait $p7; wait $p8; wait $p9; wait $p10; wait $p11; wait $p12; wait $p13; wait $p14; wait $p15; wait $p16; wait $p17; wait $p18; wait $p19; wait $p20; wait $p21; wait $p22; wait $p23; wait $p24; wait $p25; wait $p26; wait $p27; wait $p28; wait $p29; wait $p30; wait $p31    # each wait returns its job's status: a failed translation unit fails the build (set -e)
+$HIPCC --offload-arch=gfx950 -shared -fPIC "$OUT/tg_raster.o" "$OUT/tg_noise.o" "$OUT/tg_api.o" "$OUT/tg_contact_wave.o" "$OUT/tg_scene.o" "$OUT/tg_exchange.o" "$OUT/tg_fused.o" "$OUT/tg_broadphase.o" "$OUT/tg_api_state.o" "$OUT/tg_api_ops.o" "$OUT/tg_spin.o" "$OUT/tg_stack.o" "$OUT/tg_augment.o" "$OUT/tg_rollout.o" "$OUT/tg_replay.o" "$OUT/tg_affine.o" "$OUT/tg_vecnorm.o" "$OUT/tg_action_head.o" "$OUT/tg_conv_stem.o" "$OUT/tg_loss_head.o" "$OUT/tg_sac_loss.o" "$OUT/tg_mlp.o" "$OUT/tg_conv.o" "$OUT/tg_api_obs.o" -o "$OUT/libtactile_gym_hip.so"
 # (tg_api_obs.o, a unit without kernels, is linked last: the code objects of the units that have kernels keep the places they had in the library
 #  before it existed - profiles/obs_table_rate.txt, section 3.)
 # test infrastructure (include/tactile_gym_hip_test.h): device self-tests of the raster's division / block test and of the wave-mapped GJK / EPA,
