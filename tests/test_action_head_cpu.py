@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
+import build_units  # noqa: E402
 import action_head_ref as ref  # noqa: E402
 
 from tactile_gym_amd import _capi, spaces  # noqa: E402
@@ -439,8 +440,7 @@ def test_c_abi_entry_is_declared_bound_and_built():
     assert os.path.exists(_capi.LIB_PATH), "library not built"
     nm = subprocess.run(["nm", "-D", "--defined-only", _capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
     assert re.search(r"\bT tg_action_head\b", nm)
-    build = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", "build.sh")).read()
-    assert "cc tg_action_head -ffp-contract=off" in build and "$OUT/tg_action_head.o" in build and "fast-math" not in build
+    build_units.assert_exact_product_unit("tg_action_head")
 
 
 def test_action_head_kernels_use_no_scratch(tmp_path):

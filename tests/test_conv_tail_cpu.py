@@ -11,6 +11,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
+import build_units  # noqa: E402
 import conv_tail_ref as ref  # noqa: E402
 
 torch = pytest.importorskip("torch")
@@ -138,8 +139,7 @@ def test_abi_declarations_and_build_line():
         assert len(decl.split(",")) == n_args == len(_capi.SYMBOLS[name][1]), name
     L = _capi.lib()
     assert all(hasattr(L, n) for n in ("tg_conv_relu", "tg_conv_relu_bwd_workspace", "tg_conv_relu_bwd"))
-    build = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", "build.sh")).read()
-    assert "cc tg_conv -ffp-contract=off" in build and "$OUT/tg_conv.o" in build and "fast-math" not in build
+    build_units.assert_exact_product_unit("tg_conv")
     # the workspace query needs no device: the error's code and a text naming the limit
     ok = dict(B=1, Cin=32, H=8, W=8, Cout=64, KH=4, KW=4, stride=2)
     assert L.tg_conv_relu_bwd_workspace(*ok.values()) == 4 * (64 * 512 + 4 * 64)

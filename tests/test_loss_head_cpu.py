@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
+import build_units  # noqa: E402
 import loss_head_ref as ref  # noqa: E402
 
 from tactile_gym_amd import _capi  # noqa: E402
@@ -215,8 +216,7 @@ def test_c_abi_entries_are_declared_bound_and_built():
         assert re.search(rf"\bT {name}\b", nm), name
     for name, value in (("PATH_AUTO", 0), ("PATH_ONE", 1), ("PATH_GRID", 2), ("ONE_MAX_ROWS", 4096)):
         assert re.search(rf"#define TG_LOSS_{name} {value}\b", header) and getattr(_capi, "LOSS_" + name) == value
-    build = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", "build.sh")).read()
-    assert "cc tg_loss_head -ffp-contract=off" in build and "$OUT/tg_loss_head.o" in build and "fast-math" not in build
+    build_units.assert_exact_product_unit("tg_loss_head")
     core = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", "tg_head_core.h")).read()
     for unit in ("tg_action_head.hip", "tg_loss_head.hip"):                   # one copy of the chain, in the header both include
         text = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", unit)).read()

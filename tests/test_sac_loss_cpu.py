@@ -15,6 +15,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
+import build_units  # noqa: E402
 import sac_loss_ref as ref  # noqa: E402
 
 from tactile_gym_amd import _capi  # noqa: E402
@@ -327,8 +328,7 @@ def test_c_abi_entries_are_declared_bound_and_built():
         assert re.search(rf"\bT {name}\b", nm), name
     for name, value in (("MAX_CRITICS", 4), ("MAX_ROWS", 65536)):
         assert re.search(rf"#define TG_SAC_{name} {value}\b", header) and getattr(_capi, "SAC_" + name) == value
-    build = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", "build.sh")).read()
-    assert "cc tg_sac_loss -ffp-contract=off" in build and "$OUT/tg_sac_loss.o" in build and "fast-math" not in build
+    build_units.assert_exact_product_unit("tg_sac_loss")
     for unit in ("tg_loss_head.hip", "tg_sac_loss.hip"):                      # one copy of the chunk sum, in the header both include
         text = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", unit)).read()
         assert '#include "tg_loss_core.h"' in text and "__shfl_down(" not in text and not re.search(r"atomic\w*\s*\(", text)

@@ -14,6 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
+import build_units  # noqa: E402
 import vecnorm_ref as ref  # noqa: E402
 
 from tactile_gym_amd import _capi, spaces  # noqa: E402
@@ -436,8 +437,7 @@ def test_c_abi_entries_are_declared_bound_and_built():
     nm = subprocess.run(["nm", "-D", "--defined-only", _capi.LIB_PATH], capture_output=True, text=True, check=True).stdout
     for name in ENTRIES:
         assert re.search(r"\bT " + name + r"\b", nm), name
-    build = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", "build.sh")).read()
-    assert "cc tg_vecnorm -ffp-contract=off" in build and "fast-math" not in build
+    build_units.assert_exact_product_unit("tg_vecnorm")
 
 
 def test_vecnorm_kernels_use_no_scratch(tmp_path):
