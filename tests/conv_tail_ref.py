@@ -42,6 +42,19 @@ CASES = [
     (2, 5, 5, 32, 2, 2, 1, 800),
     (2, 3, 3, 32, 2, 2, 1, 4200),                    # M = 16800: 263 chunks over P = 64 workgroups (the cap): walks of 4 and 5 chunks
 ]
+# The paths of csrc/tg_conv.hip that CASES leaves unrun (`route` names them; tests/test_gpu_conv_tail_paths.py runs them)
+PATH_CASES = [
+    (32, 8, 8, 128, 4, 4, 2, 3),                     # k_conv_fwd's four-channel-tile wave layout (Cout >= 128), one channel block; K = 512, M = 27
+    (5, 9, 9, 160, 4, 4, 1, 15),                     # two such channel blocks, the second with one live tile; K = 80: chunks 32, 32, 16 and K % 64 = 16;
+                                                     # M = 540: P = 3 partials over three channel blocks and two k blocks
+    (40, 6, 6, 32, 3, 3, 1, 5),                      # K = 360: a last chunk of 8, K % 64 = 40; Cin = 40: k_conv_dx's second channel tile is partly valid
+    (2, 17, 18, 32, 16, 16, 1, 2),                   # a 16 x 16 kernel: ky / stride up to 15 in dx's packed table; J = 8192, most dx MFMAs skipped
+    (2, 23, 21, 64, 7, 6, 4, 3),                     # stride 4: ky % stride = 3; K = 84; non-square, three unread input columns
+    (64, 3, 3, 64, 3, 3, 3, 3),                      # the linear pair at stride 3 (H == KH decides, not the stride)
+    (6, 3, 3, 32, 3, 3, 1, 33),                      # K = 54: the generic forward, k_conv_lin_dx with 22 valid k in its second tile, two batch tiles
+    (2, 5, 5, 32, 2, 2, 1, 8),                       # M = 128 exactly: one full 128-position block, two full backward chunks
+]
+CAP_CASE = (64, 16, 16, 512, 16, 16, 1, 1025)        # the smallest shape at which 2^25 / (Cout K) = 4 binds P (ceil(M / 256) = 5): walks of 5, 4, 4, 4 chunks
 REAL_128 = [(32, 31, 31, 64, 4, 4, 2), (64, 14, 14, 64, 3, 3, 1), (64, 12, 12, 512, 12, 12, 1)]   # the three real shapes (batch invariance)
 BWD_SHARE, BWD_CHUNK, BWD_MAX_PARTS, BWD_MAX_FLOATS, BIAS_PARTS = 256, 64, 64, 1 << 25, 4        # csrc/tg_conv.hip's constants
 
@@ -56,6 +69,38 @@ def workspace_bytes(case):
     OH, OW = out_hw(H, W, KH, KW, stride)
     K = Cin * KH * KW
     return 4 * parts(B * OH * OW, Cout, K) * (Cout * K + BIAS_PARTS * Cout)
+
+
+def route(case, aligned=True):
+    """The launchers' decisions for one case (tg_conv_relu and tg_conv_relu_bwd of csrc/tg_conv.hip, restated): which kernels run and which of
+    their branches the sizes reach.  `aligned`: whether x and w are 16-byte aligned.  Entries that belong to a kernel that does not run are None."""
+    Cin, H, W, Cout, KH, KW, stride, B = case
+    OH, OW = out_hw(H, W, KH, KW, stride)
+    K, M = Cin * KH * KW, B * OH * OW
+    linear = H == KH and W == KW
+    r = dict(K=K, M=M, stride=stride)
+    r["fwd"] = "lin" if linear and K % 32 == 0 and aligned else "generic"
+    generic = r["fwd"] == "generic"
+    cl = 2 if Cout >= 128 else (1 if Cout >= 64 else 0)
+    CW = 32 << cl
+    r["fwd_cl"] = cl if generic else None
+    r["fwd_cblocks"] = -(-Cout // CW) if generic else None
+    r["fwd_last_cblock_partial"] = Cout % CW != 0 if generic else None
+    r["fwd_chunks"] = [32] * (K // 32) + ([K % 32] if K % 32 else []) if generic else None
+    r["n_kblocks"] = -(-K // 64)
+    r["k_mod_64"] = "0" if K % 64 == 0 else ("1..32" if K % 64 <= 32 else "33..63")
+    r["n_cblocks"] = -(-Cout // 64)
+    r["P"] = parts(M, Cout, K)
+    r["cap_bound"] = BWD_MAX_FLOATS // (Cout * K) < min(-(-M // BWD_SHARE), BWD_MAX_PARTS)
+    r["walks"] = sorted({len(range(p, -(-M // BWD_CHUNK), r["P"])) for p in range(r["P"])}, reverse=True)
+    r["dx"] = "lin" if linear else "generic"
+    r["dx_cl"] = (1 if Cin > 32 else 0) if not linear else None
+    r["dx_last_ctile_partial"] = Cin % 32 != 0 if not linear else None
+    r["dx_max_ky_div"] = max((KH - 1) // stride, (KW - 1) // stride) if not linear else None      # the 4-bit fields of k_conv_dx's table
+    r["dx_max_ky_mod"] = min(max(KH, KW) - 1, stride - 1) if not linear else None                   # the 2-bit fields
+    r["lin_dx_last_ktile"] = K % 32 if linear else None                                              # valid k of k_conv_lin_dx's last tile (0: full)
+    r["batch_tiles"] = -(-B // 32) if linear else None
+    return r
 
 
 def case_id(case):
@@ -113,6 +158,13 @@ def backward(x, w, y, dy, stride):
     return dict(dw=(g.T @ P).reshape(w.shape), db=g.sum(axis=0), dx=_scatter((g @ w2).reshape(shape6), x.shape, KH, KW, stride),
                 dw_bound=((M + 4) * u * (np.abs(g).T @ np.abs(P))).reshape(w.shape), db_bound=(M + 4) * u * np.abs(g).sum(axis=0),
                 dx_bound=(J + 4) * u * _scatter((np.abs(g) @ np.abs(w2)).reshape(shape6), x.shape, KH, KW, stride))
+
+
+def dweight_dbias(x, w, y, dy, stride):
+    """(dw, db) of `backward` alone, for a case too large to form dx and the bounds on the host."""
+    P = patches(x, w.shape[2], w.shape[3], stride)
+    g = np.where(np.asarray(y) > 0, np.asarray(dy, f64), 0.0).transpose(0, 2, 3, 1).reshape(-1, w.shape[0])
+    return (g.T @ P.reshape(g.shape[0], -1)).reshape(w.shape), g.sum(axis=0)
 
 
 def unread(case):
@@ -182,6 +234,12 @@ def forward_probe_sets():
             ((64, 12, 12, 512, 12, 12, 1), lin)]
 
 
+def path_forward_probe_sets():
+    """As forward_probe_sets, on k_conv_fwd's chains with a short last chunk behind full ones: K = 80 (chunks 32, 32, 16; Cout = 160) and K = 360
+    (a last chunk of 8).  Every window of three consecutive k: across the 31 / 32 and 63 / 64 chunk boundaries and into the short chunk."""
+    return [((5, 9, 9, 160, 4, 4, 1), _windows(80)), ((40, 6, 6, 32, 3, 3, 1), _windows(360))]
+
+
 def forward_probe(shape, triples):
     """(x, w, b, at): image i carries triple i in the window of output position at[i] = (oy, ox) against row co = i % Cout of w; y[i, i % Cout,
     oy, ox] must be exactly 0.  Consecutive images use different rows, so overlapping windows of k never meet in one row."""
@@ -222,6 +280,13 @@ def dx_probe_sets():
     stride 2, only ky, kx in {0, 2} exist: 256 of 1024 terms, each alone in its MFMA, most MFMAs skipped.  (64, 3, 3, 64, 3, 3, 1), (1, 2):
     OH = OW = 1, one term per co."""
     return [((4, 6, 6, 32, 3, 3, 1), (2, 2)), ((32, 8, 8, 64, 4, 4, 2), (2, 2)), ((64, 3, 3, 64, 3, 3, 1), (1, 2))]
+
+
+def path_dx_probe_sets():
+    """As dx_probe_sets, at the tops of the fields of k_conv_dx's packed table.  (4, 23, 21, 64, 7, 6, 4), (4, 4): stride 4, only ky, kx in {0, 4}
+    exist: 256 terms, each alone in its MFMA.  (3, 17, 18, 32, 16, 16, 1), (15, 15): a 16 x 16 kernel, ky in {14, 15}, kx in {13, 14, 15}: 192
+    terms with ky / stride of 14 and 15."""
+    return [((4, 23, 21, 64, 7, 6, 4), (4, 4)), ((3, 17, 18, 32, 16, 16, 1), (15, 15))]
 
 
 def dx_probe(shape, at):

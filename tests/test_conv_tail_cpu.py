@@ -36,7 +36,7 @@ def _close(got, want, rel=1e-12):
     assert np.abs(got - want).max() <= rel * max(np.abs(want).max(), 1e-300)
 
 
-@pytest.mark.parametrize("case", ref.CASES, ids=ref.case_id)
+@pytest.mark.parametrize("case", ref.CASES + ref.PATH_CASES, ids=ref.case_id)
 def test_reference_equals_torch_float64_autograd(case):
     Cin, H, W, Cout, KH, KW, stride, B = case
     rng = np.random.default_rng(1)
@@ -62,7 +62,7 @@ def test_reference_equals_torch_float64_autograd(case):
     assert (r["dx"][:, :, ref.unread(case)] == 0).all()
 
 
-@pytest.mark.parametrize("case", ref.CASES, ids=ref.case_id)
+@pytest.mark.parametrize("case", ref.CASES + ref.PATH_CASES, ids=ref.case_id)
 def test_grid_cases_are_exact_in_float32(case):
     Cin, H, W, Cout, KH, KW, stride, B = case
     x, w, b, y, dy = ref.grid_case(np.random.default_rng(2), case)        # asserts its magnitude conditions
@@ -99,11 +99,99 @@ def test_parts_rule_and_the_walking_cases():
     assert sizes == [6472704, 5345280, 18882560, 8454144, 9502720, 75530240]
 
 
+def test_the_partials_cap_in_the_workspace_query():
+    """conv_parts' cap 2^25 / (Cout K), asked of the library itself (the query needs no device)."""
+    L = _capi.lib()
+    for case, P in (((64, 12, 12, 512, 12, 12, 1, 4096), 7), ((64, 16, 16, 512, 16, 16, 1, 2000), 4), (ref.CAP_CASE, 4)):
+        Cin, H, W, Cout, KH, KW, stride, B = case
+        K = Cin * KH * KW
+        r = ref.route(case)
+        assert r["cap_bound"] and r["P"] == P == ref.BWD_MAX_FLOATS // (Cout * K) and P < min(-(-B // ref.BWD_SHARE), ref.BWD_MAX_PARTS)
+        got = L.tg_conv_relu_bwd_workspace(B, Cin, H, W, Cout, KH, KW, stride)
+        assert got == 4 * P * (Cout * K + 4 * Cout) == ref.workspace_bytes(case), case
+    assert L.tg_conv_relu_bwd_workspace(4096, 64, 12, 12, 512, 12, 12, 1) == 4 * 7 * (512 * 9216 + 4 * 512)
+    assert L.tg_conv_relu_bwd_workspace(2000, 64, 16, 16, 512, 16, 16, 1) == 4 * 4 * (512 * 16384 + 4 * 512)
+    assert not any(ref.route(c)["cap_bound"] for c in ref.CASES + ref.PATH_CASES)
+    for case in ref.PATH_CASES:
+        Cin, H, W, Cout, KH, KW, stride, B = case
+        assert L.tg_conv_relu_bwd_workspace(B, Cin, H, W, Cout, KH, KW, stride) == ref.workspace_bytes(case), case
+
+
+# Each path of csrc/tg_conv.hip's launchers and kernels as a predicate on conv_tail_ref.route's table
+ROUTES = {
+    "fwd generic, four channel tiles a workgroup (Cout >= 128)": lambda r: r["fwd"] == "generic" and r["fwd_cl"] == 2,
+    "fwd generic, four channel tiles, a second channel block partly active": lambda r: (r["fwd"] == "generic" and r["fwd_cl"] == 2
+                                                                                         and r["fwd_cblocks"] == 2 and r["fwd_last_cblock_partial"]),
+    "fwd generic, a short last chunk behind full chunks": lambda r: r["fwd"] == "generic" and len(r["fwd_chunks"]) > 1 and r["fwd_chunks"][-1] < 32,
+    "bwd, K > 64 with K % 64 in 1..32": lambda r: r["n_kblocks"] > 1 and r["k_mod_64"] == "1..32",
+    "bwd, K > 64 with K % 64 in 33..63": lambda r: r["n_kblocks"] > 1 and r["k_mod_64"] == "33..63",
+    "bwd, several partials over several channel blocks": lambda r: r["P"] > 1 and r["n_cblocks"] > 1,
+    "dx generic, two channel tiles, the second partly valid": lambda r: r["dx"] == "generic" and r["dx_cl"] == 1 and r["dx_last_ctile_partial"],
+    "dx generic, ky / stride = 15": lambda r: r["dx"] == "generic" and r["dx_max_ky_div"] == 15,
+    "dx generic, ky % stride = 3 (stride 4)": lambda r: r["dx"] == "generic" and r["dx_max_ky_mod"] == 3 and r["stride"] == 4,
+    "dx lin, a partly valid k tile over several batch tiles": lambda r: r["dx"] == "lin" and r["lin_dx_last_ktile"] > 0 and r["batch_tiles"] > 1,
+    "the linear pair at a stride above 1": lambda r: r["fwd"] == "lin" and r["dx"] == "lin" and r["stride"] > 1,
+}
+# what CASES reached before PATH_CASES: everything else of this table
+OLD_ROUTES = {
+    "fwd lin": lambda r: r["fwd"] == "lin",
+    "fwd generic, one, two and two-of-three channel tiles": lambda r: r["fwd"] == "generic" and r["fwd_cl"] in (0, 1),
+    "bwd, several partials": lambda r: r["P"] == 64,
+    "bwd, several channel blocks": lambda r: r["n_cblocks"] == 8,
+    "dx generic, two full channel tiles": lambda r: r["dx"] == "generic" and r["dx_cl"] == 1 and not r["dx_last_ctile_partial"],
+    "dx lin, full k tiles over several batch tiles": lambda r: r["dx"] == "lin" and r["lin_dx_last_ktile"] == 0 and r["batch_tiles"] == 3,
+}
+
+
+def test_route_table_names_the_paths_that_only_the_path_cases_reach():
+    old = [ref.route(c) for c in ref.CASES]
+    new = [ref.route(c) for c in ref.PATH_CASES]
+    for name, reached in {**ROUTES, **OLD_ROUTES}.items():
+        assert any(reached(r) for r in old + new), name
+    for name, reached in OLD_ROUTES.items():
+        assert any(reached(r) for r in old), name
+    for name, reached in ROUTES.items():                                      # the reason PATH_CASES exists: CASES alone reaches none of them
+        assert not any(reached(r) for r in old) and any(reached(r) for r in new), name
+    assert any(r["dx"] == "lin" and r["lin_dx_last_ktile"] > 0 for r in old)  # K = 18 at B = 1: one batch tile
+    # the forward's fall-back: a linear layer whose bases are not 16-byte aligned takes the generic kernel, with the layout its Cout gives
+    for case in ((64, 3, 3, 64, 3, 3, 1, 5), (64, 1, 1, 32, 1, 1, 1, 33)):
+        a, u = ref.route(case), ref.route(case, aligned=False)
+        assert a["fwd"] == "lin" and a["fwd_cl"] is None and u["fwd"] == "generic" and u["fwd_cl"] == (1 if case[3] == 64 else 0)
+        assert u["fwd_chunks"] == [32] * (a["K"] // 32) and u["dx"] == a["dx"] == "lin"
+    # the table against the issue's figures for each case
+    r = dict(zip(ref.PATH_CASES, new))
+    c = r[(32, 8, 8, 128, 4, 4, 2, 3)]
+    assert (c["K"], c["M"], c["fwd_cl"], c["fwd_cblocks"], c["fwd_last_cblock_partial"]) == (512, 27, 2, 1, False)
+    c = r[(5, 9, 9, 160, 4, 4, 1, 15)]
+    assert (c["fwd_chunks"], c["k_mod_64"], c["M"], c["P"], c["n_cblocks"], c["n_kblocks"], c["walks"]) == ([32, 32, 16], "1..32", 540, 3, 3, 2, [3])
+    c = r[(40, 6, 6, 32, 3, 3, 1, 5)]
+    assert (c["K"], c["fwd_chunks"][-1], c["k_mod_64"], c["fwd_cl"], c["dx_cl"]) == (360, 8, "33..63", 0, 1)
+    c = r[(2, 17, 18, 32, 16, 16, 1, 2)]
+    assert (c["K"], c["dx_max_ky_div"], c["dx_max_ky_mod"]) == (512, 15, 0)
+    c = r[(2, 23, 21, 64, 7, 6, 4, 3)]
+    assert (c["K"], c["fwd_chunks"], c["dx_max_ky_div"], c["dx_max_ky_mod"]) == (84, [32, 32, 20], 1, 3)
+    assert int(ref.unread((2, 23, 21, 64, 7, 6, 4, 3)).sum()) == 69           # three unread input columns
+    c = r[(6, 3, 3, 32, 3, 3, 1, 33)]
+    assert (c["K"], c["fwd"], c["dx"], c["lin_dx_last_ktile"], c["batch_tiles"]) == (54, "generic", "lin", 22, 2)
+    c = r[(2, 5, 5, 32, 2, 2, 1, 8)]
+    assert c["M"] == 128 and c["walks"] == [2]
+    c = ref.route(ref.CAP_CASE)
+    assert c["cap_bound"] and c["P"] == 4 and c["walks"] == [5, 4]
+    # the launchers themselves say what route restates (the source is the specification of these decisions)
+    src = open(os.path.join(ROOT, "tactile_gym_amd", "csrc", "tg_conv.hip")).read()
+    for text in ("conv_is_linear(a) && a.K % 32 == 0 && ((uintptr_t)x_dev | (uintptr_t)weight_dev) % 16 == 0",
+                 "const int32_t cl = Cout >= 128 ? 2 : (Cout >= 64 ? 1 : 0), MP = (4 >> cl) * 32, CW = 32 << cl;",
+                 "const int32_t n_kblocks = (a.K + 63) / 64, n_cblocks = (Cout + 63) / 64;",
+                 "const int32_t cl = Cin > 32 ? 1 : 0, NP = (4 >> cl) * 32;",
+                 "static bool conv_is_linear(const ConvArgs& a) { return a.H == a.KH && a.W == a.KW; }"):
+        assert text in src, text
+
+
 def test_order_probe_arithmetic():
     o = ref.probe_orders()
     assert o["ascending"] == 0 and o["reversed"] == 1 and o["pairwise"] == 1 and o["split"] == 1
     assert all(v.dtype == f32 for v in o.values())
-    for shape, triples in ref.forward_probe_sets():
+    for shape, triples in ref.forward_probe_sets() + ref.path_forward_probe_sets():
         Cin, H, W, Cout, KH, KW, stride = shape
         K, khw = Cin * KH * KW, KH * KW
         assert all(0 <= a < b < c < K for a, b, c in triples)
@@ -115,7 +203,7 @@ def test_order_probe_arithmetic():
         want, _ = ref.forward(x, w, b, stride)                               # exact arithmetic: every probed element is 2^24 + 1 - 2^24 = 1
         for i, (oy, ox) in enumerate(at):
             assert want[i, i % Cout, oy, ox] == 1.0
-    for shape, at in ref.dx_probe_sets():
+    for shape, at in ref.dx_probe_sets() + ref.path_dx_probe_sets():
         Cin, H, W, Cout, KH, KW, stride = shape
         x, w, y, dy, B = ref.dx_probe(shape, at)
         want = ref.backward(x, w, y, dy, stride)["dx"]
@@ -123,6 +211,16 @@ def test_order_probe_arithmetic():
         for i in range(B):
             assert want[i, i % Cin, at[0], at[1]] == 1.0
     assert len(ref.dx_terms((4, 6, 6, 32, 3, 3, 1), 2, 2)) == 288 and len(ref.dx_terms((32, 8, 8, 64, 4, 4, 2), 2, 2)) == 256
+    # the new chains: every window of three consecutive k of K = 80 and 360; 256 terms at stride 4, each alone in its MFMA (no two terms are
+    # neighbours in j), and 192 of the 16 x 16 kernel, all with ky / stride of 14 or 15
+    assert [len(t) for _, t in ref.path_forward_probe_sets()] == [78, 358]
+    for (shape, at), n in zip(ref.path_dx_probe_sets(), (256, 192)):
+        terms = ref.dx_terms(shape, *at)
+        assert len(terms) == n and len(ref.dx_probe(shape, at)[0]) == n - 2
+    (s4, at4), (k16, at16) = ref.path_dx_probe_sets()
+    terms = ref.dx_terms(s4, *at4)
+    assert all(b[0] - a[0] >= 2 for a, b in zip(terms, terms[1:])) and {t[4] % 4 for t in terms} == {0} and {t[4] for t in terms} == {0, 4}
+    assert {t[4] for t in ref.dx_terms(k16, *at16)} == {14, 15}
     assert len(ref.dx_terms((64, 3, 3, 64, 3, 3, 1), 1, 2)) == 64 and ref.dx_terms((4, 10, 13, 96, 3, 2, 3), 9, 0) == []
 
 

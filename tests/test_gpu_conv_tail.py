@@ -34,9 +34,10 @@ class _Space:
         self.shape, self.dtype = tuple(shape), np.uint8
 
 
-# conv2 of the 36 x 36 observation, the stride-3 layer with three channel tiles, and a linear layer in both input forms
+# conv2 of the 36 x 36 observation, the stride-3 layer with three channel tiles, a linear layer in both input forms, and two of
+# conv_tail_ref.PATH_CASES: Cout = 128 (the forward's four-channel-tile layout) and Cin = 40, K = 360 (short last chunk, partly valid dx tile)
 GRAD_CASES = [((32, 8, 8, 64, 4, 4, 2, 3), "conv"), ((4, 10, 13, 96, 3, 2, 3, 5), "conv"), ((64, 3, 3, 64, 3, 3, 1, 5), "linear4"),
-              ((64, 3, 3, 64, 3, 3, 1, 5), "linear2")]
+              ((64, 3, 3, 64, 3, 3, 1, 5), "linear2"), ((32, 8, 8, 128, 4, 4, 2, 3), "conv"), ((40, 6, 6, 32, 3, 3, 1, 5), "conv")]
 
 
 @pytest.mark.parametrize("case,form", GRAD_CASES, ids=[ref.case_id(c) + "-" + f for c, f in GRAD_CASES])
@@ -77,6 +78,30 @@ def test_gradients_against_float64_autograd(case, form):
     for k, n, g64 in (("dw", M, w64.grad), ("db", M, b64.grad), ("dx", J, x64.grad)):
         slack = rf[k + "_bound"] / ((n + 4) * 2.0 ** -23)
         assert (np.abs(got[k] - g64.numpy()) <= r[k + "_bound"] + slack).all(), k
+
+
+def test_linear_relu_gives_the_same_bytes_for_both_input_forms():
+    """[B, 64, 3, 3] is the convolution (64, 3, 3); the same data as [B, 576] is split by _split_k into (3, 16, 12).  The chain is defined by k
+    alone, so y, dx, dweight and dbias have the same bytes."""
+    import tactile_gym_amd as tg
+    from tactile_gym_amd import torch_layers
+    assert torch_layers._split_k(576) == (3, 16, 12)
+    B = 5
+    rng = np.random.default_rng(8)
+    x, w, b, _, dy = ref.random_case(rng, (64, 3, 3, 64, 3, 3, 1, B))
+    x = (x - 0.5).astype(f32)
+    out = []
+    for shape in ((B, 64, 3, 3), (B, 576)):
+        xd = torch.from_numpy(x).cuda().view(shape).requires_grad_()
+        wd, bd = torch.from_numpy(w).cuda().view(64, 576).requires_grad_(), torch.from_numpy(b).cuda().requires_grad_()
+        y = tg.linear_relu(xd, wd, bd)
+        assert y.shape == (B, 64)
+        y.backward(torch.from_numpy(dy).cuda().view(B, 64))
+        assert xd.grad.shape == shape
+        out.append((y.detach(), xd.grad.view(B, 576), wd.grad, bd.grad))
+    assert bool((out[0][0] > 0).any()) and bool((out[0][0] == 0).any()) and float(out[0][1].abs().max()) > 0
+    for a, c, name in zip(out[0], out[1], ("y", "dx", "dweight", "dbias")):
+        assert _same_bytes(a, c), name
 
 
 def test_a_no_grad_forward_keeps_nothing():
