@@ -49,6 +49,15 @@ int tg_selftest_penetration_division(int64_t* mismatches);
  * rectangles whose every pixel passes.  out: int64 [6]. */
 int tg_selftest_edge_exclusion(int64_t n, uint64_t seed, int64_t* out);
 
+/* The block raster's hit predicate (csrc/tg_raster_dev.hpp: pixel_hit - a median for the bounding box, min3 / max3 for the signs of the edge
+ * functions, s != 0 left to the NaN that the division then returns) against the chained compares of the other pixel loops, on the device,
+ * from the pixel loop's own e0..e2, s and d.  n cases of one record and one quad of four pixel centres: half random (image-sized triangles,
+ * slivers, coordinates up to 1e4, vertices on pixel centres), half forced specials (zero-area triangles in front of z, e_k = +-0, the
+ * bounding box's edge on the pixel centre, +-inf and NaN coordinates).  out[0] = pixels whose (hit, new z) differ (must be 0), out[1] =
+ * pixels hit, out[2] = pixels where the two forms' coverage booleans differ before the depth test (d is NaN there, or it counts in
+ * out[0]), out[3] = pixels of forced specials.  out: int64 [4]. */
+int tg_selftest_pixel_predicate(int64_t n, uint64_t seed, int64_t* out);
+
 /* The tactile render (tg_render_tactile / tg_render_tactile_heightfield) with a chosen raster kernel.  TG_RK_AUTO = the product's choice
  * (csrc/tg_raster.hip: choose_render_kernel); any other id is launched if it can draw the input and refused (-1, nothing launched) if not:
  * the block kernel above 32 triangles, 128-wide tiles on a 64-wide image, a heightfield kernel for a mesh, and so on. */

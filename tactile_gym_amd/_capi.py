@@ -378,6 +378,7 @@ TEST_SYMBOLS = {
     "tg_selftest_division": (C.c_int, [C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
     "tg_selftest_penetration_division": (C.c_int, [C.POINTER(C.c_int64)]),
     "tg_selftest_edge_exclusion": (C.c_int, [C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
+    "tg_selftest_pixel_predicate": (C.c_int, [C.c_int64, C.c_uint64, C.POINTER(C.c_int64)]),
     "tg_selftest_render_kernel": (C.c_int, [C.POINTER(TgSensor), C.POINTER(TgMesh), C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "tg_selftest_translate_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_uint64, C.c_uint64,

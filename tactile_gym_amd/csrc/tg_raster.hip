@@ -974,8 +974,9 @@ void raster_debug_stats() {}
 //   workgroup that starts late on its CU is no longer held up in its latency chains by the drawing of those that started before it.
 // Against k_render_small (two workgroups per image, each lane carrying 8 quads spread over its half): half the set-ups, 4096 instead of
 // 8192 wavefronts at 1024 envs, no wavefront whose share of the image is the whole contact patch, a third of the HBM traffic.  The pixel
-// arithmetic is that of the other kernels, expression by expression; the depth test keeps the smallest d, so neither the record order
-// nor the conservative skips can change the image.  DESIGN.md 4.2 has the measurements and the per-phase timeline.
+// arithmetic is that of the other kernels, expression by expression (the hit's booleans are pixel_hit's, tg_raster_dev.hpp: the same
+// decision in half the compares); the depth test keeps the smallest d, so neither the record order nor the conservative skips can
+// change the image.  DESIGN.md 4.2 has the measurements and the per-phase timeline.
 #ifndef TG_BLK_NQ
 #define TG_BLK_NQ 3
 #endif
@@ -1258,17 +1259,21 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
             if (qlow - rmg >= zmax) continue;
             TG_PASS_LIVE();
             const float a0 = r.y2 - fy, a1 = r.y1 - fy, a2 = r.y0 - fy;
+            // The four pixels one after the other: the empty asm makes pixel p's centre depend on pixel p - 1's result (it emits nothing and
+            // changes no value), so -O3's SLP vectoriser cannot pair one pixel's f32 arithmetic with the next one's.  Paired across the pixels
+            // (v_pk_mul_f32 / v_pk_add_f32 / v_pk_fma_f32, two issue slots each on this part, plus the moves that build the register pairs)
+            // this pass is 196 issue slots and the kernel needs 101 VGPRs; so it is 192 and 80 (profiles/blk_issue.txt).  Building the whole
+            // unit without SLP is better still (170 slots, 72 VGPRs) but is a build change: see there.
 #pragma unroll
             for (int p = 0; p < 4; ++p) {
-                const float fx = (float)(qx + p) + 0.5f;
+                float fx = (float)(qx + p) + 0.5f;
+                if (p > 0) asm("" : "+v"(fx) : "v"(z[p > 0 ? p - 1 : 0]));
                 const float e0 = (r.x1 - fx) * a0 - (r.x2 - fx) * a1;
                 const float e1 = (r.x2 - fx) * a2 - (r.x0 - fx) * a0;
                 const float e2 = (r.x0 - fx) * a1 - (r.x1 - fx) * a2;
-                const bool box = (fx >= r.xmin) & (fx <= r.xmax);
-                const bool pos = (e0 >= 0.0f) & (e1 >= 0.0f) & (e2 >= 0.0f), neg = (e0 <= 0.0f) & (e1 <= 0.0f) & (e2 <= 0.0f);
                 const float s = (e0 + e1) + e2;
                 const float d = div_mid_range((e0 * r.d0 + e1 * r.d1) + e2 * r.d2, s);
-                const bool hit = box & (pos | neg) & (s != 0.0f) & (d < z[p]);
+                const bool hit = pixel_hit(fx, r.xmin, r.xmax, e0, e1, e2, d, z[p]);     // = box & (pos | neg) & (s != 0) & (d < z)
                 z[p] = hit ? d : z[p];
             }
         }
@@ -1358,11 +1363,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
                     const float e0 = (r.x1 - fx) * a0 - (r.x2 - fx) * a1;
                     const float e1 = (r.x2 - fx) * a2 - (r.x0 - fx) * a0;
                     const float e2 = (r.x0 - fx) * a1 - (r.x1 - fx) * a2;
-                    const bool box = (fx >= r.xmin) & (fx <= r.xmax);
-                    const bool pos = (e0 >= 0.0f) & (e1 >= 0.0f) & (e2 >= 0.0f), neg = (e0 <= 0.0f) & (e1 <= 0.0f) & (e2 <= 0.0f);
                     const float s = (e0 + e1) + e2;
                     const float d = div_mid_range((e0 * r.d0 + e1 * r.d1) + e2 * r.d2, s);
-                    const bool hit = box & (pos | neg) & (s != 0.0f) & (d < z[j][p]);
+                    const bool hit = pixel_hit(fx, r.xmin, r.xmax, e0, e1, e2, d, z[j][p]);     // = box & (pos | neg) & (s != 0) & (d < z)
                     z[j][p] = hit ? d : z[j][p];
                 }
             }

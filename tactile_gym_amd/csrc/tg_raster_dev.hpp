@@ -41,6 +41,31 @@ __device__ __forceinline__ float div_mid_range(float a, float b) {
     return q;
 }
 
+// The pixel loops' hit predicate  box & (pos | neg) & (s != 0) & (d < z)  with
+//     box = (fx >= xmin) & (fx <= xmax),  pos = (e0 >= 0) & (e1 >= 0) & (e2 >= 0),  neg = (e0 <= 0) & (e1 <= 0) & (e2 <= 0),
+//     s = (e0 + e1) + e2,  d = div_mid_range((e0 d0 + e1 d1) + e2 d2, s)
+// in 5 compares instead of 10 and 3 mask operations instead of 9 (each compare writes a scalar mask that the scalar unit then combines).
+// e0..e2, s and d are the caller's, computed as before; only the booleans differ, and the result is the same for EVERY input for which
+// xmin <= xmax or both are NaN - emit() makes them as fminf / fmaxf chains over the same three values, so that always holds:
+//   * s != 0 is implied by d < z.  For s == +-0 div_mid_range returns NaN whatever the numerator: rcp(+-0) = +-inf and its Newton step is
+//     fma(-/+0, +-inf, 1) = NaN, which every later fma carries into d; NaN < z is false.  For s != 0 the term was true.
+//   * pos | neg.  v_min_f32 / v_max_f32 (IEEE mode: minNum / maxNum) return the other operand when one is NaN, and of +-0 either - both
+//     satisfy >= 0 and <= 0.  With no NaN among e0..e2 (+-inf included: they order like any other value) lo is the smallest and hi the
+//     largest, so lo >= 0 <=> all three >= 0 and hi <= 0 <=> all three <= 0: identical.  With a NaN among them the chained form is false
+//     and this one may be true - but then s, a sum over all three, is NaN, d is NaN, and d < z is false on both sides.
+//   * box.  fx is a pixel centre: finite and never zero.  v_med3_f32 of three non-NaN values is the median, so for xmin <= xmax it is fx
+//     clamped to [xmin, xmax], which equals fx exactly when xmin <= fx <= xmax (infinite bounds included; a zero bound of either sign
+//     never compares equal to fx != 0 by accident).  With a NaN among its operands v_med3_f32 returns min3, which ignores NaNs: fx when
+//     both bounds are NaN, so box is true here and false in the chained form.  Both bounds NaN means all three x_k are NaN (fminf / fmaxf
+//     drop a NaN beside a number), so every e_k is NaN, d is NaN, and d < z is false on both sides.
+// tg_selftest_pixel_predicate (tg_selftest.hip) evaluates both forms on the device, specials forced in; tests/test_raster_predicate_cpu.py
+// restates the argument over the grid of special values.
+__device__ __forceinline__ bool pixel_hit(float fx, float xmin, float xmax, float e0, float e1, float e2, float d, float z) {
+    const bool box = __builtin_amdgcn_fmed3f(fx, xmin, xmax) == fx;
+    const float lo = fminf(fminf(e0, e1), e2), hi = fmaxf(fmaxf(e0, e1), e2);
+    return box & ((lo >= 0.0f) | (hi <= 0.0f)) & (d < z);
+}
+
 __device__ __forceinline__ void project_vertex(float cx, float cy, float cw, const RasterParams& P, float& sx, float& sy, float& d) {
     float iw = 1.0f / cw;
     sx = P.hw + P.kx * (cx * iw);
