@@ -205,6 +205,12 @@ typedef struct tg_body_state_test {
     const int32_t* goal_id;
 } tg_body_state_test;
 int tg_selftest_set_body_state(tg_ctx* ctx, const tg_body_state_test* state);
+/* Reads back the reset template of a context (State.reset_tmpl; csrc/tg_state_test.hip): the arm's post-reset state that the reset kernels
+ * keep from the first move that ran through.  The context's stream is synchronised first.  *n_words = the template's size in doubles; out
+ * [cap] receives them.  With N = the arm's joints: [0, N) q, [N, 2N) qd, [2N] reset ticks, [2N + 1] valid (0: not published yet), and in
+ * object_push [2N + 2] path points, [2N + 3] the tip sphere's radius, [2N + 4 + 3k] the sphere's centre before tick k and, last, at the
+ * final pose.  -1: a NULL argument, a context without a template (*n_words = 0), cap < *n_words.  -2: a HIP call failed. */
+int tg_selftest_get_reset_template(tg_ctx* ctx, double* out, int32_t cap, int32_t* n_words);
 /* The message of the last failing call of this library on the calling thread. */
 const char* tg_selftest_last_error(void);
 

@@ -401,6 +401,7 @@ TEST_SYMBOLS = {
     "tg_selftest_stack": (C.c_int, [C.POINTER(TgStackTest), C.c_void_p]),
     "tg_selftest_physics": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp]),
     "tg_selftest_set_body_state": (C.c_int, [_ctx, C.POINTER(TgBodyStateTest)]),
+    "tg_selftest_get_reset_template": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(C.c_int32)]),
     "tg_selftest_last_error": (C.c_char_p, []),
 }
 # raster kernel ids of tg_selftest_render (TG_RK_*)

@@ -732,7 +732,7 @@ static int alloc_balance(tg_ctx* c) {
         if (getenv("TG_RESET_BANK")) tmpl = !reset_bank_env_off();
         if (cfg.solver_residual_threshold > 0.0) tmpl = false;   // threshold mode: the reset tick's truncated solve sees the fallen object (1e-6 rad): every reset is recomputed
         if (spin) tmpl = true;                                    // (its literal reset moves the arm with the spool only: the template is that state)
-        if (tmpl && dev_alloc(c, s.reset_tmpl, (2 * TG_MAX_DOF + 2) * 8)) return -2;
+        if (tmpl && dev_alloc(c, s.reset_tmpl, (size_t)kBodyTmplWords * 8)) return -2;
     }
     // load_object (base_object_env.py:66-70): loadURDF puts the object's *link* frame at init_obj_pos; the inertial frame used by
     // get/resetBasePositionAndOrientation is obj_root_inertial_pos away.  setup_object (:185-190): default embed distance.
@@ -779,7 +779,7 @@ static int alloc_push(tg_ctx* c) {
     // the arm's post-reset state + the tip's path (k_reset_contact_wave's reset template); off with reset_bank = TG_BANK_OFF / TG_RESET_BANK=0 and in
     // threshold mode (the truncated solve couples the arm to the object's rows)
     const bool tmpl = cfg.reset_bank != TG_BANK_OFF && !(cfg.solver_residual_threshold > 0.0) && !reset_bank_env_off();
-    if (tmpl && dev_alloc(c, s.reset_tmpl, (size_t)(2 * TG_MAX_DOF + 4 + 3 * 64) * 8)) return -2;
+    if (tmpl && dev_alloc(c, s.reset_tmpl, (size_t)kPushTmplWords * 8)) return -2;
     // at init_obj_pos / init_obj_orn (object_push_env.py:154-160)
     double oq[4], oR[9];
     h_quat_from_euler(cfg.obj_init_rpy, oq);

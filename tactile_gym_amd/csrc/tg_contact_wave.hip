@@ -2008,10 +2008,21 @@ __global__ __launch_bounds__(64) void k_reset_contact_wave(const DevRobot<T>* __
     for (int i = 0; i < N; ++i) { q[i] = m.rest_q[i]; qd[i] = T(0); }
     const FreeBody<T> b0 = load_body<T>(st, n, env);
     int used = 0, ccode = 0;
-    constexpr int kTmplPath = 64;
     const bool tmpl_can = SHAPE == 0 && optimistic != 0 && NT == 1 && !(m.res_thr > T(0)) && st.reset_tmpl != nullptr;
     bool tmpl_valid = false;
     if (tmpl_can) tmpl_valid = st.reset_tmpl[2 * N + 1] != 0.0;
+    // Both shortcuts below freeze the old object where the episode left it, while the reference goes on simulating it during the move: a cube that the
+    // tip was pushing when the episode ended slides on at 0.01 m/s while the arm is already back at its rest pose.  So the clear test allows for
+    // what the object can have travelled: before tick k it asks for 4 mm + k dt (|v| + rho |w|), with v, w the object's velocities at the episode's
+    // end and rho its farthest point from the centre (the cube's half diagonal, the old marble's radius) - no point of an object whose speed does not
+    // grow gets further than that.  The 4 mm themselves are spent as 1.2 mm where a contact begins (margins 1.1 mm + breaking 0.1 mm), 1 mm for the
+    // tip's travel in the tick after a test (joint steps of 0.001 rad) and 1.8 mm for what the speed bound does not cover: a cube that tips over from
+    // rest picks up speed (0.2 mm in 13 ticks from 44 degrees on an edge).  Friction is given no credit: a sliding cube stops within 0.1 mm.
+    // A cube sliding at 0.5 m/s has to be 31 mm away to keep an MG400 reset on its template; NaN velocities compare false: the literal move.
+    T rho;
+    if constexpr (SHAPE == 1) rho = (T)old_mr;
+    else rho = tsqrt(c.push.half[0] * c.push.half[0] + c.push.half[1] * c.push.half[1] + c.push.half[2] * c.push.half[2]);
+    const T drift = (norm(b0.v) + rho * norm(b0.w)) * c.dt;           // what the old object may travel in a tick
     bool took_template = false;
     if (uniform_true(tmpl_valid)) {
         const int npts = (int)st.reset_tmpl[2 * N + 2];
@@ -2021,7 +2032,7 @@ __global__ __launch_bounds__(64) void k_reset_contact_wave(const DevRobot<T>* __
             const V3<T> cw = mk((T)st.reset_tmpl[2 * N + 4 + 3 * k2], (T)st.reset_tmpl[2 * N + 5 + 3 * k2], (T)st.reset_tmpl[2 * N + 6 + 3 * k2]);
             const V3<T> loc = mulT(b0.R, cw - b0.pos);
             const T ox = tmax(tabs(loc.x) - c.push.half[0], T(0)), oy = tmax(tabs(loc.y) - c.push.half[1], T(0)), oz = tmax(tabs(loc.z) - c.push.half[2], T(0));
-            clear = clear && (tsqrt(ox * ox + oy * oy + oz * oz) - bs_r > T(0.004));
+            clear = clear && (tsqrt(ox * ox + oy * oy + oz * oz) - bs_r > T(0.004) + (T)k2 * drift);
         }
         if (uniform_true(clear)) {
 #pragma unroll
@@ -2113,10 +2124,12 @@ __global__ __launch_bounds__(64) void k_reset_contact_wave(const DevRobot<T>* __
     // takes the template: no tick at all (the same bits the optimistic move would produce - it is deterministic); otherwise it moves as above.
     // object_roll's start pose depends on the episode's marble: no template there.  The contact code a reset leaves behind is the object's
     // table contacts where the episode left it (the literal move reports those of its last tick: the same set for an object at rest).
-    const bool record = tmpl_can && !tmpl_valid;           // this move may become the template: leave the sphere's path behind
+    // While it moves an env keeps the path to itself, in LDS behind the hull (launch_reset_wave_t adds the 3 * kTmplPath words), and only a move that
+    // ran through unviolated stores any of it.  A move that is abandoned - the tip near the old cube, or on it in the first tick - leaves no word behind.
+    const bool record = tmpl_can && !tmpl_valid;           // this move may become the template: keep the sphere's path
     int n_path = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
-    bool violated = false;
+    bool violated = false, clear0 = false;                 // clear0: the tip was clear before the first tick as well (that tick is a contact tick)
     n_path = 0;
 #pragma unroll
     for (int i = 0; i < N; ++i) { q[i] = m.rest_q[i]; qd[i] = T(0); }
@@ -2173,9 +2186,7 @@ __global__ __launch_bounds__(64) void k_reset_contact_wave(const DevRobot<T>* __
             const T ident[9] = {T(1), T(0), T(0), T(0), T(1), T(0), T(0), T(0), T(1)}, z3[3] = {T(0), T(0), T(0)};
             link_frame<T, TOPO>(k, c.push.tip_link, z3, ident, ol, Rl);
             const V3<T> cw = ol + mul(Rl, bs_c);
-            if (record && w0 && n_path < kTmplPath - 1) {
-                st.reset_tmpl[2 * N + 4 + 3 * n_path] = (double)cw.x; st.reset_tmpl[2 * N + 5 + 3 * n_path] = (double)cw.y; st.reset_tmpl[2 * N + 6 + 3 * n_path] = (double)cw.z;
-            }
+            if (record && w0 && n_path < kTmplPath - 1) { L[xbase + 3 * n_path] = cw.x; L[xbase + 3 * n_path + 1] = cw.y; L[xbase + 3 * n_path + 2] = cw.z; }
             ++n_path;
             const V3<T> bp = mk(L[kLBody + 0], L[kLBody + 1], L[kLBody + 2]);
             T dist;
@@ -2188,8 +2199,8 @@ __global__ __launch_bounds__(64) void k_reset_contact_wave(const DevRobot<T>* __
                 const T ox = tmax(tabs(loc.x) - c.push.half[0], T(0)), oy = tmax(tabs(loc.y) - c.push.half[1], T(0)), oz = tmax(tabs(loc.z) - c.push.half[2], T(0));
                 dist = tsqrt(ox * ox + oy * oy + oz * oz);
             }
-            arm_only = dist - bs_r > T(0.004);
-            if (it == 0) arm_only = false;
+            arm_only = dist - bs_r > T(0.004) + (T)it * drift;
+            if (it == 0) { clear0 = uniform_true(arm_only); arm_only = false; }
             else if (!uniform_true(arm_only)) { violated = true; break; }
         }
         TG_PHASE_FENCE()
@@ -2203,9 +2214,11 @@ __global__ __launch_bounds__(64) void k_reset_contact_wave(const DevRobot<T>* __
         if (uniform_true(pos_err < T(2e-4) && tacos(ca) < T(1e-3) && total_v < T(0.1))) break;
     }
     if (!violated) {
-        if (record && !literal && n_path < kTmplPath - 1) {
-            // this move ran through with the tip clear: it is the template.  Every env that gets here writes the same values (the move is a function
-            // of constants); the flag goes last, behind a fence, and is read at kernel start only (a later launch sees all of it).
+        if (record && !literal && clear0 && n_path < kTmplPath - 1) {
+            // this move ran through with the tip clear before EVERY tick, the first included (a move of one tick never meets the test above, and a
+            // tip on the old cube in that tick moves the arm): it is the template.  Every env that gets here writes the same values (the move is
+            // a function of constants); the flag goes last, behind a fence and a barrier.  A reset reads it once, at its start: a later launch sees all of it,
+            // and a workgroup of this launch that starts late may see it too - the words it then reads are the ones fenced out before the flag.
 #pragma unroll
             for (int i = 0; i < N; ++i) { q[i] = L[kLQ + i]; qd[i] = L[kLQd + i]; }
             Kin<T, TOPO> kf;
@@ -2214,16 +2227,19 @@ __global__ __launch_bounds__(64) void k_reset_contact_wave(const DevRobot<T>* __
             const T ident[9] = {T(1), T(0), T(0), T(0), T(1), T(0), T(0), T(0), T(1)}, z3[3] = {T(0), T(0), T(0)};
             link_frame<T, TOPO>(kf, c.push.tip_link, z3, ident, ol, Rl);
             const V3<T> cw = ol + mul(Rl, bs_c);
+            if (w0) { L[xbase + 3 * n_path] = cw.x; L[xbase + 3 * n_path + 1] = cw.y; L[xbase + 3 * n_path + 2] = cw.z; }
+            __syncthreads();
+            for (int w = lane; w < 3 * (n_path + 1); w += 64) st.reset_tmpl[2 * N + 4 + w] = (double)L[xbase + w];
             if (w0) {
-                st.reset_tmpl[2 * N + 4 + 3 * n_path] = (double)cw.x; st.reset_tmpl[2 * N + 5 + 3 * n_path] = (double)cw.y; st.reset_tmpl[2 * N + 6 + 3 * n_path] = (double)cw.z;
 #pragma unroll
                 for (int i = 0; i < N; ++i) { st.reset_tmpl[i] = (double)q[i]; st.reset_tmpl[N + i] = (double)qd[i]; }
                 st.reset_tmpl[2 * N] = (double)used;
                 st.reset_tmpl[2 * N + 2] = (double)(n_path + 1);
                 st.reset_tmpl[2 * N + 3] = (double)bs_r;
-                __threadfence();
-                st.reset_tmpl[2 * N + 1] = 1.0;
             }
+            __threadfence();                                         // every lane's: the path is out before the flag ...
+            __syncthreads();                                         // ... whichever lane's stores were the last to leave
+            if (w0) st.reset_tmpl[2 * N + 1] = 1.0;
         }
         break;
     }
@@ -2288,7 +2304,8 @@ void launch_wave_t(int control_mode, int n, int n_tip, hipStream_t stream, const
 
 template <typename T, int TOPO, int SHAPE>
 void launch_reset_wave_t(int n, int n_tip, hipStream_t stream, const void* d_robot, const void* d_const, const State& st, const uint8_t* d_mask, int narrowphase = 0) {
-    const size_t lds_bytes = contact_lds_words(SHAPE, n_tip, narrowphase) * sizeof(T);
+    // (object_push, closed forms: room behind the hull for the tip sphere's path of a move that may become the reset template)
+    const size_t lds_bytes = (contact_lds_words(SHAPE, n_tip, narrowphase) + (SHAPE == 0 && !narrowphase ? 3 * kTmplPath : 0)) * sizeof(T);
     if constexpr (SHAPE == 0 && sizeof(T) == 8) {
         if (narrowphase) {
             hipLaunchKernelGGL((k_reset_contact_wave<T, TOPO, 0, true, 4>), dim3(n), dim3(64), lds_bytes, stream, (const DevRobot<T>*)d_robot,

@@ -54,6 +54,9 @@ template <typename T> struct EnvConst {
     double obj_init_rpy[3];
 };
 
+constexpr int kTmplPath = 64;                                        // points of object_push's reset template path (k_reset_contact_wave)
+constexpr int kPushTmplWords = 2 * TG_MAX_DOF + 4 + 3 * kTmplPath;   // State.reset_tmpl of object_push: q, qd, ticks, valid, points, radius, path
+constexpr int kBodyTmplWords = 2 * TG_MAX_DOF + 2;                   // ... of object_balance: q, qd, ticks, valid
 struct State {   // device pointers, SoA [field][num_envs]
     double *q, *qd, *qd_target, *tcp_pos, *tcp_rpy, *edge_ang, *embed;
     float *stim_xform, *term_xform, *reward;   // term_xform: camera<-stimulus transform of the terminal observation (fused reset)
@@ -75,7 +78,8 @@ struct State {   // device pointers, SoA [field][num_envs]
     double *body_pos, *body_rot, *body_v, *body_w, *ext_pos, *gravity;   // [3][n], [9][n], [3][n], [3][n], [3][n], [n]
     uint8_t* ext_pending;           // [n]
     unsigned long long* tmpl_stats; // [2] object_push: resets that took the reset template / that ran their blocking move (k_reset_contact_wave); null otherwise
-    double* reset_tmpl;             // [2 N + 2] object_balance: the arm's state after Robot.reset (q, qd, ticks used, valid flag) - see k_reset_body
+    double* reset_tmpl;             // [2 N + 2] object_balance: the arm's state after Robot.reset (q, qd, ticks used, valid flag) - see k_reset_body;
+                                    // object_push: kPushTmplWords, with the tip sphere's path behind them - see k_reset_contact_wave
     double* ball;                   // [13][n] ball_on_plate: position, linear velocity, angular velocity, one-shot torque, last normal impulse
     double* dish;                   // [20][n] spinning_plate: the dish's base position (0-2), orientation (3-11, row major), linear (12-14) and angular (15-17)
                                     // velocity, the last tick's summed normal impulse (18) and number of contact points (19); null otherwise

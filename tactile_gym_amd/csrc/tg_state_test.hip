@@ -103,3 +103,18 @@ extern "C" int tg_selftest_set_body_state(tg_ctx* c, const tg_body_state_test* s
     TG_HIP(hipStreamSynchronize(c->stream));
     return 0;
 }
+
+// State.reset_tmpl as the reset kernels left it.  Its size is the allocation's (tg_kernels.hpp: kPushTmplWords, kBodyTmplWords).
+extern "C" int tg_selftest_get_reset_template(tg_ctx* c, double* out, int32_t cap, int32_t* n_words) {
+    if (!c || !n_words) return fail(-1, "tg_selftest_get_reset_template: NULL argument");
+    *n_words = 0;
+    if (c->st.reset_tmpl == nullptr) return fail(-1, "tg_selftest_get_reset_template: this context has no reset template");
+    const int words = c->cfg.env_kind == TG_ENV_OBJECT_PUSH ? kPushTmplWords : kBodyTmplWords;
+    *n_words = words;
+    if (!out || cap < words) return fail(-1, "tg_selftest_get_reset_template: out holds fewer than *n_words doubles");
+    TG_ENTER(c);
+    TG_HIP(hipStreamSynchronize(c->stream));
+    TG_HIP(hipMemcpyAsync(out, c->st.reset_tmpl, (size_t)words * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    TG_HIP(hipStreamSynchronize(c->stream));
+    return 0;
+}

@@ -18,7 +18,7 @@ def make_oracle(family, i, arm="ur5", sensor="tactip", narrowphase=None, max_ste
     return getattr(ref_env, f["oracle"])(seed=f["seed"] + i, max_steps=max_steps, image_size=(SIZE, SIZE), env_modes=modes, **kw)
 
 
-def make_venv(family, arm="ur5", sensor="tactip", narrowphase=None, mapping="wave", max_steps=50):
+def make_venv(family, arm="ur5", sensor="tactip", narrowphase=None, mapping="wave", max_steps=50, auto_reset=False):
     import tactile_gym_amd as tg
     f = FAMILIES[family]
     modes = dict(f["modes"])
@@ -28,7 +28,7 @@ def make_venv(family, arm="ur5", sensor="tactip", narrowphase=None, mapping="wav
         kw["narrowphase"] = narrowphase or "closed_form"
     if family in ("ball", "spin"):
         kw = {}                                   # one mapping each: a lane per env / a wavefront per env
-    return tg.make_vec(f["env_id"], num_envs=N_ENVS, max_steps=max_steps, image_size=[SIZE, SIZE], env_modes=modes, seed=f["seed"], auto_reset=False, **kw)
+    return tg.make_vec(f["env_id"], num_envs=N_ENVS, max_steps=max_steps, image_size=[SIZE, SIZE], env_modes=modes, seed=f["seed"], auto_reset=auto_reset, **kw)
 
 
 def tip_gap(o):
