@@ -915,6 +915,38 @@ int tg_sac_actor_loss(const float* log_prob_dev, const float* const* q_pi_dev, i
                       float ent_coef, float target_entropy, int32_t want_ent_coef_loss, float* stats_out, float* dlog_prob_out,
                       float* const* dq_pi_out, void* hip_stream);
 
+/* ---- device Adam: torch.nn.utils.clip_grad_norm_ and torch.optim.Adam's step over a list of tensors ----------------------------
+ * Context free; the launches go to hip_stream, nothing is allocated or synchronised.  The tensors are n_tensors (>= 1) separate contiguous float32
+ * device arrays of counts[i] >= 1 elements, named by HOST arrays of device pointers; counts, step_size and bias_corr2_sqrt are host arrays too,
+ * all read before the call returns.  The tensors are cut into chunks of TG_OPTIM_CHUNK elements, a tensor's last chunk short, a chunk never
+ * across two tensors; the chunks are numbered in the order of the call and one workgroup takes one chunk.  The kernels take their tensor
+ * table by value, TG_OPTIM_MAX_TENSORS tensors a launch: more tensors are more launches, nothing else.
+ *
+ * tg_optim_sumsq: partials_dev[c] = the sum over chunk c of (double) g (double) g, for every chunk of the call (the caller's memory, at least
+ * the bytes that tg_optim_workspace returns for the call's chunk count).  Lane t of 256 adds elements 4 (256 k + t) + j of the chunk, k = 0 ..
+ * 3 outer, j = 0 .. 3 inner; the lanes by the tree v[i] += v[i + off], off = 32 .. 1 inside each wave, then the four wave sums in wave order: an
+ * order that depends on the counts alone, not on the addresses.
+ *
+ * tg_optim_adam: with clip != 0, sum = ((0 + partials[0]) + partials[1]) + ... over n_partials (the chunk count of the tg_optim_sumsq call,
+ * which may have covered more tensors than this call), total = (float) sqrt(sum), coef = max_norm / (total + 1e-6f), 1 where that exceeds 1 (a
+ * NaN stays); *total_norm_out = total.  Every workgroup forms these itself, in that order.  Then per element, in float32 with one rounding
+ * per operation, w1 = (float) (1 - beta1), w2 = (float) (1 - beta2), b2 = (float) beta2:
+ *     g' = g coef (clip != 0);  g'' = g' + weight_decay p (weight_decay != 0);  m = m + w1 (g'' - m);  v = v b2 + w2 (g'' g'');
+ *     den = sqrt(v) / bias_corr2_sqrt[i] + eps;  p = p + step_size[i] (m / den)
+ * with the caller's step_size[i] = (float) (-lr / (1 - beta1^step)) and bias_corr2_sqrt[i] = (float) sqrt(1 - beta2^step) of tensor i.  g is
+ * read, never written.  Errors, each without a launch: n_tensors < 1, a NULL array or tensor, a count < 1, more than 2^31 - 1 chunks; for
+ * tg_optim_sumsq a NULL or too small partials_dev; for tg_optim_adam with clip != 0 a max_norm that is negative or a NaN, a NULL partials_dev
+ * or total_norm_out, n_partials < 1.  tg_optim_workspace returns the negative code for a chunk count < 1. */
+#define TG_OPTIM_CHUNK 4096
+#define TG_OPTIM_MAX_TENSORS 64
+int64_t tg_optim_workspace(int64_t n_chunks);
+int tg_optim_sumsq(int32_t n_tensors, const float* const* grads_dev, const int64_t* counts, double* partials_dev, int64_t workspace_bytes,
+                   void* hip_stream);
+int tg_optim_adam(int32_t n_tensors, float* const* params_dev, const float* const* grads_dev, float* const* exp_avg_dev,
+                  float* const* exp_avg_sq_dev, const int64_t* counts, const float* step_size, const float* bias_corr2_sqrt, double beta1,
+                  double beta2, float eps, float weight_decay, int32_t clip, float max_norm, const double* partials_dev, int64_t n_partials,
+                  float* total_norm_out, void* hip_stream);
+
 /* ---- device MLP towers: stable_baselines3's policy, value and critic heads -----------------------------------------------------
  * Context free; the launches go to hip_stream, nothing is allocated or synchronised.  A tower is a chain of n_layers layers (1 ..
  * TG_MLP_MAX_LAYERS):  z_l = h_{l-1} W_l^T + b_l,  h_l = act_l(z_l),  W_l torch's float32 [out][in], every out in 1 .. TG_MLP_MAX_WIDTH.  A call

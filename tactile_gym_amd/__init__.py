@@ -25,6 +25,7 @@ loudly when the HIP library or a GPU is missing.
     actor_loss, ent_coef_loss, stats = tg.sac_actor_loss(log_prob, q_pi, log_ent_coef=log_ent_coef, target_entropy=-A)              # its actor and entropy-coefficient losses, one launch
     critic_stats, actor_stats, n_updates = tg.train.sac_train(actor, critic, critic_target, actor_opt, critic_opt, rb, head, 1, 64, 0.95, 0.005, log_ent_coef=log_ent_coef, ent_coef_optimizer=ent_opt, target_entropy=-A)   # SAC.train over the device pieces
     heads = tg.ActorCriticHeads(features_dim, A, dict(pi=[256, 256], vf=[256, 256])); policy = lambda obs: heads(extractor(obs))   # SB3's MlpExtractor, action_net and value_net in one launch (tg.mlp; imports torch); tg.SacActorHeads, tg.ContinuousCriticHeads: SAC's
+    opt = tg.DeviceAdam(params, lr=3e-4, eps=1e-5); opt.step(max_grad_norm=0.5)   # clip_grad_norm_ and Adam's step over every tensor in two launches (tg.optim; imports torch); SB3: optimizer_class=tg.DeviceAdam
     CustomCombinedExtractor(observation_space, cnn_base=tg.NatureCNN)   # SB3's NatureCNN, its first layer one launch on the uint8 images (tg.torch_layers; imports torch)
     CustomCombinedExtractor(observation_space, cnn_base=functools.partial(tg.NatureCNN, device_tail=True))   # and conv2, conv3 and the linear layer in HIP too: a row's features have one arithmetic order whatever the batch (tg.conv_relu, tg.linear_relu)
 """
@@ -36,7 +37,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("augment", "rollout", "replay", "vecnorm", "action_head", "collect", "torch_layers", "loss_head", "train", "mlp"):   # imported on first use: they need torch, the rest of the package does not
+    if name in ("augment", "rollout", "replay", "vecnorm", "action_head", "collect", "torch_layers", "loss_head", "train", "mlp", "optim"):   # imported on first use: they need torch, the rest of the package does not
         import importlib
         return importlib.import_module("." + name, __name__)
     if name == "DeviceRolloutBuffer":
@@ -60,4 +61,7 @@ def __getattr__(name):
     if name in ("mlp_towers", "ActorCriticHeads", "SacActorHeads", "ContinuousCriticHeads"):
         import importlib
         return getattr(importlib.import_module(".mlp", __name__), name)
+    if name == "DeviceAdam":
+        import importlib
+        return importlib.import_module(".optim", __name__).DeviceAdam
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -37,6 +37,7 @@ VECNORM_MAX_ARRAYS, VECNORM_MAX_WIDTH, VECNORM_MAX_ROWS = 4, 512, 65535   # TG_V
 HEAD_GAUSSIAN, HEAD_SQUASHED, HEAD_UNIFORM, HEAD_MAX_ACT = 0, 1, 2, 16   # TG_HEAD_* (tg_action_head)
 LOSS_PATH_AUTO, LOSS_PATH_ONE, LOSS_PATH_GRID, LOSS_ONE_MAX_ROWS = 0, 1, 2, 4096   # TG_LOSS_* (tg_ppo_loss)
 SAC_MAX_CRITICS, SAC_MAX_ROWS = 4, 65536   # TG_SAC_* (tg_sac_critic_loss, tg_sac_actor_loss)
+OPTIM_CHUNK, OPTIM_MAX_TENSORS = 4096, 64   # TG_OPTIM_* (tg_optim_sumsq, tg_optim_adam)
 STEM_KERNEL, STEM_STRIDE, STEM_OUT, STEM_MAX_CIN = 8, 4, 32, 12   # TG_STEM_* (tg_conv_stem, tg_conv_stem_bwd)
 CONV_MAX_CIN, CONV_COUT_STEP, CONV_MAX_COUT, CONV_MAX_KERNEL, CONV_MAX_STRIDE, CONV_MAX_POSITIONS = 64, 32, 512, 16, 4, 536870880   # TG_CONV_* (tg_conv_relu, tg_conv_relu_bwd)
 MLP_MAX_TOWERS, MLP_MAX_LAYERS, MLP_MAX_WIDTH, MLP_MAX_IN, MLP_MAX_ROWS = 4, 4, 256, 1024, 2147483616   # TG_MLP_* (tg_mlp_forward, tg_mlp_backward)
@@ -293,6 +294,11 @@ SYMBOLS = {
                                      C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tg_sac_actor_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_float, C.c_float, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tg_optim_workspace": (C.c_int64, [C.c_int64]),
+    "tg_optim_sumsq": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p, C.c_int64, C.c_void_p]),
+    "tg_optim_adam": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                C.POINTER(C.c_int64), _fp, _fp, C.c_double, C.c_double, C.c_float, C.c_float, C.c_int32, C.c_float, C.c_void_p,
+                                C.c_int64, C.c_void_p, C.c_void_p]),
     "tg_get_state": (C.c_int, [_ctx, C.POINTER(TgStateView)]),
     "tg_set_joint_state": (C.c_int, [_ctx, _dp, _dp]),
     "tg_copy_step_licence": (C.c_int, [_ctx, C.POINTER(C.c_int32)]),

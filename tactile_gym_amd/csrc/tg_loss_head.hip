@@ -13,6 +13,7 @@
 //   k_ppo_chunks   one workgroup per chunk: the rows' outputs, the chunk's sums into the workspace     } path 2, the same device functions
 //   k_ppo_finish   one workgroup: the chunk sums in ascending order, the finish                        }
 // The work is latency bound; what the calls buy is the dozens of torch launches they replace.
+//   tg_optim_workspace, tg_optim_sumsq, tg_optim_adam   the device Adam (tactile_gym_amd.optim) over tg_optim.h's kernels
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -20,6 +21,7 @@
 #include "tg_exchange.h"   // report_error
 #include "tg_head_core.h"  // the draw and the per-element chains, shared with tg_action_head.hip
 #include "tg_loss_core.h"  // the chunk and its sum (wave_sum, slot_put, slot_get), shared with tg_sac_loss.hip
+#include "tg_optim.h"      // the device Adam's kernels: under this unit's flag, their entries at the end of this file
 
 namespace tg {
 
@@ -473,5 +475,80 @@ extern "C" int tg_squashed_rsample_bwd(const float* g_actions_dev, const float* 
     const dim3 grid((unsigned)((B + tg::kLossThreads - 1) / tg::kLossThreads)), block(tg::kLossThreads);
     hipLaunchKernelGGL(tg::k_squashed_rsample_bwd, grid, block, 0, (hipStream_t)hip_stream, a);
     if (hipGetLastError() != hipSuccess) return report_error(-2, "tg_squashed_rsample_bwd: the kernel launch failed");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the device Adam (tg_optim.h)
+extern "C" int64_t tg_optim_workspace(int64_t n_chunks) {
+    if (n_chunks < 1 || n_chunks > INT32_MAX) return tg::report_error(-1, "tg_optim_workspace: need 1 <= n_chunks <= 2^31 - 1");
+    return n_chunks * (int64_t)sizeof(double);
+}
+
+extern "C" int tg_optim_sumsq(int32_t n_tensors, const float* const* grads_dev, const int64_t* counts, double* partials_dev,
+                              int64_t workspace_bytes, void* hip_stream) {
+    using tg::report_error;
+    if (n_tensors < 1) return report_error(-1, "tg_optim_sumsq: need n_tensors >= 1");
+    if (!grads_dev || !counts) return report_error(-1, "tg_optim_sumsq: NULL grads_dev or counts");
+    for (int32_t i = 0; i < n_tensors; ++i)
+        if (!grads_dev[i]) return report_error(-1, "tg_optim_sumsq: NULL tensor in grads_dev");
+    const int64_t chunks = tg::optim_chunks(n_tensors, counts);
+    if (chunks == -1) return report_error(-1, "tg_optim_sumsq: need every count >= 1");
+    if (chunks < 0) return report_error(-1, "tg_optim_sumsq: more than 2^31 - 1 chunks");
+    if (!partials_dev || workspace_bytes < chunks * (int64_t)sizeof(double))
+        return report_error(-1, "tg_optim_sumsq: partials_dev needs tg_optim_workspace(chunks) bytes");
+    hipStream_t s = (hipStream_t)hip_stream;
+    tg::OptimTable tb = {};
+    tb.partials = partials_dev;
+    tg::optim_launches(
+        tb, n_tensors, counts, [&](tg::OptimTensor& row, int32_t i) { row.g = grads_dev[i]; },
+        [&](const tg::OptimTable& t, unsigned grid) { hipLaunchKernelGGL(tg::k_optim_sumsq, dim3(grid), dim3(tg::kLossThreads), 0, s, t); });
+    if (hipGetLastError() != hipSuccess) return report_error(-2, "tg_optim_sumsq: a kernel launch failed");
+    return 0;
+}
+
+extern "C" int tg_optim_adam(int32_t n_tensors, float* const* params_dev, const float* const* grads_dev, float* const* exp_avg_dev,
+                             float* const* exp_avg_sq_dev, const int64_t* counts, const float* step_size, const float* bias_corr2_sqrt,
+                             double beta1, double beta2, float eps, float weight_decay, int32_t clip, float max_norm,
+                             const double* partials_dev, int64_t n_partials, float* total_norm_out, void* hip_stream) {
+    using tg::report_error;
+    if (n_tensors < 1) return report_error(-1, "tg_optim_adam: need n_tensors >= 1");
+    if (!params_dev || !grads_dev || !exp_avg_dev || !exp_avg_sq_dev) return report_error(-1, "tg_optim_adam: NULL pointer array");
+    if (!counts || !step_size || !bias_corr2_sqrt) return report_error(-1, "tg_optim_adam: NULL counts, step_size or bias_corr2_sqrt");
+    for (int32_t i = 0; i < n_tensors; ++i)
+        if (!params_dev[i] || !grads_dev[i] || !exp_avg_dev[i] || !exp_avg_sq_dev[i]) return report_error(-1, "tg_optim_adam: NULL tensor");
+    const int64_t chunks = tg::optim_chunks(n_tensors, counts);
+    if (chunks == -1) return report_error(-1, "tg_optim_adam: need every count >= 1");
+    if (chunks < 0) return report_error(-1, "tg_optim_adam: more than 2^31 - 1 chunks");
+    if (clip) {
+        if (!(max_norm >= 0.0f)) return report_error(-1, "tg_optim_adam: need max_norm >= 0");
+        if (!partials_dev || n_partials < 1) return report_error(-1, "tg_optim_adam: the clip needs partials_dev and n_partials >= 1");
+        if (!total_norm_out) return report_error(-1, "tg_optim_adam: the clip needs total_norm_out");
+    }
+    hipStream_t s = (hipStream_t)hip_stream;
+    tg::OptimTable tb = {};
+    tb.partials = const_cast<double*>(partials_dev);
+    tb.total_norm = total_norm_out;
+    tb.n_partials = clip ? n_partials : 0;
+    tb.w1 = (float)(1.0 - beta1);
+    tb.w2 = (float)(1.0 - beta2);
+    tb.b2 = (float)beta2;
+    tb.eps = eps;
+    tb.wd = weight_decay;
+    tb.max_norm = max_norm;
+    tg::optim_launches(
+        tb, n_tensors, counts,
+        [&](tg::OptimTensor& row, int32_t i) {
+            row.p = params_dev[i];
+            row.g = grads_dev[i];
+            row.m = exp_avg_dev[i];
+            row.v = exp_avg_sq_dev[i];
+            row.ss = step_size[i];
+            row.bc2s = bias_corr2_sqrt[i];
+        },
+        [&](const tg::OptimTable& t, unsigned grid) {
+            if (clip) hipLaunchKernelGGL(tg::k_optim_adam<true>, dim3(grid), dim3(tg::kLossThreads), 0, s, t);
+            else hipLaunchKernelGGL(tg::k_optim_adam<false>, dim3(grid), dim3(tg::kLossThreads), 0, s, t);
+        });
+    if (hipGetLastError() != hipSuccess) return report_error(-2, "tg_optim_adam: a kernel launch failed");
     return 0;
 }

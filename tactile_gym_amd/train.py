@@ -25,6 +25,7 @@ SB3's ContinuousCritic does.
 import torch
 
 from .loss_head import ppo_loss, sac_actor_loss, sac_critic_loss
+from .optim import DeviceAdam
 
 __all__ = ["ppo_train", "sac_train", "polyak_update"]
 
@@ -35,8 +36,10 @@ def ppo_train(policy, optimizer, buf, n_epochs, batch_size, clip_range, clip_ran
     advantages normalised per minibatch.  Per minibatch: mean, log_std, values = policy(observations); tg.ppo_loss; optimizer.zero_grad();
     loss.backward(); clip_grad_norm_ over the optimiser's parameters (max_grad_norm=None: none); optimizer.step().  target_kl: training stops
     before the step of the first minibatch whose approx_kl exceeds 1.5 target_kl, as in SB3 - that 4-byte read per minibatch is the only host
-    read; None reads nothing.  Returns the last minibatch's stats (float32 [8], on the device; loss_head.STATS), None when there was none."""
+    read; None reads nothing.  With a tg.DeviceAdam the clip and the step are optimizer.step(max_grad_norm=max_grad_norm): two launches, and
+    p.grad keeps backward's values (max_grad_norm=None then means the optimiser's own max_grad_norm).  Returns the last minibatch's stats (float32 [8], on the device; loss_head.STATS), None when there was none."""
     params = [p for group in optimizer.param_groups for p in group["params"]]
+    device_adam = isinstance(optimizer, DeviceAdam)
     stats = None
     for _ in range(n_epochs):
         for batch in buf.get(batch_size, augment=augment, out_dtype=torch.float32 if out_dtype is None else out_dtype):
@@ -48,6 +51,9 @@ def ppo_train(policy, optimizer, buf, n_epochs, batch_size, clip_range, clip_ran
                 return stats
             optimizer.zero_grad()
             loss.backward()
+            if device_adam:                           # the clip and the step in two launches
+                optimizer.step(max_grad_norm=max_grad_norm)
+                continue
             if max_grad_norm is not None:
                 torch.nn.utils.clip_grad_norm_(params, max_grad_norm)
             optimizer.step()
